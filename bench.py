@@ -111,6 +111,43 @@ def cpu_baseline(sc, X, Y, Z, budget_s=12.0):
     return out, plane  # plane: the oracle's state of planes z = 0..mt_planes-1
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+DUMP_FULL_VOXELS = 1 << 22  # state planes up to this many voxels are written whole
+DUMP_SAMPLE = 1 << 20  # larger ones: this many voxels at fixed, seeded places
+
+
+def dump_outputs(path, state, merged=None, X=None, Y=None, Z=None):
+    """--dump-outputs: what the timed path's last step left for its caller, as float32 / float64
+    .npy files under `path`.  `state`: the carved state plane (nz, Y, X) uint8 of rank 0 (bit 0
+    occupied, bit 1 seen) -- whole when small, else at DUMP_SAMPLE flat indices drawn with seed 0
+    (`state_sample_index.npy`), plus per-row counts of occupied and seen voxels over the whole
+    plane.  `merged` (N > 1): the whole grid's packed occupancy after the collective (bytes,
+    Z planes of X*Y bits, little-endian) -- occupied voxels per row and at the same kind of sample."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    flat = state.reshape(-1)
+    if flat.size <= DUMP_FULL_VOXELS:
+        arrays["state"] = state.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(flat.size, size=DUMP_SAMPLE, replace=False))
+        arrays["state_sample_index"] = idx.astype(np.float64)
+        arrays["state_sample"] = flat[idx].astype(np.float32)
+    arrays["occupied_per_row"] = (state & 1).sum(axis=2, dtype=np.int64).astype(np.float32)
+    arrays["seen_per_row"] = ((state >> 1) & 1).sum(axis=2, dtype=np.int64).astype(np.float32)
+    if merged is not None:
+        planes = merged.reshape(Z, X * Y // 8)
+        rows = planes.reshape(Z, Y, X // 8) if X % 8 == 0 else planes
+        arrays["merged_occupied_per_row"] = np.bitwise_count(rows).sum(axis=-1, dtype=np.int64).astype(np.float32)
+        n = Z * Y * X
+        idx = np.sort(np.random.default_rng(1).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+        arrays["merged_sample_index"] = idx.astype(np.float64)
+        arrays["merged_sample"] = ((merged[idx >> 3] >> (idx & 7).astype(np.uint8)) & 1).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def block_noise_masks(V, H, W, block, seed=0):
     """Masks of random block x block pixel squares, half of them background: every pixel
     rectangle larger than a square is "mixed", so the rectangle tests settle next to nothing --
@@ -341,6 +378,11 @@ def main():
     ap.add_argument("--no-workloads", action="store_true",
                     help="skip the `workloads` array (the other BASELINE configurations, a worst "
                          "case for the culling and the 1024^3 target with parity)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step computed -- the carved state "
+                         "(whole, or a fixed seeded sample of a large one) and its per-row counts; "
+                         "N > 1: also the merged occupancy -- as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -568,7 +610,7 @@ def main():
         overflowed = any(xs.overflowed() for xs in exs)
         # the slot of the LAST job: its planes are what the last exchange merged
         last = (nstep[0] - 1) % jobs
-        merged_plane = None
+        merged_plane = merged_bytes = None
         if ex is not None:  # (`packets`: expanded here, on demand -- after the timed region)
             for c in ctxs:
                 c.set_exchange_stream(0)
@@ -594,7 +636,7 @@ def main():
         if rank == 0:
             occ = float((st & 1).mean())
             if ex is not None:  # the merged plane must hold this rank's planes
-                got = merged_plane.cpu().numpy().view(np.uint8)
+                merged_bytes = got = merged_plane.cpu().numpy().view(np.uint8)
                 got = got.reshape(Z, X * Y // 8)[ctx.planes]
                 mine = np.packbits((st.reshape(len(ctx.planes), -1) & 1).astype(np.uint8),
                                    axis=1, bitorder="little")
@@ -610,7 +652,7 @@ def main():
         kern_ms = None if kern_ms != kern_ms else kern_ms  # (no NaN in the JSON line)
         views_ms = None if views_ms != views_ms else views_ms
         return dict(X=X, Y=Y, Z=Z, V=V, dt=dt, dts=dts, kern_ms=kern_ms, views_ms=views_ms, sc=sc, occ=occ,
-                    state=st if (world == 1 and rank == 0) else None,
+                    state=st if rank == 0 else None, merged=merged_bytes,
                     nplanes=nplanes, layout=layout, ev_steps=len(ev), nvox=nvox_global, merge_ok=merge_ok[0],
                     jobs=jobs, slots_agree=slots_agree,
                     overflowed=overflowed, exchange_bytes_per_rank=xbytes)
@@ -1003,6 +1045,9 @@ def main():
         except Exception as ex:  # noqa: BLE001
             out["workloads"] = [{"error": f"{type(ex).__name__}: {ex}"}]
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, r["state"], r["merged"], r["X"], r["Y"], r["Z"])
+        out["dump_outputs"] = args.dump_outputs
     if rank == 0:
         print(json.dumps(out))
     if world > 1:

@@ -53,6 +53,37 @@ def test_one_gpu_line():
     assert d["vs_baseline"] is None and d["scaling"] == "weak"
 
 
+def test_dump_outputs(tmp_path, oracle):
+    """--dump-outputs: the same arguments write the same files, and what they hold is the carved
+    model of the timed path (a 128^3 state plane is written whole): the oracle's, voxel for voxel."""
+    import numpy as np
+    from ar_voxel_project_amd import synthetic
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "128", "--steps", "4",
+                            "--warmup", "1", "--rounds", "1", "--extra-grid", "0", "--no-workloads",
+                            "--no-ablation", "--no-e2e", "--no-cpu", "--jobs-in-flight", "0",
+                            "--dump-outputs", str(d)],
+                           capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = last_json_line(r.stdout)
+        assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["dump_outputs"] == str(d)
+    names = sorted(os.listdir(dirs[0]))
+    assert names == ["occupied_per_row.npy", "seen_per_row.npy", "state.npy"]
+    assert sorted(os.listdir(dirs[1])) == names
+    total = 0
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    sc = synthetic.sphere_scene(128, 36)
+    want = oracle.carve(128, 128, 128, sc.voxel_size, sc.M, sc.masks, threads=os.cpu_count() or 1)
+    state = np.load(dirs[0] / "state.npy")
+    assert np.array_equal(state, want.astype(np.float32))
+    assert np.array_equal(np.load(dirs[0] / "occupied_per_row.npy"), (want & 1).sum(axis=2))
+
+
 @pytest.mark.parametrize("jobs", [1, 4])
 def test_two_rank_rehearsal_every_collective(jobs):
     # jobs = 1: the driver's line (one job after the other, the hand-off on side streams beside the
