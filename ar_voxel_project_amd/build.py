@@ -51,7 +51,25 @@ def build_host_tests() -> str:
     build_library()
     _make("tests/cpp")
     _make("tools/cpp", "all")  # arvx_bench6 (the reference's -c=6 table), arvx_dropin_time
+    build_weld_host_test()
     return os.path.join(ROOT, "tests", "cpp", "test_host")
+
+
+def build_weld_host_test() -> str:
+    """g++ -> tests/cpp/test_weld_host: arvx::weldMesh (include/arvx/marching_cubes.hpp) on a mesh
+    from a file; the layer is header-only over libarvx.so, which is built first if missing."""
+    lib_dir = os.path.join(ROOT, "ar_voxel_project_amd", "lib")
+    if not os.path.exists(os.path.join(lib_dir, "libarvx.so")):
+        build_library()
+    src = os.path.join(ROOT, "tests", "cpp", "test_weld_host.cpp")
+    exe = os.path.join(ROOT, "tests", "cpp", "test_weld_host")
+    cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra",
+           "-I" + os.path.join(ROOT, "include"), "-pthread", "-o", exe, src, "-L" + lib_dir, "-larvx",
+           "-Wl,-rpath," + lib_dir]
+    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if res.returncode != 0:
+        raise RuntimeError(f"{' '.join(cmd)} failed:\n{res.stdout}")
+    return exe
 
 
 if __name__ == "__main__":

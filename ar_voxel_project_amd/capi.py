@@ -51,7 +51,7 @@ SYMBOLS = [
     "arvx_colors_upload", "arvx_closure", "arvx_closure_count", "arvx_closure_download",
     "arvx_closure_download32",
     "arvx_mc_cells", "arvx_mc_cells_download", "arvx_mc_mesh", "arvx_mc_mesh_download",
-    "arvx_mc_mesh_download_faces",
+    "arvx_mc_mesh_download_faces", "arvx_mc_mesh_welded", "arvx_mc_mesh_welded_download",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
     "arvx_export_model", "arvx_get_stats", "arvx_selftest_divide", "arvx_selftest_round",
@@ -616,6 +616,35 @@ class Context:
             assert np.array_equal(v2, verts) and np.array_equal(faces[:, 3:], rgb)
             assert np.array_equal(faces[:, :3], t3[:, None] + np.arange(3, dtype=np.uint32))
         return verts, rgb
+
+    def mc_mesh_welded(self, apply_unseen: bool = False, vertex_colors: bool = False):
+        """The mesh of mc_mesh with shared vertices (arvx_mc_mesh_welded): (verts (V, 3) float32
+        in voxel units, ascending (z, y, x), faces (T, 3) uint32 vertex indices, face_rgb (T, 3)
+        uint32[, vertex_rgb (V, 3) float32 when vertex_colors])."""
+        nv, nt = C.c_int64(), C.c_int64()
+        self._lib.arvx_mc_mesh_welded.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_int64)]
+        self._lib.arvx_mc_mesh_welded_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p]
+        self._ck(self._lib.arvx_mc_mesh_welded(self._h, int(apply_unseen), C.byref(nv),
+                                               C.byref(nt)))
+        verts = np.empty((nv.value, 3), np.float32)
+        records = np.empty((nt.value, 6), np.uint32)  # i0, i1, i2, r, g, b
+        vrgb = np.empty((nv.value, 3), np.float32) if vertex_colors else None
+        self._ck(self._lib.arvx_mc_mesh_welded_download(
+            self._h, verts.ctypes.data, records.ctypes.data,
+            vrgb.ctypes.data if vrgb is not None else None))
+        out = (verts, np.ascontiguousarray(records[:, :3]), np.ascontiguousarray(records[:, 3:]))
+        return out + (vrgb,) if vertex_colors else out
+
+    def mc_mesh_welded_count(self, apply_unseen: bool = False):
+        """arvx_mc_mesh_welded without the download: (V, T); the mesh stays on the device."""
+        nv, nt = C.c_int64(), C.c_int64()
+        self._lib.arvx_mc_mesh_welded.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64),
+                                                  C.POINTER(C.c_int64)]
+        self._ck(self._lib.arvx_mc_mesh_welded(self._h, int(apply_unseen), C.byref(nv),
+                                               C.byref(nt)))
+        return int(nv.value), int(nt.value)
 
     def mc_mesh_count(self, apply_unseen: bool = False) -> int:
         """arvx_mc_mesh without the download: the triangles stay on the device."""

@@ -31,6 +31,7 @@
 #include "fast_carve_kernels.h"
 #include "mc_kernels.h"
 #include "mc_mesh_kernels.h"
+#include "mc_weld_kernels.h"
 #include "exchange_kernels.h"
 #include <algorithm>
 
@@ -2742,6 +2743,119 @@ int arvx_mc_mesh_download_faces(arvx_ctx *ctx, float *verts, uint32_t *faces) {
                                 hipMemcpyDeviceToHost, ctx->stream));
         ARVX_SYNC(ctx);
     }
+    return ARVX_OK;
+}
+
+// The welded mesh (mc_weld_kernels.h): vertex plane, cells, triangles and vertices, all launched
+// before the call's ONE synchronisation, as in arvx_mc_mesh; the three lists' lengths come back
+// together, and a mesh that outgrew its buffers is built once more with room for all of it.
+int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int64_t *triangles) {
+    ARVX_CHECK_CTX(ctx);
+    if (!vertices || !triangles) return fail(ARVX_ERR_INVALID, "null argument");
+    if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
+        return fail(ARVX_ERR_STATE, "arvx_mc_mesh_welded needs a whole-grid context (vertex indices "
+                                    "are ranks in the whole grid)");
+    if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
+        return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d",
+                    ctx->closure_unseen);
+    ctx->free_mc();
+    ctx->weld_ready = false;
+    ctx->weld_verts = ctx->weld_tris = 0;
+    *vertices = *triangles = 0;
+    // the vertex plane: occupied voxels with an empty 6-neighbour, in the occupancy the cell walk
+    // reads (the records: closure fills included); its chunk counts come with it
+    const int XW = (ctx->X + 63) / 64;
+    const arvx::BitGrid g{ctx->X, ctx->Y, ctx->Z, XW};
+    const size_t nw = (size_t)XW * ctx->Y * ctx->Z;
+    ARVX_HIP(ctx->pool_weld_planes.reserve(2 * nw * sizeof(unsigned long long)));
+    ARVX_HIP(ctx->pool_weld_rank.reserve(nw * sizeof(arvx::SparseWord)));
+    unsigned long long *d_occ = (unsigned long long *)ctx->pool_weld_planes.p, *d_vtx = d_occ + nw;
+    arvx::SparseWord *d_rank = (arvx::SparseWord *)ctx->pool_weld_rank.p;
+    if (int rc = launch_bit_pack(ctx, g, 0, 0, d_occ, nullptr)) return rc;
+    int *d_counts = nullptr;
+    if (int rc = chunk_counts(ctx, nw, &d_counts)) return rc;
+    hipLaunchKernelGGL(arvx::bit_surface_count_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0,
+                       ctx->stream, d_occ, g, 0, ctx->Z, d_vtx, d_counts);
+    ARVX_HIP(hipGetLastError());
+    // room: what the last welded mesh needed, or a surface's share of the voxels
+    long long ccap = mc_cells_cap(ctx);
+    long long tcap = (long long)(ctx->pool_weld_faces.cap / (6 * sizeof(unsigned)));
+    if (tcap <= 0) tcap = 2 * ccap;
+    long long vcap = (long long)(ctx->pool_weld_index.cap / sizeof(int));
+    if (vcap <= 0) vcap = ccap;
+    long long ncells = 0, ntris = 0, nverts = 0;
+    for (int attempt = 0;; ++attempt) {
+        ARVX_HIP(ctx->pool_weld_index.reserve((size_t)vcap * sizeof(int)));
+        ARVX_HIP(ctx->pool_weld_verts.reserve((size_t)vcap * 3 * sizeof(float)));
+        ARVX_HIP(ctx->pool_weld_rgb.reserve((size_t)vcap * 3 * sizeof(float)));
+        ARVX_HIP(ctx->pool_weld_faces.reserve((size_t)tcap * 6 * sizeof(unsigned)));
+        const long long *d_nverts = nullptr;
+        if (int rc = bit_compact(ctx, d_vtx, nw, g, vcap, (int *)ctx->pool_weld_index.p, d_rank, 4,
+                                 &d_nverts))
+            return rc;
+        const long long *d_ncells = nullptr;
+        if (int rc = mc_cells_launch(ctx, ccap, &d_ncells)) return rc;
+        arvx::McMeshParams mp;
+        carve_geometry(ctx, mp.g);
+        mp.g.rec = ctx->d_rec;
+        mp.paint = paint_plane(ctx);
+        mp.apply_unseen = apply_unseen ? 1 : 0;
+        mp.col = colour_list(ctx);
+        mp.col_rgba = ctx->d_surf_rgba;
+        mp.clo = closure_list(ctx);
+        mp.clo_rgba = (const float4 *)ctx->d_clo_rgba;
+        ARVX_HIP(ctx->pool_mesh_off.reserve((size_t)(ccap + 1) * sizeof(int)));
+        int *d_off = (int *)ctx->pool_mesh_off.p;
+        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, 3, nullptr))
+            return rc;
+        hipLaunchKernelGGL(arvx::mc_weld_tri_kernel, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0,
+                           ctx->stream, mp, arvx::SparseList{d_rank}, (const int4 *)ctx->d_mc_cells, ccap,
+                           d_ncells, tcap, d_off, (unsigned *)ctx->pool_weld_faces.p);
+        ARVX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(arvx::mc_weld_vertex_kernel, dim3((unsigned)((vcap + 255) / 256)), dim3(256), 0,
+                           ctx->stream, mp, (const int *)ctx->pool_weld_index.p, vcap, d_nverts,
+                           (float *)ctx->pool_weld_verts.p, (float *)ctx->pool_weld_rgb.p);
+        ARVX_HIP(hipGetLastError());
+        ARVX_SYNC(ctx);
+        ncells = host_total(ctx, 2);
+        ntris = host_total(ctx, 3);
+        nverts = host_total(ctx, 4);
+        if (ncells < 0 || ntris < 0 || nverts < 0) return fail(ARVX_ERR_HIP, "the scans left no count");
+        if ((ncells <= ccap && ntris <= tcap && nverts <= vcap) || attempt) break;
+        if (ncells > ccap) {
+            tcap = std::max(tcap, ntris + 5 * (ncells - ccap));
+            ccap = ncells + ncells / 8;
+        }
+        if (ntris > tcap) tcap = ntris + ntris / 8;
+        if (nverts > vcap) vcap = nverts + nverts / 8;
+    }
+    if (ncells == 0) ctx->d_mc_cells = nullptr;
+    ctx->mc_count = ncells;
+    ctx->mc_ready = true;
+    ctx->weld_verts = nverts;
+    ctx->weld_tris = ntris;
+    ctx->weld_ready = true;
+    *vertices = nverts;
+    *triangles = ntris;
+    return ARVX_OK;
+}
+
+int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
+    if ((ctx->weld_verts > 0 && !verts) || (ctx->weld_tris > 0 && !faces))
+        return fail(ARVX_ERR_INVALID, "null argument");
+    if (ctx->weld_verts > 0) {
+        ARVX_HIP(hipMemcpyAsync(verts, ctx->pool_weld_verts.p, (size_t)ctx->weld_verts * 12,
+                                hipMemcpyDeviceToHost, ctx->stream));
+        if (vertex_rgb)
+            ARVX_HIP(hipMemcpyAsync(vertex_rgb, ctx->pool_weld_rgb.p, (size_t)ctx->weld_verts * 12,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (ctx->weld_tris > 0)
+        ARVX_HIP(hipMemcpyAsync(faces, ctx->pool_weld_faces.p, (size_t)ctx->weld_tris * 24,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
     return ARVX_OK;
 }
 

@@ -194,6 +194,12 @@ struct Ctx {
     DevPool pool_surf_index, pool_surf_rgb, pool_surf_depth, pool_surf_has, pool_clo_index,
         pool_clo_rgba, pool_mc_cells, pool_raw_masks, pool_mesh_verts, pool_mesh_rgb, pool_mesh_off;
     int64_t mesh_tris = 0;  // triangles of the last arvx_mc_mesh
+    // arvx_mc_mesh_welded: the occupancy and vertex planes, the vertex plane's ranks and list, and
+    // the welded mesh (positions, vertex colours, face records)
+    DevPool pool_weld_planes, pool_weld_rank, pool_weld_index, pool_weld_verts, pool_weld_rgb,
+        pool_weld_faces;
+    int64_t weld_verts = 0, weld_tris = 0;
+    bool weld_ready = false;
     void release_pools() {
         pool_surf_index.release();
         pool_surf_rgb.release();
@@ -207,6 +213,13 @@ struct Ctx {
         pool_mesh_verts.release();
         pool_mesh_rgb.release();
         pool_mesh_off.release();
+        pool_weld_planes.release();
+        pool_weld_rank.release();
+        pool_weld_index.release();
+        pool_weld_verts.release();
+        pool_weld_rgb.release();
+        pool_weld_faces.release();
+        weld_ready = false;
         pool_xscratch.release();
         pool_vstrip.release();
         vstrip_key = 0;

@@ -59,6 +59,38 @@ __device__ __forceinline__ unsigned mc_mean3(float a, float b, float c) {
     return (unsigned)roundf(s / 3.f);
 }
 
+// Step A of the triangle kernels (mc_mesh_kernel, mc_weld_kernels.h): the triangles of one cell as
+// packed descriptors in the wave's LDS rows t0 .. t0 + nt - 1 -- word 0: x + 1 | (y + 1) << 16,
+// word 1: z + 1 | offset bits << 16 (bit 3 v + axis: offset of vertex v along the axis) -- with no
+// memory traffic beyond the table row, read as ONE 16-byte load.
+template <int kRow>
+__device__ __forceinline__ void mc_cell_descriptors(const int4 cell, int t0, uint32_t (*mine)[kRow]) {
+    // corner i of ProcessVoxel (src/MarchingCubes.h:537-552); bit i of idx set = NOT in the model
+    // x offsets of corners 0..7: 1 0 0 1 1 0 0 1; y: 0 0 1 1 0 0 1 1; z: 0 0 0 0 1 1 1 1
+    constexpr unsigned kCx = 0x99u, kCy = 0xCCu, kCz = 0xF0u;
+    const int idx = cell.w & 255;
+    const int nt = kMcTri.n[idx];
+    const uint4 rw = *reinterpret_cast<const uint4 *>(kMcTri.e[idx]);  // 16 edge numbers
+    const unsigned long long elo = (unsigned long long)rw.x | ((unsigned long long)rw.y << 32),
+                             ehi = (unsigned long long)rw.z | ((unsigned long long)rw.w << 32);
+    // (cell coordinates start at -1: stored + 1; grids are at most 16384 wide)
+    const uint32_t w0 = (uint32_t)(cell.x + 1) | ((uint32_t)(cell.y + 1) << 16);
+    for (int k = 0; k < nt; ++k) {
+        unsigned bits = 0;  // bit 3 v + axis: offset of vertex v along the axis
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+            const int j = 3 * k + v;
+            const int e = (int)(((j < 8 ? elo >> (8 * j) : ehi >> (8 * (j - 8)))) & 15ull);
+            const int a = e & 7, b = mc::kSecondCorner[e];  // e % 8 and its partner (:491)
+            const int cn = ((idx >> a) & 1) ? b : a;         // the corner that is in the model
+            bits |= (((kCx >> cn) & 1u) | (((kCy >> cn) & 1u) << 1) | (((kCz >> cn) & 1u) << 2))
+                    << (3 * v);
+        }
+        mine[t0 + k][0] = w0;
+        mine[t0 + k][1] = (uint32_t)(cell.z + 1) | (bits << 16);
+    }
+}
+
 constexpr int kMeshMaxTris = 5;  // Bourke's table: at most five triangles per cell
 
 // The triangles of the 64 consecutive cells of a wave are one contiguous range of the output
@@ -93,33 +125,7 @@ __global__ __launch_bounds__(256) void mc_mesh_kernel(const McMeshParams p,
     const long long base = tri_offset[c0];
     const int ntri = (int)(tri_offset[clast] - base) + kMcTri.n[cells[clast].w & 255];
     uint32_t(*mine)[5] = s_tri[wave];
-    // corner i of ProcessVoxel (src/MarchingCubes.h:537-552); bit i of idx set = NOT in the model
-    // x offsets of corners 0..7: 1 0 0 1 1 0 0 1; y: 0 0 1 1 0 0 1 1; z: 0 0 0 0 1 1 1 1
-    constexpr unsigned kCx = 0x99u, kCy = 0xCCu, kCz = 0xF0u;
-    if (c < n) {  // ---- A
-        const int4 cell = cells[c];
-        const int idx = cell.w & 255;
-        const int t0 = (int)(tri_offset[c] - base), nt = kMcTri.n[idx];
-        const uint4 rw = *reinterpret_cast<const uint4 *>(kMcTri.e[idx]);  // 16 edge numbers
-        const unsigned long long elo = (unsigned long long)rw.x | ((unsigned long long)rw.y << 32),
-                                 ehi = (unsigned long long)rw.z | ((unsigned long long)rw.w << 32);
-        // (cell coordinates start at -1: stored + 1; grids are at most 16384 wide)
-        const uint32_t w0 = (uint32_t)(cell.x + 1) | ((uint32_t)(cell.y + 1) << 16);
-        for (int k = 0; k < nt; ++k) {
-            unsigned bits = 0;  // bit 3 v + axis: offset of vertex v along the axis
-#pragma unroll
-            for (int v = 0; v < 3; ++v) {
-                const int j = 3 * k + v;
-                const int e = (int)(((j < 8 ? elo >> (8 * j) : ehi >> (8 * (j - 8)))) & 15ull);
-                const int a = e & 7, b = mc::kSecondCorner[e];  // e % 8 and its partner (:491)
-                const int cn = ((idx >> a) & 1) ? b : a;         // the corner that is in the model
-                bits |= (((kCx >> cn) & 1u) | (((kCy >> cn) & 1u) << 1) | (((kCz >> cn) & 1u) << 2))
-                        << (3 * v);
-            }
-            mine[t0 + k][0] = w0;
-            mine[t0 + k][1] = (uint32_t)(cell.z + 1) | (bits << 16);
-        }
-    }
+    if (c < n) mc_cell_descriptors(cells[c], (int)(tri_offset[c] - base), mine);  // ---- A
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): the wave's LDS writes have landed
     __builtin_amdgcn_wave_barrier();

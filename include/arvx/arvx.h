@@ -404,6 +404,28 @@ int arvx_mc_mesh_download(arvx_ctx *ctx, float *verts, uint32_t *face_rgb);
  * host mesh takes both arrays without a conversion loop. */
 int arvx_mc_mesh_download_faces(arvx_ctx *ctx, float *verts, uint32_t *faces);
 
+/* The same mesh with shared vertices (an extension beyond the reference, which gives every
+ * triangle three fresh vertices).  Definition: take the T triangles arvx_mc_mesh returns for the
+ * same state and apply_unseen, vertices v[3t+k] and face colours face_rgb[t].  The welded mesh has
+ *   - vertices: the distinct positions v[.], compared as float values, ascending by (z, y, x) --
+ *     on the device every vertex is a lattice point, so this is Model::flatten order (x fastest):
+ *     the occupied voxels with an empty 6-neighbour (out-of-grid counts as empty), closure fills
+ *     included.  V of them;
+ *   - faces: the same T triangles in the same order; faces[t][k] is the index of v[3t+k] in the
+ *     vertex list.  Snapping makes some triangles degenerate (two or three equal indices): they are
+ *     kept, as the reference writes them;
+ *   - face colours: face_rgb[t], unchanged (the `i + 1` quirk included);
+ *   - vertex colours: the colour Model::get returns for the vertex's voxel, with arvx_mc_mesh's
+ *     precedence (UNSEEN paint, closure, colour pass, MODEL_COLOR); so for corners a, b, c:
+ *     face_rgb[t] == round(((col[a] + col[b]) + col[b]) / 3) per channel in fp32.
+ * arvx_mc_mesh_welded builds it with ONE host synchronisation and returns V and T; whole-grid
+ * contexts only (slab and striped contexts: ARVX_ERR_STATE).  arvx_mc_mesh_welded_download copies
+ * 3V floats of positions (voxel units), 6T uints of face records {i0, i1, i2, r, g, b} -- the C++
+ * layer's Triangle -- and, if vertex_rgb is not null, 3V floats of vertex colours.  Runs
+ * arvx_mc_cells itself; the unwelded mesh of an earlier arvx_mc_mesh stays valid. */
+int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int64_t *triangles);
+int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb);
+
 /* Model::voxels as the reference would hold it after carve [+ colour]
  * [+ handleUnseen]: n*4 floats (RGBA), n = slab voxels. */
 int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen);

@@ -22,10 +22,12 @@
 #ifndef ARVX_MARCHING_CUBES_HPP
 #define ARVX_MARCHING_CUBES_HPP
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -55,6 +57,8 @@ class SimpleMesh {  // src/MarchingCubes.h:33-92
     }
     HostVector<Vec3f> &GetVertices() { return m_vertices; }
     HostVector<Triangle> &GetTriangles() { return m_triangles; }
+    const HostVector<Vec3f> &GetVertices() const { return m_vertices; }
+    const HostVector<Triangle> &GetTriangles() const { return m_triangles; }
 
     // The reference ends every line with std::endl (one flush per line); '\n' and one flush at
     // the end give the same bytes.
@@ -215,6 +219,31 @@ inline bool ProcessVoxel(Model *model, int x, int y, int z, SimpleMesh *mesh, fl
     return any;
 }
 
+namespace detail {
+// The model's context, ready for the device mesh of a model whose w are all 0 or 1: painted voxels
+// are derived on the device when the paint is exactly "not seen" (*apply_unseen = 1), else carried
+// by the byte plane (bit2); the colours are on the device.
+inline arvx_ctx *mesh_context(Model *model, int &apply_unseen) {
+    arvx_ctx *ctx = model->device_for_reading();
+    const bool painted = model->painted();
+    if (painted && !model->paint_is_unseen()) {
+        const std::vector<uint8_t> st = model->byte_state();
+        detail::check(arvx_state_upload(ctx, st.data()), "arvx_state_upload");
+        model->set_colors_on_device(false);
+    }
+    if (!model->colors_on_device()) {
+        std::vector<int64_t> idx;
+        std::vector<float> rgb;
+        (void)model->sorted_colors(idx, rgb);  // (w is 0 or 1 here)
+        detail::check(arvx_colors_upload(ctx, (int64_t)idx.size(), idx.data(), rgb.data()),
+                      "arvx_colors_upload");
+        model->set_colors_on_device(true);
+    }
+    apply_unseen = (painted && model->paint_is_unseen()) ? 1 : 0;
+    return ctx;
+}
+}  // namespace detail
+
 // The mesh marchingCubes() writes, without writing it.  When every w of the model is 0 or 1
 // (all the reference's own pipeline produces) the triangles come from the device
 // (arvx_mc_mesh: state, colour list and closure result are already there); a model with
@@ -243,27 +272,11 @@ inline SimpleMesh marchingCubesMesh(Model *model, float threshold = 0.5f) {
             ProcessVoxel(model, c.x, c.y, c.z, &mesh, threshold);
         return mesh;
     }
-    arvx_ctx *ctx = model->device_for_reading();
-    // painted voxels: derived on the device when the paint is exactly "not seen", else carried
-    // by the byte plane (bit2)
-    const bool painted = model->painted();
-    if (painted && !model->paint_is_unseen()) {
-        const std::vector<uint8_t> st = model->byte_state();
-        detail::check(arvx_state_upload(ctx, st.data()), "arvx_state_upload");
-        model->set_colors_on_device(false);
-    }
-    if (!model->colors_on_device()) {
-        std::vector<int64_t> idx;
-        std::vector<float> rgb;
-        (void)model->sorted_colors(idx, rgb);  // (w is 0 or 1 here)
-        detail::check(arvx_colors_upload(ctx, (int64_t)idx.size(), idx.data(), rgb.data()),
-                      "arvx_colors_upload");
-        model->set_colors_on_device(true);
-    }
+    int apply_unseen = 0;
+    arvx_ctx *ctx = detail::mesh_context(model, apply_unseen);
     ARVX_TRACE("context + colours");
     int64_t n = 0;
-    detail::check(arvx_mc_mesh(ctx, (painted && model->paint_is_unseen()) ? 1 : 0, &n),
-                  "arvx_mc_mesh");
+    detail::check(arvx_mc_mesh(ctx, apply_unseen, &n), "arvx_mc_mesh");
     ARVX_TRACE("arvx_mc_mesh");
     // the device writes both arrays in the mesh's own layout: a triangle's three corners as
     // nine floats, its face as (3t, 3t+1, 3t+2, r, g, b)
@@ -281,11 +294,14 @@ inline SimpleMesh marchingCubesMesh(Model *model, float threshold = 0.5f) {
     return mesh;
 }
 
-inline bool marchingCubes(Model *model, float scale = 1.0f, Vec3f translation = Vec3f(0, 0, 0),
-                          float threshold = 0.5f, std::string outFileName = "out/mesh.off") {
+namespace detail {
+// marchingCubes' frame around a mesh builder: log lines, Benchmark stage, WriteMesh
+template <class Build>
+inline bool marching_cubes_write(Model *model, float scale, Vec3f translation, float threshold,
+                                 const std::string &outFileName, Build build) {
     std::cout << "LOG - MC: starting to process Voxels." << std::endl;
     detail::timing(kStageMarchingCubes, true);
-    SimpleMesh mesh = marchingCubesMesh(model, threshold);
+    SimpleMesh mesh = build(model, threshold);
     detail::timing(kStageMarchingCubes, false);
     std::cout << "LOG - MC: voxel processing completed.\n Writing mesh..." << std::endl;
     volatile float factor = scale * model->getSize();
@@ -295,6 +311,73 @@ inline bool marchingCubes(Model *model, float scale = 1.0f, Vec3f translation = 
     }
     std::cout << "LOG - MC: Mesh written, marchingCubes completed." << std::endl;
     return true;
+}
+}  // namespace detail
+
+inline bool marchingCubes(Model *model, float scale = 1.0f, Vec3f translation = Vec3f(0, 0, 0),
+                          float threshold = 0.5f, std::string outFileName = "out/mesh.off") {
+    return detail::marching_cubes_write(model, scale, translation, threshold, outFileName,
+                                        [](Model *m, float t) { return marchingCubesMesh(m, t); });
+}
+
+// ---- welded mesh (an extension beyond the reference) -------------------------------------------
+//
+// The definition of arvx_mc_mesh_welded (include/arvx/arvx.h) applied to any mesh: the distinct
+// vertex positions, compared as float values, ascending by (z, y, x); the same triangles in the
+// same order with their indices into that list and their colours; degenerate triangles kept.
+inline SimpleMesh weldMesh(const SimpleMesh &mesh) {
+    const HostVector<Vec3f> &v = mesh.GetVertices();
+    const HostVector<Triangle> &tris = mesh.GetTriangles();
+    auto before = [&v](unsigned int a, unsigned int b) {
+        const Vec3f &p = v[a], &q = v[b];
+        if (p.z() != q.z()) return p.z() < q.z();
+        if (p.y() != q.y()) return p.y() < q.y();
+        return p.x() < q.x();
+    };
+    std::vector<unsigned int> order(v.size()), index(v.size());
+    std::iota(order.begin(), order.end(), 0u);
+    std::sort(order.begin(), order.end(), before);
+    SimpleMesh out;
+    unsigned int next = 0;
+    for (size_t k = 0; k < order.size(); ++k) {
+        if (k == 0 || before(order[k - 1], order[k])) next = out.AddVertex(v[order[k]]);
+        index[order[k]] = next;
+    }
+    out.GetTriangles().reserve(tris.size());
+    for (const Triangle &t : tris)
+        out.AddFace(index[t.idx0], index[t.idx1], index[t.idx2], t.r, t.g, t.b);
+    return out;
+}
+
+// marchingCubesMesh with shared vertices: weldMesh(marchingCubesMesh(model, threshold)).  When
+// every w is 0 or 1 the device builds it directly (arvx_mc_mesh_welded: 12 bytes per vertex and
+// 24 per triangle cross PCIe instead of 60 per triangle); a model with fractional w -- vertices
+// interpolated, not snapped -- is welded on the host.
+inline SimpleMesh marchingCubesMeshWelded(Model *model, float threshold = 0.5f) {
+    if (!(threshold > 0.f)) return SimpleMesh();
+    bool on_device = false;
+    (void)model->inside_state(threshold, on_device);
+    if (!on_device) return weldMesh(marchingCubesMesh(model, threshold));
+    int apply_unseen = 0;
+    arvx_ctx *ctx = detail::mesh_context(model, apply_unseen);
+    int64_t nv = 0, nt = 0;
+    detail::check(arvx_mc_mesh_welded(ctx, apply_unseen, &nv, &nt), "arvx_mc_mesh_welded");
+    SimpleMesh mesh;
+    HostVector<Vec3f> &mv = mesh.GetVertices();
+    HostVector<Triangle> &mt = mesh.GetTriangles();
+    mv.resize((size_t)nv);  // (recycled memory, not zeroed: host_pool.hpp)
+    mt.resize((size_t)nt);
+    detail::check(arvx_mc_mesh_welded_download(ctx, nv ? mv[0].data() : nullptr,
+                                                 nt ? &mt[0].idx0 : nullptr, nullptr),
+                  "arvx_mc_mesh_welded_download");
+    return mesh;
+}
+
+// marchingCubes writing the welded mesh: same arguments, log lines and Benchmark stage.
+inline bool marchingCubesWelded(Model *model, float scale = 1.0f, Vec3f translation = Vec3f(0, 0, 0),
+                                float threshold = 0.5f, std::string outFileName = "out/mesh.off") {
+    return detail::marching_cubes_write(model, scale, translation, threshold, outFileName,
+                                        [](Model *m, float t) { return marchingCubesMeshWelded(m, t); });
 }
 
 namespace detail {
