@@ -52,17 +52,28 @@ def build_host_tests() -> str:
     _make("tests/cpp")
     _make("tools/cpp", "all")  # arvx_bench6 (the reference's -c=6 table), arvx_dropin_time
     build_weld_host_test()
+    build_smooth_host_test()
     return os.path.join(ROOT, "tests", "cpp", "test_host")
 
 
 def build_weld_host_test() -> str:
     """g++ -> tests/cpp/test_weld_host: arvx::weldMesh (include/arvx/marching_cubes.hpp) on a mesh
     from a file; the layer is header-only over libarvx.so, which is built first if missing."""
+    return _build_host_test("test_weld_host")
+
+
+def build_smooth_host_test() -> str:
+    """g++ -> tests/cpp/test_smooth_host: arvx::smoothMesh (include/arvx/marching_cubes.hpp) on a
+    welded mesh from a file, built as build_weld_host_test builds its test."""
+    return _build_host_test("test_smooth_host")
+
+
+def _build_host_test(name: str) -> str:
     lib_dir = os.path.join(ROOT, "ar_voxel_project_amd", "lib")
     if not os.path.exists(os.path.join(lib_dir, "libarvx.so")):
         build_library()
-    src = os.path.join(ROOT, "tests", "cpp", "test_weld_host.cpp")
-    exe = os.path.join(ROOT, "tests", "cpp", "test_weld_host")
+    src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
+    exe = os.path.join(ROOT, "tests", "cpp", name)
     cmd = [os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-ffp-contract=off", "-Wall", "-Wextra",
            "-I" + os.path.join(ROOT, "include"), "-pthread", "-o", exe, src, "-L" + lib_dir, "-larvx",
            "-Wl,-rpath," + lib_dir]

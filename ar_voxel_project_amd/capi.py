@@ -52,6 +52,7 @@ SYMBOLS = [
     "arvx_closure_download32",
     "arvx_mc_cells", "arvx_mc_cells_download", "arvx_mc_mesh", "arvx_mc_mesh_download",
     "arvx_mc_mesh_download_faces", "arvx_mc_mesh_welded", "arvx_mc_mesh_welded_download",
+    "arvx_mc_mesh_smooth", "arvx_mc_mesh_smooth_download",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
     "arvx_export_model", "arvx_get_stats", "arvx_selftest_divide", "arvx_selftest_round",
@@ -173,6 +174,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
             lib.arvx_occupancy_pack_compress.argtypes = [p, C.c_void_p, C.c_int64, C.c_void_p]
             lib.arvx_occupancy_expand_striped_others.argtypes = [p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
                                                                  C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "arvx_mc_mesh_smooth"):
+        lib.arvx_mc_mesh_smooth.argtypes = [p, C.c_int, C.c_float, C.c_float]
+        lib.arvx_mc_mesh_smooth_download.argtypes = [p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if ab_build and not hasattr(lib, name):
             continue
@@ -628,6 +632,7 @@ class Context:
                                                            C.c_void_p]
         self._ck(self._lib.arvx_mc_mesh_welded(self._h, int(apply_unseen), C.byref(nv),
                                                C.byref(nt)))
+        self._weld_v = int(nv.value)  # (mc_mesh_smooth_download's V)
         verts = np.empty((nv.value, 3), np.float32)
         records = np.empty((nt.value, 6), np.uint32)  # i0, i1, i2, r, g, b
         vrgb = np.empty((nv.value, 3), np.float32) if vertex_colors else None
@@ -644,7 +649,27 @@ class Context:
                                                   C.POINTER(C.c_int64)]
         self._ck(self._lib.arvx_mc_mesh_welded(self._h, int(apply_unseen), C.byref(nv),
                                                C.byref(nt)))
+        self._weld_v = int(nv.value)  # (mc_mesh_smooth_download's V)
         return int(nv.value), int(nt.value)
+
+    def mc_mesh_smooth(self, iterations: int = 1, lam: float = 0.5, mu: float = -0.53,
+                       download: bool = True):
+        """Taubin smoothing and vertex normals of the mesh of the last mc_mesh_welded
+        (arvx_mc_mesh_smooth): (verts (V, 3) float32, normals (V, 3) float32); the faces are
+        mc_mesh_welded's.  download=False: the call only, the result stays on the device."""
+        self._ck(self._lib.arvx_mc_mesh_smooth(self._h, int(iterations), float(lam), float(mu)))
+        if not download:
+            return None
+        return self.mc_mesh_smooth_download()
+
+    def mc_mesh_smooth_download(self, verts: bool = True, normals: bool = True):
+        """arvx_mc_mesh_smooth_download: (verts, normals), each (V, 3) float32 or None."""
+        nv = getattr(self, "_weld_v", 0)
+        v = np.empty((nv, 3), np.float32) if verts else None
+        n = np.empty((nv, 3), np.float32) if normals else None
+        self._ck(self._lib.arvx_mc_mesh_smooth_download(
+            self._h, v.ctypes.data if v is not None else None, n.ctypes.data if n is not None else None))
+        return v, n
 
     def mc_mesh_count(self, apply_unseen: bool = False) -> int:
         """arvx_mc_mesh without the download: the triangles stay on the device."""

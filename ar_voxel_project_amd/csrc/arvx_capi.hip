@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -32,6 +33,7 @@
 #include "mc_kernels.h"
 #include "mc_mesh_kernels.h"
 #include "mc_weld_kernels.h"
+#include "mc_smooth_kernels.h"
 #include "exchange_kernels.h"
 #include <algorithm>
 
@@ -2760,6 +2762,7 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
                     ctx->closure_unseen);
     ctx->free_mc();
     ctx->weld_ready = false;
+    ctx->smooth_ready = ctx->smooth_csr_ready = false;  // (a new mesh: new CSRs)
     ctx->weld_verts = ctx->weld_tris = 0;
     *vertices = *triangles = 0;
     // the vertex plane: occupied voxels with an empty 6-neighbour, in the occupancy the cell walk
@@ -2856,6 +2859,121 @@ int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, f
         ARVX_HIP(hipMemcpyAsync(faces, ctx->pool_weld_faces.p, (size_t)ctx->weld_tris * 24,
                                 hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+// Taubin smoothing and vertex normals of the welded mesh (mc_smooth_kernels.h).  V and T are
+// known on the host and every buffer is sized from bounds (neighbour entries <= min(26 V, 6 T),
+// incidences <= 3 T), so no count has to come back: the call only launches, and
+// arvx_mc_mesh_smooth_download has the synchronisation.  The CSRs are built at the first call on
+// a welded mesh and kept for the next ones.
+static int smooth_csr(Ctx *ctx) {
+    const long long V = ctx->weld_verts, T = ctx->weld_tris;
+    const long long ncap = std::min(26 * V, 6 * T), icap = 3 * T;
+    const unsigned blocks_v = (unsigned)((V + 1 + 255) / 256), blocks_t = (unsigned)((T + 255) / 256);
+    // masks (V) | incidence counts (V + 1) | neighbour counts (V + 1) | their two offsets (V + 1 each)
+    ARVX_HIP(ctx->pool_smooth_csr.reserve((size_t)(5 * V + 4) * sizeof(int)));
+    ARVX_HIP(ctx->pool_smooth_nbr.reserve((size_t)std::max(ncap, 1ll) * sizeof(unsigned)));
+    ARVX_HIP(ctx->pool_smooth_inc.reserve((size_t)std::max(icap, 1ll) * sizeof(unsigned)));
+    unsigned *masks = (unsigned *)ctx->pool_smooth_csr.p;
+    int *icount = (int *)(masks + V), *ncount = icount + V + 1, *noff = ncount + V + 1, *ioff = noff + V + 1;
+    unsigned *nbr = (unsigned *)ctx->pool_smooth_nbr.p, *inc = (unsigned *)ctx->pool_smooth_inc.p;
+    const unsigned *faces = (const unsigned *)ctx->pool_weld_faces.p;
+    const int *index = (const int *)ctx->pool_weld_index.p;
+    ARVX_HIP(hipMemsetAsync(masks, 0, (size_t)(2 * V + 1) * sizeof(int), ctx->stream));  // masks, icount
+    if (T > 0) {
+        hipLaunchKernelGGL(arvx::mc_smooth_adjacency_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T,
+                           V, index, ctx->X, ctx->Y, masks, icount);
+        ARVX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(arvx::mc_smooth_degree_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
+                       (const unsigned *)masks, V, ncount);
+    ARVX_HIP(hipGetLastError());
+    // (slot 5: a total no call reads)
+    if (int rc = scan_counts(ctx, ncount, nullptr, V + 1, nullptr, noff, 5, nullptr)) return rc;
+    if (int rc = scan_counts(ctx, icount, nullptr, V + 1, nullptr, ioff, 5, nullptr)) return rc;
+    hipLaunchKernelGGL(arvx::mc_smooth_neighbours_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
+                       (const unsigned *)masks, V, index, ctx->X, ctx->Y,
+                       arvx::SparseList{(const arvx::SparseWord *)ctx->pool_weld_rank.p}, (const int *)noff,
+                       ncap, nbr);
+    ARVX_HIP(hipGetLastError());
+    if (T > 0) {
+        hipLaunchKernelGGL(arvx::mc_smooth_incidence_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T,
+                           V, icount, (const int *)ioff, icap, inc);
+        ARVX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(arvx::mc_smooth_sort_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
+                       (const int *)ioff, V, icap, inc);
+    ARVX_HIP(hipGetLastError());
+    ctx->smooth_csr_ready = true;
+    return ARVX_OK;
+}
+
+int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu) {
+    ARVX_CHECK_CTX(ctx);
+    if (iterations < 0 || !std::isfinite(lambda) || !std::isfinite(mu))
+        return fail(ARVX_ERR_INVALID, "iterations must be >= 0 and the factors finite");
+    if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
+    ctx->smooth_ready = false;
+    const long long V = ctx->weld_verts, T = ctx->weld_tris;
+    if (V == 0) {
+        ctx->smooth_q = 0;
+        ctx->smooth_ready = true;
+        return ARVX_OK;
+    }
+    if (!ctx->smooth_csr_ready)
+        if (int rc = smooth_csr(ctx)) return rc;
+    const long long ncap = std::min(26 * V, 6 * T), icap = 3 * T;
+    const unsigned *faces = (const unsigned *)ctx->pool_weld_faces.p;
+    int *noff = (int *)ctx->pool_smooth_csr.p + V + 2 * (V + 1), *ioff = noff + V + 1;
+    const unsigned blocks_v = (unsigned)((V + 255) / 256), blocks_t = (unsigned)((T + 255) / 256);
+    // the steps: welded positions -> buffer 1 -> buffer 2 -> buffer 1 ...
+    ARVX_HIP(ctx->pool_smooth_verts.reserve((size_t)6 * V * sizeof(float)));
+    float *buf[3] = {(float *)ctx->pool_weld_verts.p, (float *)ctx->pool_smooth_verts.p,
+                     (float *)ctx->pool_smooth_verts.p + 3 * V};
+    int q = 0;
+    for (int s = 0; s < 2 * iterations; ++s) {
+        const int next = q == 1 ? 2 : 1;
+        hipLaunchKernelGGL(arvx::mc_smooth_step_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
+                           (const float *)buf[q], V, (const int *)noff, ncap,
+                           (const unsigned *)ctx->pool_smooth_nbr.p, (s & 1) ? mu : lambda, buf[next]);
+        ARVX_HIP(hipGetLastError());
+        q = next;
+    }
+    // the normals of the final positions
+    ARVX_HIP(ctx->pool_smooth_cross.reserve((size_t)std::max(3 * T, 1ll) * sizeof(float)));
+    ARVX_HIP(ctx->pool_smooth_normals.reserve((size_t)3 * V * sizeof(float)));
+    if (T > 0) {
+        hipLaunchKernelGGL(arvx::mc_smooth_cross_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T,
+                           (const float *)buf[q], V, (float *)ctx->pool_smooth_cross.p);
+        ARVX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(arvx::mc_smooth_normal_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
+                       (const int *)ioff, V, icap, (const unsigned *)ctx->pool_smooth_inc.p,
+                       (const float *)ctx->pool_smooth_cross.p, T, (float *)ctx->pool_smooth_normals.p);
+    ARVX_HIP(hipGetLastError());
+    ctx->smooth_q = q;
+    ctx->smooth_ready = true;
+    return ARVX_OK;
+}
+
+int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->smooth_ready) return fail(ARVX_ERR_STATE, "no smoothed mesh (call arvx_mc_mesh_smooth)");
+    const long long V = ctx->weld_verts;
+    if (V > 0 && verts) {
+        const float *q = ctx->smooth_q == 0 ? (const float *)ctx->pool_weld_verts.p
+                                            : (const float *)ctx->pool_smooth_verts.p + (ctx->smooth_q - 1) * 3 * V;
+        ARVX_HIP(hipMemcpyAsync(verts, q, (size_t)V * 12, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (V > 0 && normals)
+        ARVX_HIP(hipMemcpyAsync(normals, ctx->pool_smooth_normals.p, (size_t)V * 12, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    ARVX_HIP(hipStreamSynchronize(ctx->stream));
+    if (int rc = check_fault(ctx)) {  // (a scan gave up: the CSRs are built again)
+        ctx->smooth_ready = ctx->smooth_csr_ready = false;
+        return rc;
+    }
     return ARVX_OK;
 }
 

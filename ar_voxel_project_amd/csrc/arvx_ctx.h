@@ -200,6 +200,13 @@ struct Ctx {
         pool_weld_faces;
     int64_t weld_verts = 0, weld_tris = 0;
     bool weld_ready = false;
+    // arvx_mc_mesh_smooth: the welded mesh's CSRs -- masks, counts and offsets; neighbour list;
+    // incidence list -- (built once per welded mesh), the two position buffers, the faces' cross
+    // products and the normals
+    DevPool pool_smooth_csr, pool_smooth_nbr, pool_smooth_inc, pool_smooth_verts, pool_smooth_cross,
+        pool_smooth_normals;
+    bool smooth_csr_ready = false, smooth_ready = false;
+    int smooth_q = 0;  // where the smoothed positions are: 0 the welded mesh's, 1 / 2 a buffer
     void release_pools() {
         pool_surf_index.release();
         pool_surf_rgb.release();
@@ -220,6 +227,13 @@ struct Ctx {
         pool_weld_rgb.release();
         pool_weld_faces.release();
         weld_ready = false;
+        pool_smooth_csr.release();
+        pool_smooth_nbr.release();
+        pool_smooth_inc.release();
+        pool_smooth_verts.release();
+        pool_smooth_cross.release();
+        pool_smooth_normals.release();
+        smooth_csr_ready = smooth_ready = false;
         pool_xscratch.release();
         pool_vstrip.release();
         vstrip_key = 0;

@@ -426,6 +426,30 @@ int arvx_mc_mesh_download_faces(arvx_ctx *ctx, float *verts, uint32_t *faces);
 int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int64_t *triangles);
 int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb);
 
+/* Taubin smoothing and vertex normals of the welded mesh (an extension beyond the reference, whose
+ * vertices all sit on the voxel lattice).  Definition, on a welded mesh with V positions p (fp32)
+ * and T faces (i0, i1, i2); every fp32 operation rounded on its own (no fma), '/' and sqrtf IEEE:
+ *   - neighbours: N(i) = { j != i : some face contains both i and j }, each once, ascending;
+ *   - one step with factor f, per component: p'_i = p_i when N(i) is empty, else
+ *     s = +0; s = s + p_j for j in N(i) ascending; m = s / (float)|N(i)|; d = m - p_i;
+ *     p'_i = p_i + (f * d).  Every vertex reads the previous step's positions (Jacobi);
+ *   - Taubin (iterations, lambda, mu): 2 * iterations steps with factors lambda, mu, lambda, mu,
+ *     ... (iterations = 0: the positions unchanged; mu = 0: plain Laplacian smoothing).  The
+ *     usual factors are lambda = 0.5, mu = -0.53;
+ *   - vertex normals on the final positions q: per face c_t = a x b with a = q[i2] - q[i0],
+ *     b = q[i1] - q[i0] (c_t.x = a.y*b.z - a.z*b.y, and so on; the mesh's own winding points into
+ *     the model, this points out); n_i = sum of c_t over the faces that contain i, each face once,
+ *     in ascending t from +0; l = sqrtf((n.x*n.x + n.y*n.y) + n.z*n.z); normal = n / l per
+ *     component, (0, 0, 0) when l == 0.
+ * arvx_mc_mesh_smooth acts on the mesh of the last arvx_mc_mesh_welded (none: ARVX_ERR_STATE, as
+ * on slab and striped contexts; iterations < 0 or a factor that is not finite: ARVX_ERR_INVALID).
+ * It does not synchronise.  The adjacency is built at the first call on a welded mesh and reused
+ * by the next ones; arvx_mc_mesh_welded_download keeps returning the lattice positions.
+ * arvx_mc_mesh_smooth_download copies 3V floats of positions and 3V floats of unit normals; either
+ * pointer may be null (ARVX_ERR_STATE before the first arvx_mc_mesh_smooth on the welded mesh). */
+int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu);
+int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals);
+
 /* Model::voxels as the reference would hold it after carve [+ colour]
  * [+ handleUnseen]: n*4 floats (RGBA), n = slab voxels. */
 int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen);

@@ -380,6 +380,125 @@ inline bool marchingCubesWelded(Model *model, float scale = 1.0f, Vec3f translat
                                         [](Model *m, float t) { return marchingCubesMeshWelded(m, t); });
 }
 
+// ---- smoothed mesh (an extension beyond the reference) ------------------------------------------
+//
+// The definition of arvx_mc_mesh_smooth (include/arvx/arvx.h) applied to any welded mesh on the
+// host: Taubin smoothing with (iterations, lambda, mu), then -- if normals is not null -- the unit
+// vertex normals of the result.  Returns the mesh with the smoothed positions and the same
+// triangles.  (Compiled with -ffp-contract=off, as the tools and tests are, this is bit for bit
+// what the device computes.)
+inline SimpleMesh smoothMesh(const SimpleMesh &welded, int iterations, float lambda = 0.5f,
+                             float mu = -0.53f, HostVector<Vec3f> *normals = nullptr) {
+    const HostVector<Triangle> &tris = welded.GetTriangles();
+    const size_t V = welded.GetVertices().size();
+    // N(i): the other corners of i's faces, each once, ascending
+    std::vector<std::vector<unsigned int>> nbr(V);
+    for (const Triangle &t : tris) {
+        const unsigned int c[3] = {t.idx0, t.idx1, t.idx2};
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b)
+                if (c[a] != c[b]) nbr[c[a]].push_back(c[b]);
+    }
+    for (std::vector<unsigned int> &n : nbr) {
+        std::sort(n.begin(), n.end());
+        n.erase(std::unique(n.begin(), n.end()), n.end());
+    }
+    std::vector<Vec3f> p(welded.GetVertices().begin(), welded.GetVertices().end()), next(V);
+    for (int s = 0; s < 2 * iterations; ++s) {
+        const float f = (s & 1) ? mu : lambda;
+        for (size_t i = 0; i < V; ++i) {
+            if (nbr[i].empty()) {
+                next[i] = p[i];
+                continue;
+            }
+            const float k = (float)nbr[i].size();
+            for (int c = 0; c < 3; ++c) {
+                float sum = 0.f;
+                for (unsigned int j : nbr[i]) sum = sum + p[j][c];
+                const float d = sum / k - p[i][c];
+                const float fd = f * d;
+                next[i][c] = p[i][c] + fd;
+            }
+        }
+        p.swap(next);
+    }
+    SimpleMesh out;
+    HostVector<Vec3f> &ov = out.GetVertices();
+    ov.resize(V);
+    std::copy(p.begin(), p.end(), ov.begin());
+    HostVector<Triangle> &ot = out.GetTriangles();
+    ot.resize(tris.size());
+    std::copy(tris.begin(), tris.end(), ot.begin());
+    if (normals) {
+        std::vector<Vec3f> n(V);
+        for (const Triangle &t : tris) {  // ascending t; each face once per corner vertex
+            const Vec3f &q0 = p[t.idx0], &q1 = p[t.idx1], &q2 = p[t.idx2];
+            const float ax = q2.x() - q0.x(), ay = q2.y() - q0.y(), az = q2.z() - q0.z();
+            const float bx = q1.x() - q0.x(), by = q1.y() - q0.y(), bz = q1.z() - q0.z();
+            const float l0 = ay * bz, r0 = az * by, l1 = az * bx, r1 = ax * bz, l2 = ax * by, r2 = ay * bx;
+            const Vec3f c(l0 - r0, l1 - r1, l2 - r2);
+            const unsigned int v[3] = {t.idx0, t.idx1, t.idx2};
+            for (int k = 0; k < 3; ++k) {
+                if ((k > 0 && v[k] == v[0]) || (k > 1 && v[k] == v[1])) continue;
+                for (int e = 0; e < 3; ++e) n[v[k]][e] = n[v[k]][e] + c[e];
+            }
+        }
+        normals->resize(V);
+        for (size_t i = 0; i < V; ++i) {
+            const float xx = n[i].x() * n[i].x(), yy = n[i].y() * n[i].y(), zz = n[i].z() * n[i].z();
+            const float l = std::sqrt((xx + yy) + zz);
+            (*normals)[i] = l == 0.f ? Vec3f(0, 0, 0) : Vec3f(n[i].x() / l, n[i].y() / l, n[i].z() / l);
+        }
+    }
+    return out;
+}
+
+// marchingCubesMeshWelded, smoothed: smoothMesh(marchingCubesMeshWelded(model, threshold), ...).
+// When every w is 0 or 1 the device smooths the welded mesh it has just built
+// (arvx_mc_mesh_smooth); a model with fractional w is smoothed on the host.
+inline SimpleMesh marchingCubesMeshSmoothed(Model *model, float threshold = 0.5f, int iterations = 1,
+                                            float lambda = 0.5f, float mu = -0.53f,
+                                            HostVector<Vec3f> *normals = nullptr) {
+    if (!(threshold > 0.f)) {
+        if (normals) normals->clear();
+        return SimpleMesh();
+    }
+    bool on_device = false;
+    (void)model->inside_state(threshold, on_device);
+    if (!on_device) return smoothMesh(marchingCubesMeshWelded(model, threshold), iterations, lambda, mu, normals);
+    int apply_unseen = 0;
+    arvx_ctx *ctx = detail::mesh_context(model, apply_unseen);
+    int64_t nv = 0, nt = 0;
+    detail::check(arvx_mc_mesh_welded(ctx, apply_unseen, &nv, &nt), "arvx_mc_mesh_welded");
+    detail::check(arvx_mc_mesh_smooth(ctx, iterations, lambda, mu), "arvx_mc_mesh_smooth");
+    SimpleMesh mesh;
+    HostVector<Vec3f> &mv = mesh.GetVertices();
+    HostVector<Triangle> &mt = mesh.GetTriangles();
+    mv.resize((size_t)nv);  // (recycled memory, not zeroed: host_pool.hpp)
+    mt.resize((size_t)nt);
+    // (the welded download needs a vertex array: the lattice positions land where the smoothed
+    // ones then go)
+    detail::check(arvx_mc_mesh_welded_download(ctx, nv ? mv[0].data() : nullptr,
+                                                 nt ? &mt[0].idx0 : nullptr, nullptr),
+                  "arvx_mc_mesh_welded_download");
+    if (normals) normals->resize((size_t)nv);
+    detail::check(arvx_mc_mesh_smooth_download(ctx, nv ? mv[0].data() : nullptr,
+                                                 (normals && nv) ? (*normals)[0].data() : nullptr),
+                  "arvx_mc_mesh_smooth_download");
+    return mesh;
+}
+
+// marchingCubes writing the smoothed welded mesh: marchingCubes' arguments, log lines and
+// Benchmark stage, then the smoothing's.
+inline bool marchingCubesSmoothed(Model *model, float scale = 1.0f, Vec3f translation = Vec3f(0, 0, 0),
+                                  float threshold = 0.5f, std::string outFileName = "out/mesh.off",
+                                  int iterations = 1, float lambda = 0.5f, float mu = -0.53f) {
+    return detail::marching_cubes_write(model, scale, translation, threshold, outFileName,
+                                        [=](Model *m, float t) {
+                                            return marchingCubesMeshSmoothed(m, t, iterations, lambda, mu);
+                                        });
+}
+
 namespace detail {
 // carve(..., intermediateMeshes = true) without a caller-supplied hook writes what the
 // reference writes after every view (src/VoxelCarving.cpp:65-68): the model so far, moved

@@ -177,14 +177,16 @@ int main(int argc, char *argv[]) {
         {"calibration", "out/cameracalibration.yml"}, {"carve", "1"}, {"x", "100"}, {"y", "100"},
         {"z", "100"}, {"size", "0.0028"}, {"color", "0"}, {"scale", "1.0"}, {"dx", "0.0"},
         {"dy", "0.0"}, {"dz", "0.0"}, {"model_debug", "false"}, {"postprocessing", "true"},
-        {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"}};
+        {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
+        {"smooth", "0"}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
                   << "  -c=5 voxel carving, -c=6 benchmark; -images -masks -poses | -scene, "
                      "-calibration, -carve, -x -y -z -size, -color, -scale -dx -dy -dz,\n"
                      "  -postprocessing, -intermediateMesh, -outFile (flags of the reference's "
-                     "src/main.cpp:16-39), -weld (shared mesh vertices)\n";
+                     "src/main.cpp:16-39), -weld (shared mesh vertices),\n"
+                     "  -smooth=N (the welded mesh after N Taubin iterations, lambda 0.5, mu -0.53)\n";
         return 0;
     }
     const int choose = parser.i("c");
@@ -341,8 +343,12 @@ int main(int argc, char *argv[]) {
                          "part of this library"
                       << std::endl;
         if (parser.b("postprocessing")) arvx::applyClosure(&model, 3);
-        // -weld (an extension beyond the reference): the same mesh with shared vertices
-        if (parser.b("weld"))
+        // -weld (an extension beyond the reference): the same mesh with shared vertices;
+        // -smooth=N (N > 0): that mesh after N Taubin iterations
+        if (parser.i("smooth") > 0)
+            arvx::marchingCubesSmoothed(&model, parser.f("scale"), modelTranslation, 0.5f,
+                                        parser.str("outFile"), parser.i("smooth"));
+        else if (parser.b("weld"))
             arvx::marchingCubesWelded(&model, parser.f("scale"), modelTranslation, 0.5f,
                                       parser.str("outFile"));
         else
