@@ -589,6 +589,17 @@ class Context:
             assert np.array_equal(i32, idx) and np.array_equal(r32.view(np.uint32), rgba.view(np.uint32))
         return idx, rgba
 
+    def closure_download(self):
+        """The last closure's filled voxels (arvx_closure_count / _download): (flat indices, RGBA)."""
+        n = C.c_int64()
+        self._ck(self._lib.arvx_closure_count(self._h, C.byref(n)))
+        idx = np.empty(n.value, np.int64)
+        rgba = np.empty((n.value, 4), np.float32)
+        if n.value:
+            self._ck(self._lib.arvx_closure_download(
+                self._h, idx.ctypes.data_as(C.POINTER(C.c_int64)), _fp(rgba)))
+        return idx, rgba
+
     def mc_cells(self) -> np.ndarray:
         """(n, 4) int32 -- x, y, z, cube index of the cells marchingCubes would
         triangulate, in its visiting order (x outermost, z innermost)."""

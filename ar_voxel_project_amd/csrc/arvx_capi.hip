@@ -890,12 +890,23 @@ static int need_rec(Ctx *ctx, bool lazy_ok) {
     return ARVX_OK;
 }
 
+// The state holds a closure's fills but its list -- their colours -- is gone (handleUnseen, a colour
+// call, new views or images since): the reference's Model would still give them their means, which
+// the context no longer has.  Calls that return colours are refused then (arvx.h, arvx_closure).
+static int fills_without_colours(Ctx *ctx) {
+    if (ctx->closure_fills && !ctx->closure_ready)
+        return fail(ARVX_ERR_STATE, "the closure's list of filled voxels is gone (handleUnseen, a colour call, "
+                                    "new views or images since): upload the state and its colours again");
+    return ARVX_OK;
+}
+
 // every call that changes occupied / seen bits goes through here: results derived from the
 // old state are dropped
 static void state_changes(Ctx *ctx, bool keeps_paint) {
     ++ctx->state_seq;
     ctx->color_ready = false;
     ctx->closure_ready = false;
+    ctx->closure_fills = false;
     if (!keeps_paint) ctx->paint_valid = false;
 }
 // ... and one that may occupy or un-see voxels (everything but carving, the greedy carve and
@@ -2120,6 +2131,7 @@ int arvx_surface_depth_download(arvx_ctx *ctx, float *depth) {
 // Model::voxels of the owned voxels, built on the device in chunks and copied out.
 int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen) {
     ARVX_CHECK_CTX(ctx);
+    if (int frc = fills_without_colours(ctx)) return frc;
     if (int mrc = need_rec(ctx)) return mrc;
     if (!rgba) return fail(ARVX_ERR_INVALID, "null rgba");
     arvx::CarveParams g;
@@ -2370,8 +2382,8 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
         return fail(ARVX_ERR_INVALID, "kernel size %d (odd, 1..9)", kernel_size);
     if (ctx->stripe_world > 1)
         return fail(ARVX_ERR_STATE, "arvx_closure needs contiguous slabs (neighbour planes)");
-    if (ctx->closure_ready)
-        return fail(ARVX_ERR_STATE, "closure already applied to this model state");
+    if (ctx->closure_ready || ctx->closure_fills)
+        return fail(ARVX_ERR_STATE, "closure already applied to this model state (carve, upload or reset first)");
     const int radius = (kernel_size - 1) / 2;
     // the planes that get filled here: all owned ones, plus the halo planes whose box lies
     // inside the planes that carry colours (stage_ranges)
@@ -2430,6 +2442,8 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     // Coarse tiles that exist only as their code: the few that receive a voxel are marked by the fill
     // plane's producer and written out by rec_or_bitgrid_lazy_kernel, the others stay codes (grids
     // whose rows and planes fill whole tiles; else every tile is written out first, as in round 4)
+    // (never a second closure on the lazy state: closure_fills is refused above, and
+    // rec_or_bitgrid_lazy_kernel depends on that)
     const bool lazy_or = ctx->lazy && ctx->Y % 8 == 0 && Zext % 8 == 0;
     arvx::CoarseMark mark{lazy_or ? (uint8_t *)ctx->pool_ccode.p : nullptr, rp.coarseX, rp.coarseY, rp.cyShift,
                           rp.czShift};
@@ -2445,6 +2459,7 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
         if (int mrc = need_rec(ctx)) return mrc;  // every record exists from here on
     ++ctx->state_seq;
     state_rewritten(ctx);  // (voxels of tiles an earlier carve emptied may be occupied again)
+    ctx->closure_fills = true;
     if (lazy_or)
         hipLaunchKernelGGL(arvx::rec_or_bitgrid_lazy_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, g.Z,
                            (const unsigned long long *)d_fill, (const uint8_t *)ctx->pool_ccode.p);
@@ -2494,6 +2509,7 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     }
     ctx->clo_count = total;
     ctx->clo_host_count = -1;  // the list's host copy is fetched when somebody asks
+    if (total == 0) ctx->closure_fills = false;  // (nothing was filled: the state is as before)
     if (total == 0) {
         ctx->d_clo_index = nullptr;
         ctx->d_clo_rgba = nullptr;
@@ -2644,6 +2660,7 @@ int arvx_mc_cells_download(arvx_ctx *ctx, int32_t *cells) {
 
 int arvx_mc_mesh(arvx_ctx *ctx, int apply_unseen, int64_t *triangles) {
     ARVX_CHECK_CTX(ctx);
+    if (int frc = fills_without_colours(ctx)) return frc;
     if (!triangles) return fail(ARVX_ERR_INVALID, "null argument");
     if (ctx->stripe_world > 1)
         return fail(ARVX_ERR_STATE, "arvx_mc_mesh needs contiguous slabs (neighbour planes)");
@@ -2753,6 +2770,7 @@ int arvx_mc_mesh_download_faces(arvx_ctx *ctx, float *verts, uint32_t *faces) {
 // together, and a mesh that outgrew its buffers is built once more with room for all of it.
 int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int64_t *triangles) {
     ARVX_CHECK_CTX(ctx);
+    if (int frc = fills_without_colours(ctx)) return frc;
     if (!vertices || !triangles) return fail(ARVX_ERR_INVALID, "null argument");
     if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
         return fail(ARVX_ERR_STATE, "arvx_mc_mesh_welded needs a whole-grid context (vertex indices "

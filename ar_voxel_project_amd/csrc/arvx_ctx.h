@@ -182,6 +182,9 @@ struct Ctx {
     int64_t clo_count = 0;
     bool closure_ready = false;
     int closure_unseen = 0;
+    // the state holds the fills of a closure (its list may have been dropped since): a second
+    // closure is refused until a carve, an upload or a reset replaces the state (arvx.h)
+    bool closure_fills = false;
     int closure_radius = 0;
     std::vector<int> h_clo_index;
     DevPool pool_clo_bits, pool_clo_rank;  // the filled voxels' plane and index (SparseWord)

@@ -274,6 +274,9 @@ __global__ __launch_bounds__(256) void rec_or_bitgrid_kernel(const CarveParams p
 // the code's constants with the bits on top --, and from this launch on the marked code reads as
 // "records hold the state" (lazy_code).  Tiles without a code get the bits OR-ed in as above; coded
 // tiles without a mark receive nothing and stay codes.
+// A tile whose code has bit 7 from an EARLIER closure is rewritten from its constants as well, which
+// would drop that closure's fills: this relies on arvx_closure refusing a state that already holds a
+// closure's fills (ctx->closure_fills) -- every call that clears that flag also ends the lazy state.
 __global__ __launch_bounds__(256) void rec_or_bitgrid_lazy_kernel(const CarveParams p, int nz,
                                                                   const unsigned long long *__restrict__ bits,
                                                                   const uint8_t *__restrict__ ccode) {

@@ -361,10 +361,29 @@ int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const flo
  * neighbours.  apply_unseen != 0: the model is taken as it is after
  * handleUnseen().  State bytes may carry bit2 (voxel painted UNSEEN_COLOR by
  * a host Model; kept beside the records as a bit plane until the next carve, plane upload or
- * reset).  Whole-grid contexts and slabs with at least r + 1 halo planes
+ * reset).  bit2 is meant for occupied voxels -- the C++ Model sends it on no other, since there
+ * handleUnseen occupies what it paints.  On an empty voxel it is kept as given (the byte downloads
+ * unchanged) and the paint wins where colours are returned: arvx_export_model gives UNSEEN_COLOR
+ * with w = 1 there, and the closure averages it as an occupied UNSEEN_COLOR neighbour.
+ * Whole-grid contexts and slabs with at least r + 1 halo planes
  * (arvx_ctx_create_slab_halo): a slab fills -- and reports -- the voxels of its own planes.
  * The filled voxels become occupied;
- * arvx_export_model(ctx, ., same apply_unseen) then returns the closed model. */
+ * arvx_export_model(ctx, ., same apply_unseen) then returns the closed model.
+ * What the context's results belong to, for any order of calls:
+ *   - the colour list (arvx_color, arvx_colors_upload) lives until the next carve, fast carve,
+ *     state upload or reset, arvx_set_views or arvx_set_images; handleUnseen and the closure keep it;
+ *   - the closure's list of filled voxels lives until any of those, arvx_handle_unseen, the next
+ *     arvx_color or arvx_colors_upload;
+ *   - the paint plane (bit2 of arvx_state_upload) lives until the next carve, fast carve, upload
+ *     or reset.
+ * A closure that filled voxels leaves them occupied in the state.  Once its list is gone the
+ * context no longer has their colours, which the reference's Model keeps: until a carve, fast
+ * carve, upload or reset replaces the state, the calls that return colours (arvx_export_model,
+ * arvx_mc_mesh, arvx_mc_mesh_welded) and a second arvx_closure -- which would average those
+ * colours -- are refused with ARVX_ERR_STATE.  A second closure is refused while the first one's
+ * list is still there as well ("already applied").  Occupancy-only calls (state downloads,
+ * arvx_mc_cells) and the colour pass stay available.  The C++ Model keeps the fills' colours on the
+ * host and uploads state and colours again before the stages that need them. */
 int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen);
 int arvx_closure_count(arvx_ctx *ctx, int64_t *count);
 /* Filled voxels, ascending flat index, 4 floats RGBA each. */

@@ -220,14 +220,21 @@ class Model {
 
     // src/Model.cpp:36-47: every voxel that no view saw becomes UNSEEN_COLOR (204, 0, 0, 1) --
     // occupied, whatever it was.  When the current state lives on the device the bit operation
-    // runs there (arvx_handle_unseen) and the paint plane is derived at the next download.
+    // runs there (arvx_handle_unseen) and the paint plane is derived at the next download -- but not
+    // on a closure's result: the context would drop the closure's list (its fills' colours live in
+    // this model), so the state comes to the host and goes back with its colours when needed.
     void handleUnseen() {
         std::cout << "LOG - PP: marking unseen voxels from model." << std::endl;
         pristine_ = false;
+        if (closure_on_device_) {
+            sync_host();
+            host_changed();
+        }
         if (host_stale_) {
             detail::check(arvx_handle_unseen(link_->ctx), "arvx_handle_unseen");
             paint_pending_ = true;
         } else {
+            sync_host();  // (the planes may still be packets: an accessor after a device stage)
             paint_unseen_host();
             device_stale_ = true;
         }
@@ -330,6 +337,7 @@ class Model {
             if (pristine_) {
                 detail::check(arvx_state_reset(link_->ctx), "arvx_state_reset");
             } else {
+                sync_host();  // (packets -> planes: the upload sends the planes)
                 detail::check(arvx_state_upload_planes(link_->ctx, occ_.data(), seen_.data()),
                               "arvx_state_upload_planes");
             }
@@ -420,14 +428,16 @@ class Model {
         if (!unit_w)
             for (const Vec4f &v : rgba)
                 if (v.w() != 0.f && v.w() != 1.f) odd_w_ = true;
-        if (!host_stale_) {  // the host planes are current: the voxels become occupied here
+        // the paint plane lives on the host only: a filled voxel was empty, so paint left there by
+        // a voxel that a carve removed since is not the fill's colour
+        if (!host_stale_) sync_host();  // (the host state is current: the voxels become occupied here)
+        if (!host_stale_ || !paint_.empty())
             for (size_t k = 0; k < index.size(); ++k) {
                 const int x = index[k] % size_x, y = (index[k] / size_x) % size_y,
                           z = index[k] / (size_x * size_y);
-                if (rgba[k].w() != 0) occ_[word(x, y, z)] |= 1u << (x & 31);
+                if (!host_stale_ && rgba[k].w() != 0) occ_[word(x, y, z)] |= 1u << (x & 31);
                 if (!paint_.empty()) paint_[word(x, y, z)] &= ~(1u << (x & 31));
             }
-        }
         if (!overlay_.empty())
             for (size_t k = 0; k < index.size(); ++k) overlay_.erase(index[k]);
         fidx_ = std::move(index);
@@ -489,9 +499,10 @@ class Model {
                 for (int x = 0; x < size_x; ++x) {
                     const size_t w = word(x, y, z);
                     const int sh = x & 31;
+                    // (paint of a voxel carved since is no paint: get() answers zero there)
                     s[(size_t)flatten(x, y, z)] =
                         (uint8_t)(((occ_[w] >> sh) & 1u) | (((seen_[w] >> sh) & 1u) << 1) |
-                                  ((!paint_.empty() ? (paint_[w] >> sh) & 1u : 0u) << 2));
+                                  ((!paint_.empty() ? ((paint_[w] & occ_[w]) >> sh) & 1u : 0u) << 2));
                 }
         return s;
     }
@@ -524,7 +535,7 @@ class Model {
     const uint32_t *occ_plane() const { sync_host(); return occ_.data(); }
     const uint32_t *seen_plane() const { sync_host(); return seen_.data(); }
     uint32_t *occ_plane_for_writing() { sync_host(); return occ_.data(); }
-    uint32_t *seen_plane_for_writing() { return seen_.data(); }
+    uint32_t *seen_plane_for_writing() { sync_host(); return seen_.data(); }
     void planes_replaced() { host_changed(); }
 
     // Bring the host's knowledge of the state up to date with the device (no-op when it is).

@@ -9,6 +9,7 @@
 #include <fstream>
 #include <iostream>
 #include <memory>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -196,7 +197,8 @@ static int run_carve(const char *scene, const char *out, const char *mode) {
             // The carved model reaches the host as two compressed packets (Model::sync_bits) where
             // the grid allows it; the accessors must answer from them exactly what they answer
             // from the planes, which exist only after somebody asks for them as planes.
-            arvx::carve(intr, model, views);
+            // (views 2.. first, views 0 and 1 below: the second carve really changes the state)
+            arvx::carve(intr, model, std::vector<arvx::View>(views.begin() + 2, views.end()));
             const size_t N = (size_t)X * Y * Z;
             std::vector<uint8_t> a(N), b(N);
             auto sweep = [&](std::vector<uint8_t> &dst) {
@@ -217,10 +219,13 @@ static int run_carve(const char *scene, const char *out, const char *mode) {
             if (arvx_state_download_planes(model.device_if_any(), qo.data(), qs.data()) != ARVX_OK) return 17;
             if (std::memcmp(qo.data(), po, qo.size() * 4) || std::memcmp(qs.data(), ps, qs.size() * 4)) return 18;
             // a host-side write goes to the planes, the next carve brings packets again
+            // ... with the other views, so that the state really changes
             model.set(1, 1, 1, Vec4f(0, 0, 0, 0));
-            arvx::carve(intr, model, views);
+            arvx::carve(intr, model, std::vector<arvx::View>(views.begin(), views.begin() + 2));
             if (model.get(1, 1, 1)(3) != 0 || !model.planes_pending()) return 19;
-            model.handleUnseen();  // (on the device; the paint plane is derived at the next sync)
+            // get() above left the state as packets (host_stale_ cleared, planes_stale_ set), so
+            // handleUnseen runs on the HOST and must expand the packets before it paints
+            model.handleUnseen();
         } else if (!std::strcmp(mode, "threads")) {
             // several jobs in flight from several host threads: every thread owns its models
             // (contexts share nothing; calls on ONE context are not thread safe, calls on
@@ -290,6 +295,119 @@ static int run_carve(const char *scene, const char *out, const char *mode) {
     return 0;
 }
 
+// A script of Model operations on a scene (tests/test_cpp_host.py, compared with
+// tests/stage_model.HostModel), one per line:
+//   carve [first count] | fast | closest | average | unseen | closure k | get | visited | inner |
+//   occ_plane | set x y z r g b w | see x y z | copy | dump
+// get / visited / inner sweep the accessor over every voxel (they move the state between the
+// device, the packets and the planes); copy continues on a copy of the model; dump appends the
+// model's RGBA (16 bytes per voxel) and seen bits (one byte each) to `out`.
+static int run_script(const char *scene, const char *script, const char *out) {
+    std::ifstream f(scene, std::ios::binary);
+    int32_t hd[7];
+    f.read((char *)hd, sizeof hd);
+    const int X = hd[0], Y = hd[1], Z = hd[2], V = hd[3], W = hd[4], H = hd[5], C = hd[6];
+    float s;
+    f.read((char *)&s, 4);
+    arvx::Intrinsics intr;
+    f.read((char *)intr.K, 36);
+    std::vector<arvx::View> views(V);
+    for (auto &v : views) f.read((char *)v.pose, 48);
+    std::vector<uint8_t> masks((size_t)V * H * W * C), images((size_t)V * H * W * 3);
+    f.read((char *)masks.data(), masks.size());
+    f.read((char *)images.data(), images.size());
+    std::vector<uint8_t> st0((size_t)X * Y * Z);
+    f.read((char *)st0.data(), st0.size());
+    if (!f) { std::fprintf(stderr, "short scene file\n"); return 2; }
+    for (int i = 0; i < V; ++i) {
+        views[i].mask = {masks.data() + (size_t)i * H * W * C, W, H, C, (size_t)W * C};
+        views[i].image = {images.data() + (size_t)i * H * W * 3, W, H, 3, (size_t)W * 3};
+    }
+    auto model = std::make_unique<Model>(X, Y, Z, s);
+    for (int z = 0; z < Z; ++z)
+        for (int y = 0; y < Y; ++y)
+            for (int x = 0; x < X; ++x) {
+                const uint8_t b = st0[(size_t)x + (size_t)X * (y + (size_t)Y * z)];
+                if (!(b & 1)) model->set(x, y, z, Vec4f(0, 0, 0, 0));
+                if (b & 2) model->see(x, y, z);
+            }
+    std::ifstream ops(script);
+    std::ofstream o(out, std::ios::binary);
+    std::string line;
+    int lineno = 0;
+    try {
+        while (std::getline(ops, line)) {
+            ++lineno;
+            std::istringstream in(line);
+            std::string op;
+            if (!(in >> op)) continue;
+            Model &m = *model;
+            size_t sum = 0;  // (keeps the sweeps from being optimised away)
+            if (op == "carve") {
+                int first = 0, count = V;
+                if (in >> first >> count) {
+                    if (first < 0 || count < 1 || first + count > V) return 2;
+                    arvx::carve(intr, m, std::vector<arvx::View>(views.begin() + first, views.begin() + first + count));
+                } else {
+                    arvx::carve(intr, m, views);
+                }
+            } else if (op == "fast") {
+                arvx::fastCarve(intr, m, views);
+            } else if (op == "closest") {
+                arvx::reconstructClosestColor(intr, m, views);
+            } else if (op == "average") {
+                arvx::reconstructAvgColor(intr, m, views);
+            } else if (op == "unseen") {
+                m.handleUnseen();
+            } else if (op == "closure") {
+                int k = 3;
+                in >> k;
+                if (arvx::applyClosure(&m, k) != 0) return 5;
+            } else if (op == "get" || op == "visited" || op == "inner") {
+                for (int z = 0; z < Z; ++z)
+                    for (int y = 0; y < Y; ++y)
+                        for (int x = 0; x < X; ++x)
+                            sum += op == "get" ? (m.get(x, y, z)(3) != 0)
+                                   : op == "visited" ? m.visited(Vec3i(x, y, z)) : m.isInner(x, y, z);
+            } else if (op == "occ_plane") {
+                sum += m.occ_plane()[0];
+            } else if (op == "set") {
+                int x, y, z;
+                float r, g, b, w;
+                if (!(in >> x >> y >> z >> r >> g >> b >> w)) return 2;
+                m.set(x, y, z, Vec4f(r, g, b, w));
+            } else if (op == "see") {
+                int x, y, z;
+                if (!(in >> x >> y >> z)) return 2;
+                m.see(x, y, z);
+            } else if (op == "copy") {
+                model = std::make_unique<Model>(m);
+            } else if (op == "dump") {
+                for (int z = 0; z < Z; ++z)
+                    for (int y = 0; y < Y; ++y)
+                        for (int x = 0; x < X; ++x) {
+                            const Vec4f v = m.get(x, y, z);
+                            o.write((const char *)v.data(), 16);
+                        }
+                for (int z = 0; z < Z; ++z)
+                    for (int y = 0; y < Y; ++y)
+                        for (int x = 0; x < X; ++x) {
+                            const char b = m.visited(Vec3i(x, y, z)) ? 1 : 0;
+                            o.write(&b, 1);
+                        }
+            } else {
+                std::fprintf(stderr, "line %d: unknown operation %s\n", lineno, op.c_str());
+                return 2;
+            }
+            if (sum == (size_t)-1) std::puts("");
+        }
+    } catch (const arvx::Error &e) {
+        std::fprintf(stderr, "line %d: arvx::Error %d: %s\n", lineno, e.code, e.what());
+        return 3;
+    }
+    return o ? 0 : 4;
+}
+
 // model file: int32 X,Y,Z ; float voxel size ; X*Y*Z * 4 floats (Model::voxels, x fastest).
 // Writes what the reference's marchingCubes(&model, scale, t, threshold, out) writes.
 static int run_mc(const char *model_path, const char *out_off, float scale, float tx, float ty,
@@ -341,9 +459,11 @@ int main(int argc, char **argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "packet_decode")) return test_packet_decode(argv[2]);
     if (argc == 3 && !std::strcmp(argv[1], "calibration")) return test_calibration(argv[2]);
     if (argc == 5 && !std::strcmp(argv[1], "carve")) return run_carve(argv[2], argv[3], argv[4]);
+    if (argc == 5 && !std::strcmp(argv[1], "script")) return run_script(argv[2], argv[3], argv[4]);
     if (argc == 9 && !std::strcmp(argv[1], "mc"))
         return run_mc(argv[2], argv[3], std::stof(argv[4]), std::stof(argv[5]), std::stof(argv[6]),
                       std::stof(argv[7]), std::stof(argv[8]));
-    std::fprintf(stderr, "usage: test_host model | test_host carve <scene> <out> <mode>\n");
+    std::fprintf(stderr, "usage: test_host model | test_host carve <scene> <out> <mode> | "
+                         "test_host script <scene> <ops> <out>\n");
     return 2;
 }

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from tests import golden_io, scenes
+from tests.stage_model import closure_any_kernel
 
 pytestmark = pytest.mark.gpu
 
@@ -70,31 +71,6 @@ def test_closure_multiword_rows_random_occupancy(arvx, oracle, dims, ksize):
     assert np.array_equal(idx, filled) and len(idx) > 0
 
 
-def closure_any_kernel(model, X, Y, Z, ksize):
-    """numpy restatement of applyClosure for any odd kernel size (the oracle's C
-    version is the literal 3x3x3 one): mean RGBA of the occupied neighbours, summed in
-    the reference's x, y, z offset order in fp32."""
-    r = (ksize - 1) // 2
-    m = model.reshape(Z, Y, X, 4)
-    occ = m[..., 3] != 0
-    out = m.copy()
-    pad = np.zeros((Z + 2 * r, Y + 2 * r, X + 2 * r, 4), np.float32)
-    pad[r:r + Z, r:r + Y, r:r + X] = np.where(occ[..., None], m, 0)
-    pocc = np.zeros((Z + 2 * r, Y + 2 * r, X + 2 * r), np.float32)
-    pocc[r:r + Z, r:r + Y, r:r + X] = occ
-    acc = np.zeros((Z, Y, X, 4), np.float32)
-    cnt = np.zeros((Z, Y, X), np.float32)
-    for a in range(-r, r + 1):          # x offset outermost (src/Postprocessing3d.cpp:31-48)
-        for b in range(-r, r + 1):
-            for c in range(-r, r + 1):
-                sl = (slice(r + c, r + c + Z), slice(r + b, r + b + Y), slice(r + a, r + a + X))
-                acc = (acc + pad[sl]).astype(np.float32)
-                cnt += pocc[sl]
-    fill = (~occ) & (cnt > 0)
-    out[fill] = (acc[fill] / cnt[fill][:, None]).astype(np.float32)
-    return out.reshape(-1, 4)
-
-
 def test_closure_kernel_5_and_uploaded_colors(arvx, oracle):
     """Bigger box, and a model whose colours come from the caller (arvx_colors_upload)."""
     X, Y, Z = 18, 15, 12
@@ -120,6 +96,34 @@ def test_closure_kernel_5_and_uploaded_colors(arvx, oracle):
         else:
             assert len(idx) > 0 and np.all(out[idx, 3] == 1.0)
             assert np.array_equal(out[occ], model[occ])
+
+
+@pytest.mark.parametrize("ksize", [5, 7, 9])
+def test_closure_large_kernels_exact_colors(arvx, oracle, ksize):
+    """Kernel sizes above 3 with uploaded, non-uniform colours and some voxels painted
+    UNSEEN_COLOR (bit2): the whole RGBA model -- every filled voxel's mean of its box -- against
+    closure_any_kernel, bit for bit."""
+    X, Y, Z = 37, 23, 19
+    rng = np.random.default_rng(50 + ksize)
+    st0 = np.where(rng.random((Z, Y, X)) < 0.06, 3, 2).astype(np.uint8).reshape(-1)
+    occ = np.flatnonzero(st0 & 1)
+    painted = occ[rng.random(len(occ)) < 0.2]
+    st0[painted] |= 4
+    pick = np.setdiff1d(occ[rng.random(len(occ)) < 0.6], painted)
+    model = oracle.model_from_state(st0 & 3)
+    model[painted] = (204, 0, 0, 1)
+    model[pick, :3] = rng.integers(0, 256, size=(len(pick), 3)).astype(np.float32)
+    want = closure_any_kernel(model, X, Y, Z, ksize)
+    filled = np.flatnonzero((want[:, 3] != 0) & (model[:, 3] == 0))
+    assert len(filled) > 0 and len(np.unique(want[filled, 0])) > 10  # (means, not one colour)
+    with arvx.Context(X, Y, Z, 0.01) as ctx:
+        ctx.upload_state(st0)
+        ctx.upload_colors(pick, model[pick, :3])
+        idx, rgba = ctx.closure(ksize, False)
+        out = ctx.export_model(False)
+    assert np.array_equal(idx, filled)
+    assert np.array_equal(rgba.view(np.uint32), want[filled].view(np.uint32))
+    assert np.array_equal(out.view(np.uint32), want.view(np.uint32))
 
 
 @pytest.mark.parametrize("name", golden_io.names())

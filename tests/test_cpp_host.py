@@ -159,8 +159,9 @@ def test_cpp_model_answers_from_packets(host_bin, oracle, tmp_path, X, Y, Z):
     assert r.returncode == 0, r.stderr + r.stdout
     rgba, seen = read_result(out, X * Y * Z)
     M = oracle.compose(sc.K, sc.Rt)
-    st0[1, 1, 1] &= 0xfe  # the binary's set(1, 1, 1, zero) between its two carves
-    st = oracle.carve(X, Y, Z, s, M, sc.masks, state=st0)
+    st = oracle.carve(X, Y, Z, s, M[2:], sc.masks[2:], state=st0)  # views 2.. first
+    st[1, 1, 1] &= 0xfe  # the binary's set(1, 1, 1, zero) between its two carves
+    st = oracle.carve(X, Y, Z, s, M[:2], sc.masks[:2], state=st)  # then views 0 and 1
     want = oracle.handle_unseen(st, oracle.model_from_state(st))
     assert np.array_equal(seen, (st.reshape(-1) & 2) == 2)
     assert np.array_equal(rgba, want)
@@ -287,3 +288,111 @@ def test_bench6_table(host_bin, oracle, tmp_path):
             name = f"out/bench/mesh_large_{ver}_avg.off"
             assert open(os.path.join(str(tmp_path), name), "rb").read() == want.encode()
     print(r.stdout[r.stdout.index("Benchmark (all"):])
+
+
+# ---- Model scripts (test_host script) against tests/stage_model.HostModel -------------------
+
+SCRIPT_GRIDS = {"packets": (64, 24, 16), "planes": (30, 20, 12)}  # (X % 32 == 0: the packet form)
+
+
+def script_ops(seed, X, Y, Z):
+    """A seeded script: stages, accessor sweeps, host writes, copies and dumps in random order."""
+    rng = np.random.default_rng(300 + seed)
+    ops = []
+    kinds = ["carve", "carve_views", "fast", "closest", "average", "unseen", "closure", "get", "visited",
+             "inner", "occ_plane", "set", "see", "copy", "dump"]
+    p = np.array([10, 6, 3, 6, 6, 10, 9, 7, 4, 3, 3, 5, 5, 3, 10], float)
+    for _ in range(int(rng.integers(6, 13))):
+        k = kinds[rng.choice(len(kinds), p=p / p.sum())]
+        if k == "carve_views":
+            f = int(rng.integers(0, 4))
+            ops.append(f"carve {f} {int(rng.integers(1, 5 - f))}")
+        elif k == "closure":
+            ops.append(f"closure {int(rng.choice([1, 3, 3, 5]))}")
+        elif k == "set":
+            x, y, z = int(rng.integers(X)), int(rng.integers(Y)), int(rng.integers(Z))
+            v = rng.choice([0, 1, 2])
+            rgb = rng.integers(0, 256, 3) if v else (0, 0, 0)
+            ops.append(f"set {x} {y} {z} {rgb[0]} {rgb[1]} {rgb[2]} {0 if v == 0 else 1}")
+        elif k == "see":
+            ops.append(f"see {int(rng.integers(X))} {int(rng.integers(Y))} {int(rng.integers(Z))}")
+        else:
+            ops.append(k)
+    ops.append("dump")
+    return ops
+
+
+def run_script(host_bin, oracle, tmp_path, grid, ops):
+    from tests import stage_model as sm
+    X, Y, Z = grid
+    V = 5
+    sc = scenes.syn.sphere_scene(32, V, W=96, H=72, with_images=True)
+    s = np.float32(0.512 / max(X, Y, Z))
+    rng = np.random.default_rng(X + Y + Z)
+    st0 = np.where(rng.random((Z, Y, X)) < 0.05, 0, 1).astype(np.uint8)
+    st0 |= (rng.random((Z, Y, X)) < 0.1).astype(np.uint8) * 2
+    scene, script, out = str(tmp_path / "scene.bin"), str(tmp_path / "ops.txt"), str(tmp_path / "out.bin")
+    write_scene(scene, X, Y, Z, s, sc.K, sc.Rt, sc.masks, sc.images, st0)
+    with open(script, "w") as f:
+        f.write("\n".join(ops) + "\n")
+    r = subprocess.run([host_bin, "script", scene, script, out], capture_output=True, text=True)
+    assert r.returncode == 0, f"ops {ops}: {r.stderr[-2000:]}"
+    h = sm.HostModel(sm.Scene(oracle, X, Y, Z, s, oracle.compose(sc.K, sc.Rt), sc.campos, sc.masks, sc.images),
+                     st0)
+    n = X * Y * Z
+    raw = np.fromfile(out, np.uint8)
+    ndump = 0
+    for step, op in enumerate(ops):
+        a = op.split()
+        if a[0] == "carve":
+            h.carve(*[int(v) for v in a[1:]])
+        elif a[0] == "fast":
+            h.fast_carve()
+        elif a[0] in ("closest", "average"):
+            h.color(0 if a[0] == "closest" else 1)
+        elif a[0] == "unseen":
+            h.handle_unseen()
+        elif a[0] == "closure":
+            h.closure(int(a[1]))
+        elif a[0] == "set":
+            h.set(*[int(v) for v in a[1:4]], [float(v) for v in a[4:]])
+        elif a[0] == "see":
+            h.see(*[int(v) for v in a[1:]])
+        elif a[0] == "dump":
+            chunk = raw[ndump * 17 * n:(ndump + 1) * 17 * n]
+            rgba = chunk[:16 * n].view(np.float32).reshape(n, 4)
+            seen = chunk[16 * n:].astype(bool)
+            bad = np.flatnonzero((rgba != h.rgba).any(axis=1) | (seen != h.seen))
+            assert len(bad) == 0, (f"ops {ops[:step + 1]}: {len(bad)} voxels differ at dump {ndump}, first "
+                                   f"{bad[:4].tolist()}: want {h.rgba[bad[:2]].tolist()} {h.seen[bad[:2]].tolist()} "
+                                   f"got {rgba[bad[:2]].tolist()} {seen[bad[:2]].tolist()}")
+            ndump += 1
+    assert len(raw) == ndump * 17 * n
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("grid", sorted(SCRIPT_GRIDS))
+@pytest.mark.parametrize("seed", range(8))
+def test_cpp_model_scripts(host_bin, oracle, tmp_path, grid, seed):
+    """Seeded orders of Model operations (reference Model semantics: a carve zeroes what it
+    removes and keeps the colours of the rest, handleUnseen paints every never-seen voxel, the
+    closure averages its box), every dump against HostModel."""
+    X, Y, Z = SCRIPT_GRIDS[grid]
+    run_script(host_bin, oracle, tmp_path, SCRIPT_GRIDS[grid], script_ops(seed, X, Y, Z))
+
+
+PINNED_SCRIPTS = {
+    # handleUnseen on the host while the planes are still packets (after get): it must paint the
+    # carved state, not the planes from before the carve, and the closure's upload must send that
+    "unseen_after_a_read": ["carve", "get", "unseen", "closure 3", "dump"],
+    # paint of voxels that a later carve removed: the closure's byte upload must not mark them
+    # painted (the device would count them as occupied UNSEEN_COLOR voxels)
+    "carved_paint": ["unseen", "carve", "closure 3", "dump"],
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("grid", sorted(SCRIPT_GRIDS))
+@pytest.mark.parametrize("name", sorted(PINNED_SCRIPTS))
+def test_cpp_model_pinned_scripts(host_bin, oracle, tmp_path, grid, name):
+    run_script(host_bin, oracle, tmp_path, SCRIPT_GRIDS[grid], PINNED_SCRIPTS[name])
