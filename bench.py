@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- dense carve throughput on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One step = one pass of the hot path over one synthetic batch: a fresh model
 (all voxels occupied) is carved by all V silhouette views (sphere
@@ -13,9 +13,10 @@ rebuilt inside every timed step (arvx_set_views_device), then arvx_carve runs.
 
 `value` / `ms_per_step`: the K steps run ONE AFTER THE OTHER on one context and stream (the
 metric is a carve's wall time: reference src/VoxelCarving.cpp:60-72 is one call, one carve), timed
-R = 5 times (`rounds`: every round's figure, median, min, max; `value` is the median round), plus one
-further round with HIP events around single launches for `carve_kernel_ms` / `views_kernel_ms` / the
-`roofline` (the events cost GPU time between dependent kernels: that round is not part of `value`).
+R = 5 times (`rounds`: every round's figure, median, min, max; `value` is the median round); --full
+adds one further round with HIP events around single launches for `carve_kernel_ms` /
+`views_kernel_ms` / the `roofline` (the events cost GPU time between dependent kernels: that round is
+not part of `value`).
 `throughput_jobs_in_flight`: the same K steps dealt to --jobs-in-flight contexts (default 4), each on
 its own stream -- a caller with a stream of frames hides one job's latency-bound kernels behind
 another's issue-bound one; reported beside the headline, never as it.
@@ -37,10 +38,15 @@ N > 1   one rank per GPU; rank r carves Z slab r of a grid that holds N x 512^3
         --jobs 1 the hand-off of step k runs on a second stream beside step k + 1
         (arvx_ctx_set_exchange_stream).  Every job's hand-off is inside the timed region.
 
-The JSON line also carries `roofline` (algorithmic HBM bytes of SURVEY 8d / the
-carve kernel's launch time measured with HIP events on its own stream) and
-`cpu_baseline` (the CPU oracle's reference-shaped port, one thread, timed on this
-host on a bounded slab of the same workload).
+A plain run does only what the headline needs: set-up, the W warm-up steps, the R timed rounds of
+K steps, --dump-outputs, and the JSON line (`full`: false).  Everything else the line can carry runs
+with --full only: the round with HIP events (`carve_kernel_ms`, `views_kernel_ms`, `roofline`:
+algorithmic HBM bytes of SURVEY 8d / the carve kernel's launch time measured with HIP events on its
+own stream), `throughput_jobs_in_flight`, `e2e`, `extra` (--extra-grid), `ablation_no_cull`,
+`cpu_baseline` (the CPU oracle's reference-shaped port, one thread, timed on this host on a bounded
+slab of the same workload) with `parity_vs_oracle`, `workloads`, and for N > 1 the other
+`collectives`, `c4_1024x72` and `arvx_mgpu`.  The --no-* switches, --extra-grid and
+--jobs-in-flight choose among those legs.
 """
 from __future__ import annotations
 
@@ -303,6 +309,97 @@ def run_workloads(capi, synthetic, dev, check):
     return out
 
 
+def roofline(r, no_cull, world):
+    """--full: `roofline` of the headline's carve kernels, from the kernel times of its round with
+    HIP events (`r`: what run_config returned) and the PMC counts of profiles/traffic.json."""
+    from ar_voxel_project_amd import build
+    # roofline of the carve kernels: SURVEY 8(d) algorithmic bytes, HBM-read side:
+    # N*V (one state byte per voxel-view) + V*W*H (one mask byte per pixel), for the
+    # voxels THIS rank's launch processes.
+    nv_rank = r["X"] * r["Y"] * r["nplanes"]
+    alg_bytes = nv_rank * r["V"] + r["V"] * r["sc"].W * r["sc"].H
+    kern_ms = r["kern_ms"]  # None without events (ARVX_BENCH_EVENTS=none)
+    views_ms = r["views_ms"]
+    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms else None
+    traffic = traffic_step = None
+    valu = valu_all = valu_views = None
+    profile_note = None
+    tpath = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tpath) and world == 1:
+        try:
+            tj = json.load(open(tpath))
+            key = f"{r['X']}x{r['Y']}x{r['Z']}x{r['V']}" + ("_nocull" if no_cull else "")
+            ent = tj.get(key, {})
+            stamp = build.source_stamp()
+            if ent and ent.get("source_stamp") != stamp:
+                # the PMC pass was taken on other kernel sources: its counts say nothing about this build
+                profile_note = (f"profiles/traffic.json[{key}] was taken on kernel sources "
+                                f"{ent.get('source_stamp')}, this build is {stamp}: no PMC figures")
+                ent = {}
+            traffic = ent.get("bytes_per_launch")
+            traffic_step = ent.get("bytes_per_step")
+            valu_all = ent.get("valu_wave_instructions") or None
+            valu_views = ent.get("valu_wave_instructions_views") or None
+            ins = ent.get("valu_wave_instructions", {}).get("exact")
+            t_ns = ent.get("kernel_avg_ns_rocprofv3", {}).get("exact")
+            if ins and t_ns:
+                peak = 256 * 4 * 2.4e9 / 2
+                valu = {"kernel": "carve_exact_blocks_kernel", "SQ_INSTS_VALU": ins,
+                        "kernel_us_rocprofv3": t_ns / 1e3, "achieved_Ginst_per_s": ins / t_ns,
+                        "peak_Ginst_per_s": peak / 1e9, "frac": ins / (t_ns * 1e-9) / peak,
+                        "source": "profiles/traffic.json (PMC pass of the same command, same sources)"}
+        except Exception as ex:  # noqa: BLE001
+            profile_note = f"profiles/traffic.json unreadable: {ex}"
+            traffic = None
+    phys = (traffic / (kern_ms * 1e-3) / 1e9) if (traffic and kern_ms) else None
+    step_kernel_ms = (kern_ms + views_ms) if (kern_ms and views_ms) else None
+    # What bounds the carve is vector-instruction issue (the exact kernel) and dependent-read
+    # latency (the classification), not HBM: the roofline is stated against the issue peak --
+    # 256 CUs x 4 SIMDs, one wave64 instruction per 2 cycles at 2.4 GHz (the guide's FP32 vector
+    # peak counted in instructions; fp64 adds / converts issue at half that).  Work = the VALU
+    # wave-instructions of the launch's three kernels (SQ_INSTS_VALU, a PMC pass of the same
+    # command: profiles/traffic.json -- deterministic for a fixed scene), time = this run's.
+    VALU_PEAK = 256 * 4 * 2.4e9 / 2 / 1e9  # G wave-instructions / s
+    ins_all = sum(valu_all.values()) if valu_all else None
+    ok_k = bool(ins_all and kern_ms)
+    return {"bound": "valu-issue",
+            "achieved": (ins_all / (kern_ms * 1e-3) / 1e9) if ok_k else None,
+            "peak": VALU_PEAK, "unit": "G wave-instructions/s",
+            "frac": (ins_all / (kern_ms * 1e-3) / 1e9 / VALU_PEAK) if ok_k else None,
+            "traffic": traffic,
+            "kernel": "carve_coarse_kernel + carve_classify_dense_kernel + "
+                      "carve_exact_blocks_kernel<LEFT> (one arvx_carve call of a fresh model)",
+            "kernel_ms": kern_ms,
+            "valu_wave_instructions": valu_all,
+            "dominant_kernel": valu,
+            "profile_note": profile_note,
+            "measured_here": "kernel_ms (HIP events on the launch stream)",
+            "from_profiles": "valu_wave_instructions, traffic, dominant_kernel: "
+                             "profiles/traffic.json (rocprofv3 --pmc passes of this command, tied "
+                             "to the kernel sources by `source_stamp`)",
+            "hbm_effective": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
+                              "algorithmic_bytes": alg_bytes,
+                              "note": "SURVEY 8d's per-view streaming formulation (N*V + V*W*H "
+                                      "read bytes) / kernel time: an EFFECTIVE rate -- the "
+                                      "kernels keep 2 bits per voxel, write them once and settle "
+                                      "~99 % of the (sub-tile, view) pairs from pixel "
+                                      "rectangles, so it exceeds the physical peak"},
+            "hbm_physical": {"traffic_bytes": traffic, "GBps": phys,
+                             "frac": (phys / HBM_PEAK_GBS) if phys else None,
+                             "note": "2 x FETCH_SIZE + WRITE_SIZE per the guide's gfx950 "
+                                     "correction"},
+            "step": {"kernels": "views_strip_kernel (arvx_set_views_device) + the three carve kernels",
+                     "kernel_ms": step_kernel_ms,
+                     "valu_wave_instructions": ((ins_all + sum(valu_views.values()))
+                                                if (ins_all and valu_views) else None),
+                     "hbm_effective_frac": (alg_bytes / (step_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
+                     if step_kernel_ms else None,
+                     "traffic": traffic_step,
+                     "hbm_physical_frac": (traffic_step / (step_kernel_ms * 1e-3) / 1e9 /
+                                           HBM_PEAK_GBS) if (traffic_step and step_kernel_ms) else None}}
+
+
 def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: run `python -m torch.distributed.run
     --nproc-per-node N bench.py <the same arguments>` as a child process (one rank per GPU, RCCL
@@ -361,28 +458,33 @@ def main():
                     help="jobs in flight for the HEADLINE (default 1: one step after the other, what "
                          "the metric means); > 1 deals the steps to that many contexts and streams")
     ap.add_argument("--jobs-in-flight", type=int, default=4,
-                    help="the `throughput_jobs_in_flight` leg: every job is a whole step (fresh "
+                    help="the `throughput_jobs_in_flight` leg (--full): every job is a whole step (fresh "
                          "model, views derived, carved); job k runs on context and stream k %% jobs, "
                          "so that the latency-bound head of one job runs beside the issue-bound "
                          "exact kernel of another (0 = skip the leg)")
     ap.add_argument("--rounds", type=int, default=5,
                     help="the timed region (K steps) is run this many times: median / min / max")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end (PCIe-inclusive) leg")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end (PCIe-inclusive) leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-ablation", action="store_true",
-                    help="skip the NO_CULL ablation leg (keeps a profile to one kernel variant)")
+                    help="--full: skip the NO_CULL ablation leg (keeps a profile to one kernel variant)")
     ap.add_argument("--extra-grid", type=int, default=1024,
-                    help="also time this grid at N=1 (0 = skip); reported under 'extra'")
+                    help="--full: also time this grid at N=1 (0 = skip); reported under 'extra'")
     ap.add_argument("--no-mgpu", action="store_true",
-                    help="N > 1: skip the one-process-all-GPUs leg (libarvx_mgpu.so)")
+                    help="--full, N > 1: skip the one-process-all-GPUs leg (libarvx_mgpu.so)")
     ap.add_argument("--no-workloads", action="store_true",
-                    help="skip the `workloads` array (the other BASELINE configurations, a worst "
+                    help="--full: skip the `workloads` array (the other BASELINE configurations, a worst "
                          "case for the culling and the 1024^3 target with parity)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the headline's last timed step computed -- the carved state "
                          "(whole, or a fixed seeded sample of a large one) and its per-row counts; "
                          "N > 1: also the merged occupancy -- as DIR/<name>.npy (float32 / float64, "
                          "at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the HIP-event round (kernel times, "
+                         "roofline), jobs in flight, e2e, the extra grid, the no-cull ablation, the CPU "
+                         "baseline with parity, the workloads, and for N > 1 the other collectives, "
+                         "BASELINE config 4 and the one-process leg (default: the headline alone)")
     args = ap.parse_args()
 
     if args.gpus < 1:
@@ -487,6 +589,8 @@ def main():
                                                        for _ in range(3))
               for k in range(n_ev)}
         if jobs > 1:  # kernels of several jobs interleave: a launch has no duration of its own
+            ev = {}
+        if not args.full:  # the round with the events only serves the kernel times of --full
             ev = {}
         nstep = [0]
         merge_ok = [None]
@@ -673,11 +777,13 @@ def main():
     def measure(base, V, steps, warmup, collective, jobs, rounds=1):
         """K steps, `jobs` in flight (1: one after the other), `rounds` times.  With jobs > 1 a launch
         has no duration of its own: the kernel times then come from a short run of one job after
-        the other in the same frame."""
+        the other in the same frame (--full)."""
         m = run_config(base, V, steps, warmup, collective, jobs=jobs, rounds=rounds)
         m["latency_ms"] = m["dt"] / steps * 1e3
         m["latency_steps"] = steps
-        if jobs > 1 and not m["overflowed"]:
+        if jobs > 1 and not args.full:  # the latency run below is one of --full
+            m["latency_ms"] = m["latency_steps"] = None
+        elif jobs > 1 and not m["overflowed"]:
             k = max(8, steps // 2)
             q = run_config(base, V, k, min(warmup, 5), collective, jobs=1)
             m.update(kern_ms=q["kern_ms"], views_ms=q["views_ms"], ev_steps=q["ev_steps"],
@@ -699,92 +805,6 @@ def main():
                   "note": f"every round = exactly {args.steps} steps one after the other between "
                           "barrier + synchronize; `value` / `ms_per_step` = the median round"}
 
-    # roofline of the carve kernels: SURVEY 8(d) algorithmic bytes, HBM-read side:
-    # N*V (one state byte per voxel-view) + V*W*H (one mask byte per pixel), for the
-    # voxels THIS rank's launch processes.
-    nv_rank = r["X"] * r["Y"] * r["nplanes"]
-    alg_bytes = nv_rank * r["V"] + r["V"] * r["sc"].W * r["sc"].H
-    kern_ms = r["kern_ms"]  # None without events (ARVX_BENCH_EVENTS=none)
-    views_ms = r["views_ms"]
-    achieved = alg_bytes / (kern_ms * 1e-3) / 1e9 if kern_ms else None
-    traffic = traffic_step = None
-    valu = valu_all = valu_views = None
-    profile_note = None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath) and world == 1:
-        try:
-            tj = json.load(open(tpath))
-            key = f"{r['X']}x{r['Y']}x{r['Z']}x{r['V']}" + ("_nocull" if args.no_cull else "")
-            ent = tj.get(key, {})
-            stamp = build.source_stamp()
-            if ent and ent.get("source_stamp") != stamp:
-                # the PMC pass was taken on other kernel sources: its counts say nothing about this build
-                profile_note = (f"profiles/traffic.json[{key}] was taken on kernel sources "
-                                f"{ent.get('source_stamp')}, this build is {stamp}: no PMC figures")
-                ent = {}
-            traffic = ent.get("bytes_per_launch")
-            traffic_step = ent.get("bytes_per_step")
-            valu_all = ent.get("valu_wave_instructions") or None
-            valu_views = ent.get("valu_wave_instructions_views") or None
-            ins = ent.get("valu_wave_instructions", {}).get("exact")
-            t_ns = ent.get("kernel_avg_ns_rocprofv3", {}).get("exact")
-            if ins and t_ns:
-                peak = 256 * 4 * 2.4e9 / 2
-                valu = {"kernel": "carve_exact_blocks_kernel", "SQ_INSTS_VALU": ins,
-                        "kernel_us_rocprofv3": t_ns / 1e3, "achieved_Ginst_per_s": ins / t_ns,
-                        "peak_Ginst_per_s": peak / 1e9, "frac": ins / (t_ns * 1e-9) / peak,
-                        "source": "profiles/traffic.json (PMC pass of the same command, same sources)"}
-        except Exception as ex:  # noqa: BLE001
-            profile_note = f"profiles/traffic.json unreadable: {ex}"
-            traffic = None
-    phys = (traffic / (kern_ms * 1e-3) / 1e9) if (traffic and kern_ms) else None
-    step_kernel_ms = (kern_ms + views_ms) if (kern_ms and views_ms) else None
-    # What bounds the carve is vector-instruction issue (the exact kernel) and dependent-read
-    # latency (the classification), not HBM: the roofline is stated against the issue peak --
-    # 256 CUs x 4 SIMDs, one wave64 instruction per 2 cycles at 2.4 GHz (the guide's FP32 vector
-    # peak counted in instructions; fp64 adds / converts issue at half that).  Work = the VALU
-    # wave-instructions of the launch's three kernels (SQ_INSTS_VALU, a PMC pass of the same
-    # command: profiles/traffic.json -- deterministic for a fixed scene), time = this run's.
-    VALU_PEAK = 256 * 4 * 2.4e9 / 2 / 1e9  # G wave-instructions / s
-    ins_all = sum(valu_all.values()) if valu_all else None
-    ok_k = bool(ins_all and kern_ms)
-    roofline = {"bound": "valu-issue",
-                "achieved": (ins_all / (kern_ms * 1e-3) / 1e9) if ok_k else None,
-                "peak": VALU_PEAK, "unit": "G wave-instructions/s",
-                "frac": (ins_all / (kern_ms * 1e-3) / 1e9 / VALU_PEAK) if ok_k else None,
-                "traffic": traffic,
-                "kernel": "carve_coarse_kernel + carve_classify_dense_kernel + "
-                          "carve_exact_blocks_kernel<LEFT> (one arvx_carve call of a fresh model)",
-                "kernel_ms": kern_ms,
-                "valu_wave_instructions": valu_all,
-                "dominant_kernel": valu,
-                "profile_note": profile_note,
-                "measured_here": "kernel_ms (HIP events on the launch stream)",
-                "from_profiles": "valu_wave_instructions, traffic, dominant_kernel: "
-                                 "profiles/traffic.json (rocprofv3 --pmc passes of this command, tied "
-                                 "to the kernel sources by `source_stamp`)",
-                "hbm_effective": {"achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
-                                  "algorithmic_bytes": alg_bytes,
-                                  "note": "SURVEY 8d's per-view streaming formulation (N*V + V*W*H "
-                                          "read bytes) / kernel time: an EFFECTIVE rate -- the "
-                                          "kernels keep 2 bits per voxel, write them once and settle "
-                                          "~99 % of the (sub-tile, view) pairs from pixel "
-                                          "rectangles, so it exceeds the physical peak"},
-                "hbm_physical": {"traffic_bytes": traffic, "GBps": phys,
-                                 "frac": (phys / HBM_PEAK_GBS) if phys else None,
-                                 "note": "2 x FETCH_SIZE + WRITE_SIZE per the guide's gfx950 "
-                                         "correction"},
-                "step": {"kernels": "views_strip_kernel (arvx_set_views_device) + the three carve kernels",
-                         "kernel_ms": step_kernel_ms,
-                         "valu_wave_instructions": ((ins_all + sum(valu_views.values()))
-                                                    if (ins_all and valu_views) else None),
-                         "hbm_effective_frac": (alg_bytes / (step_kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
-                         if step_kernel_ms else None,
-                         "traffic": traffic_step,
-                         "hbm_physical_frac": (traffic_step / (step_kernel_ms * 1e-3) / 1e9 /
-                                               HBM_PEAK_GBS) if (traffic_step and step_kernel_ms) else None}}
-
     out = {
         "metric": "Mvoxel-views/s (voxels x views / s) + carve wall-time, 512^3 grid x 36 views",
         "value": value, "unit": "Mvoxel-views/s", "n_gpus": world, "steps": args.steps,
@@ -804,17 +824,22 @@ def main():
         "rounds": rounds_out,
         "latency_ms_per_step": r["latency_ms"],
         "slots_agree": r["slots_agree"],
-        "carve_kernel_ms": kern_ms, "views_kernel_ms": views_ms,
-        "kernel_ms_from": f"HIP events on the launch stream around {r['ev_steps']} of the "
-                          f"{r.get('latency_steps', args.steps)} steps of one further round (an "
-                          f"event is a packet between dependent kernels; that round is not part of "
-                          f"`value`)",
-        "carve_only_value": (vv / (kern_ms * 1e-3) / 1e6) if kern_ms else None,
         "occupied_fraction": r["occ"],
-        "roofline": roofline,
+        "full": args.full,
     }
+    if args.full:
+        kern_ms = r["kern_ms"]  # None without events (ARVX_BENCH_EVENTS=none)
+        out.update({
+            "carve_kernel_ms": kern_ms, "views_kernel_ms": r["views_ms"],
+            "kernel_ms_from": f"HIP events on the launch stream around {r['ev_steps']} of the "
+                              f"{r.get('latency_steps', args.steps)} steps of one further round (an "
+                              f"event is a packet between dependent kernels; that round is not part of "
+                              f"`value`)",
+            "carve_only_value": (vv / (kern_ms * 1e-3) / 1e6) if kern_ms else None,
+            "roofline": roofline(r, args.no_cull, world),
+        })
 
-    if world == 1 and rank == 0 and args.jobs_in_flight > 1 and args.jobs == 1:
+    if args.full and world == 1 and rank == 0 and args.jobs_in_flight > 1 and args.jobs == 1:
         # the same steps with several jobs in flight: a throughput figure of its own, not the headline
         try:
             tj_ = run_config(args.grid, args.views, args.steps, min(args.warmup, 5), "none",
@@ -829,7 +854,7 @@ def main():
         except Exception as ex:  # noqa: BLE001
             out["throughput_jobs_in_flight"] = {"error": f"{type(ex).__name__}: {ex}"}
 
-    if world > 1:
+    if args.full and world > 1:
         # One scaling run answers every collective question: the headline above is the default
         # (compressed all-gather over striped slabs); the north star's all-reduce and the plain
         # all-gather follow with a few steps each -- the same job, the same timing frame, not
@@ -852,12 +877,13 @@ def main():
                 coll[mode] = {"error": f"{type(ex).__name__}: {ex}"}
         if rank == 0:
             out["collectives"] = coll
-            out["collective_backend"] = {
-                "backend": dist.get_backend(), "ranks": dist.get_world_size(),
-                "library": ("gloo (one-GPU rehearsal)" if rehearsal else
-                            "RCCL " + ".".join(str(v) for v in torch.cuda.nccl.version()))}
+    if world > 1 and rank == 0:
+        out["collective_backend"] = {
+            "backend": dist.get_backend(), "ranks": dist.get_world_size(),
+            "library": ("gloo (one-GPU rehearsal)" if rehearsal else
+                        "RCCL " + ".".join(str(v) for v in torch.cuda.nccl.version()))}
 
-    if world == 8 and (args.grid, args.views) == (512, 36):
+    if args.full and world == 8 and (args.grid, args.views) == (512, 36):
         # BASELINE config 4 as it is written: 1024^3 x 72 views over the 8 GPUs
         try:
             k = max(3, args.steps // 2)
@@ -873,7 +899,7 @@ def main():
             if rank == 0:
                 out["c4_1024x72"] = {"error": str(ex)}
 
-    if world > 1 and not rehearsal and not args.no_mgpu:
+    if args.full and world > 1 and not rehearsal and not args.no_mgpu:
         # The same job driven by ONE process over all GPUs (libarvx_mgpu.so: ncclCommInitAll, one
         # stream per device) -- the form a drop-in caller of the reference's carve() uses
         # (include/arvx/multi_gpu.hpp).  Run as a child process of rank 0 while the ranks of this
@@ -894,7 +920,7 @@ def main():
                 out["arvx_mgpu"] = {"error": f"{type(ex).__name__}: {ex}"}
         dist.barrier(group=host)
 
-    if rank == 0 and world == 1 and args.extra_grid and args.extra_grid != args.grid:
+    if args.full and rank == 0 and world == 1 and args.extra_grid and args.extra_grid != args.grid:
         try:
             k = max(3, args.steps // 4)
             e = measure(args.extra_grid, args.views, k, 1, "none", args.jobs, min(3, args.rounds))
@@ -912,7 +938,7 @@ def main():
         except Exception as ex:  # e.g. not enough memory on a shared box
             out["extra"] = {"error": str(ex)}
 
-    if rank == 0 and world == 1 and not args.no_cull and not args.no_ablation:
+    if args.full and rank == 0 and world == 1 and not args.no_cull and not args.no_ablation:
         # Ablation in the same run: the same kernel with the rectangle tests off, i.e.
         # every voxel projected exactly in every view until it is carved (wave ballot
         # early-out only).  This is the closest thing to the per-view streaming
@@ -946,7 +972,7 @@ def main():
         except Exception as ex:
             out["ablation_no_cull"] = {"error": str(ex)}
 
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e:
         # SURVEY 8d's second figure: the step with its inputs coming from and its result going to
         # the HOST -- page-locked u8 masks -> device (arvx_set_views), carve, the carved model back
         # in page-locked memory: as two compressed packets (arvx_state_download_packets; ~1/10 of the
@@ -1025,7 +1051,7 @@ def main():
         except Exception as ex:  # noqa: BLE001
             out["e2e"] = {"error": f"{type(ex).__name__}: {ex}"}
 
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"], oracle_plane = cpu_baseline(r["sc"], r["X"], r["Y"], r["Z"])
         # the state the timed steps left on the GPU against the oracle's, voxel for voxel
         nz = oracle_plane.shape[0]
@@ -1035,11 +1061,11 @@ def main():
         if not same:
             print("[bench] GPU state differs from the oracle in "
                   f"{int((r['state'][:nz] != oracle_plane).sum())} voxels", file=sys.stderr)
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
         out["parity_vs_oracle"] = None
 
-    if rank == 0 and world == 1 and not args.no_workloads:
+    if args.full and rank == 0 and world == 1 and not args.no_workloads:
         try:
             out["workloads"] = run_workloads(capi, synthetic, dev, check=not args.no_cpu)
         except Exception as ex:  # noqa: BLE001

@@ -1,7 +1,8 @@
-"""bench.py as the driver runs it: the one-GPU line and -- rehearsed with two ranks on one GPU
-over gloo (ARVX_BENCH_ONE_GPU=1) -- the N > 1 line with every collective, several jobs in flight
-and the hand-off on its side streams.  Small grids: what is checked is the contract of the JSON
-line and that every merge holds the right planes, not the numbers."""
+"""bench.py as the driver runs it: the plain one-GPU line (the headline alone), the --full line
+and -- rehearsed with two ranks on one GPU over gloo (ARVX_BENCH_ONE_GPU=1) -- the N > 1 line with
+every collective, several jobs in flight and the hand-off on its side streams.  Small grids: what
+is checked is the contract of the JSON line and that every merge holds the right planes, not the
+numbers."""
 import json
 import os
 import subprocess
@@ -11,8 +12,13 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CONTRACT = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
-            "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline")
+HEADLINE = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+            "scaling", "vs_baseline", "dtype", "data", "config")
+CONTRACT = HEADLINE + ("roofline", "cpu_baseline")
+# what only --full measures: legs of their own, beside the headline's timed rounds
+FULL_ONLY = ("carve_kernel_ms", "views_kernel_ms", "kernel_ms_from", "carve_only_value", "roofline",
+             "throughput_jobs_in_flight", "collectives", "c4_1024x72", "arvx_mgpu", "extra",
+             "ablation_no_cull", "e2e", "cpu_baseline", "parity_vs_oracle", "workloads")
 
 
 def free_port():
@@ -28,8 +34,30 @@ def last_json_line(text):
     return json.loads(lines[-1])
 
 
-def test_one_gpu_line():
+def test_plain_line():
+    """A plain run is the headline alone: its timed rounds and the line, no leg of --full (the
+    extra grid, whose default is 1024, included)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--grid", "128", "--steps", "9",
+                        "--warmup", "2", "--rounds", "3"],
+                       capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = last_json_line(r.stdout)
+    for k in HEADLINE:
+        assert k in d, k
+    for k in FULL_ONLY:
+        assert k not in d, k
+    assert d["full"] is False
+    assert d["n_gpus"] == 1 and d["steps"] == 9 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["unit"] == "Mvoxel-views/s" and d["dtype"] == "u8"
+    assert d["config"]["grid"] == [128, 128, 128] and d["config"]["jobs_in_flight"] == 1
+    assert d["rounds"]["n"] == 3 and d["rounds"]["min"] <= d["ms_per_step"] <= d["rounds"]["max"]
+    assert d["value"] == pytest.approx(128 ** 3 * 36 / (d["ms_per_step"] * 1e-3) / 1e6, rel=1e-9)
+    assert d["latency_ms_per_step"] == pytest.approx(d["ms_per_step"], rel=1e-9)
+    assert d["slots_agree"] is True and 0 < d["occupied_fraction"] < 1
+
+
+def test_one_gpu_line():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--grid", "128", "--steps", "9",
                         "--warmup", "2", "--extra-grid", "0", "--no-workloads", "--no-ablation",
                         "--rounds", "3"],
                        capture_output=True, text=True, cwd=ROOT, timeout=600)
@@ -38,6 +66,7 @@ def test_one_gpu_line():
     for k in CONTRACT:
         assert k in d, k
     assert d["n_gpus"] == 1 and d["steps"] == 9 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["full"] is True
     # the headline is one step after the other; several jobs in flight is a figure of its own
     assert d["config"]["jobs_in_flight"] == 1 and d["slots_agree"] is True
     assert d["rounds"]["n"] == 3 and len(d["rounds"]["ms_per_step"]) == 3
@@ -91,7 +120,7 @@ def test_two_rank_rehearsal_every_collective(jobs):
     env = dict(os.environ, ARVX_BENCH_ONE_GPU="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--grid", "128", "--steps", "9",
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--grid", "128", "--steps", "9",
                         "--warmup", "2", "--no-mgpu", "--rounds", "2", "--jobs", str(jobs)],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -124,6 +153,7 @@ def test_bench_starts_its_own_ranks():
     d = last_json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["collective_backend"]["ranks"] == 2
     assert d["config"]["merged_plane_holds_rank0_planes"] is True
+    assert d["full"] is False and "collectives" not in d  # the other collectives are --full's
 
 
 def test_bench_refuses_a_world_that_is_not_gpus():
