@@ -63,6 +63,8 @@ int fail_msg(int code, const char *msg) { return fail(code, "%s", msg); }
 }  // namespace arvx
 
 using arvx::Ctx;
+using Event = Ctx::Event;
+using Form = Ctx::Form;
 
 #define ARVX_CHECK_CTX(ctx)                                          \
     do {                                                             \
@@ -145,7 +147,7 @@ static int check_fault(Ctx *ctx) {
     ctx->compact_tickets = 0;
     ctx->compact_epoch = 0;
     ctx->counts_clean[0] = ctx->counts_clean[1] = false;
-    ctx->packets_valid = false;
+    ctx->packets_seq = 0;
     return fail(ARVX_ERR_HIP, "a kernel gave up waiting for another workgroup (mark %u): the "
                 "results of the calls since the last synchronisation are undefined", what);
 }
@@ -155,16 +157,6 @@ static int check_fault(Ctx *ctx) {
         ARVX_HIP(hipStreamSynchronize((ctx)->stream));        \
         if (int arvx_f_ = check_fault(ctx)) return arvx_f_;   \
     } while (0)
-
-static int ensure_scratch(Ctx *ctx, size_t need) {
-    if (ctx->scratch_bytes >= need) return ARVX_OK;
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    ctx->d_scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    ARVX_HIP(hipMalloc(&ctx->d_scratch, need));
-    ctx->scratch_bytes = need;
-    return ARVX_OK;
-}
 
 static int need_rec(Ctx *ctx, bool lazy_ok = false);
 static void carve_geometry(const Ctx *ctx, arvx::CarveParams &p);
@@ -183,7 +175,7 @@ static int launch_bit_pack(Ctx *ctx, const arvx::BitGrid &g, int closure_occupie
     const size_t nwords = (size_t)g.XW * g.Y * g.Z;
     arvx::CarveParams p;
     carve_geometry(ctx, p);
-    p.rec = ctx->d_rec;
+    p.rec = ctx->rec();
     hipLaunchKernelGGL(arvx::bitgrid_from_rec_kernel, dim3((unsigned)((nwords + 255) / 256)),
                        dim3(256), 0, ctx->stream, p, 0, g.Z, closure_occupied, apply_unseen,
                        closure_occupied ? paint_plane(ctx) : nullptr, occ, unseen);
@@ -340,9 +332,9 @@ static int selftest_xyz(Ctx *ctx, int64_t n, const int32_t *xyz, size_t out_floa
                         Launch launch) {
     if (n < 1 || !xyz || !out) return fail(ARVX_ERR_INVALID, "bad argument");
     const size_t in_bytes = (size_t)n * 3 * sizeof(int32_t);
-    if (int rc = ensure_scratch(ctx, in_bytes + out_floats * sizeof(float) + 64)) return rc;
-    int *d_xyz = (int *)ctx->d_scratch;
-    float *d_out = (float *)((uint8_t *)ctx->d_scratch + ((in_bytes + 15) & ~(size_t)15));
+    ARVX_HIP(ctx->pool_scratch.reserve(in_bytes + out_floats * sizeof(float) + 64));
+    int *d_xyz = (int *)ctx->pool_scratch.p;
+    float *d_out = (float *)((uint8_t *)ctx->pool_scratch.p + ((in_bytes + 15) & ~(size_t)15));
     ARVX_HIP(hipMemcpyAsync(d_xyz, xyz, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     launch(d_xyz, d_out);
     ARVX_HIP(hipGetLastError());
@@ -371,7 +363,7 @@ int arvx_ctx_set_projection_assoc(arvx_ctx *ctx, int assoc) {
     if (!ctx) return fail(ARVX_ERR_INVALID, "null context");
     if (assoc != ARVX_ASSOC_RIGHT && assoc != ARVX_ASSOC_LEFT)
         return fail(ARVX_ERR_INVALID, "grouping %d (ARVX_ASSOC_RIGHT or ARVX_ASSOC_LEFT)", assoc);
-    if (ctx->assoc != assoc) ctx->color_ready = false;  // (colours were voted with the other one)
+    if (ctx->assoc != assoc) ctx->drop(Event::ProjectionAssoc);  // (colours were voted with the other one)
     ctx->assoc = assoc;
     return ARVX_OK;
 }
@@ -444,7 +436,7 @@ int arvx_ctx_create_slab_halo(arvx_ctx **out, int device, int X, int Y, int Z, f
         return arvx::fail_hip(e, "hipStreamCreate", __FILE__, __LINE__);
     }
     c->stream = c->own_stream;
-    e = hipMalloc(&c->d_stats, 16 * sizeof(unsigned long long));  // 8 counters + flags
+    e = c->pool_stats.reserve(16 * sizeof(unsigned long long));  // 8 counters + flags
     if (e != hipSuccess) {
         arvx_ctx_destroy(c);
         return arvx::fail_hip(e, "hipMalloc(stats)", __FILE__, __LINE__);
@@ -463,8 +455,7 @@ int arvx_ctx_create_slab_halo(arvx_ctx **out, int device, int X, int Y, int Z, f
         arvx_ctx_destroy(c);
         return arvx::fail_hip(e, "hipHostMalloc(fault word)", __FILE__, __LINE__);
     }
-    c->fresh_pending = true;  // a fresh Model exists only as this flag: see need_rec
-    e = hipMemsetAsync(c->d_stats, 0, 64, c->stream);
+    e = hipMemsetAsync(c->stats(), 0, 64, c->stream);
     if (e != hipSuccess) {
         arvx_ctx_destroy(c);
         return arvx::fail_hip(e, "hipMemsetAsync", __FILE__, __LINE__);
@@ -501,26 +492,15 @@ int arvx_ctx_create(arvx_ctx **out, int device, int X, int Y, int Z, float voxel
 
 int arvx_ctx_destroy(arvx_ctx *ctx) {
     if (!ctx) return ARVX_OK;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->own_stream) (void)hipStreamSynchronize(ctx->own_stream);
-    ctx->free_views();
-    ctx->free_color();
-    ctx->free_mc();
-    ctx->release_pools();
-    if (ctx->d_flood) (void)hipFree(ctx->d_flood);
-    if (ctx->d_flood_rec) (void)hipFree(ctx->d_flood_rec);
-    if (ctx->d_rec) (void)hipFree(ctx->d_rec);
-    if (ctx->d_state) (void)hipFree(ctx->d_state);
-    if (ctx->d_stats) (void)hipFree(ctx->d_stats);
-    if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    if (ctx->d_coarse) (void)hipFree(ctx->d_coarse);
-    if (ctx->d_stream) (void)hipFree(ctx->d_stream);
-    if (ctx->h_fault) (void)hipHostFree(ctx->h_fault);
-    if (ctx->own_stream) {
-        (void)hipStreamSynchronize(ctx->own_stream);
-        release_stream(ctx->device, ctx->own_stream);
+    const int device = ctx->device;
+    const hipStream_t own = ctx->own_stream;
+    (void)hipSetDevice(device);
+    if (own) (void)hipStreamSynchronize(own);
+    delete ctx;  // (its members free every buffer it holds)
+    if (own) {
+        (void)hipStreamSynchronize(own);
+        release_stream(device, own);
     }
-    delete ctx;
     return ARVX_OK;
 }
 
@@ -573,13 +553,13 @@ static int views_common(Ctx *ctx, int V, const float *M, const float *campos, in
     if (C < 1 || C > 4) return fail(ARVX_ERR_INVALID, "channels=%d out of range [1,4]", C);
     // the same number and size of views as before: keep every buffer (a pipeline sends its
     // views once per stage, src/main.cpp:262-284)
-    const bool same = ctx->d_M && ctx->V == V && ctx->W == W && ctx->H == H;
+    const bool same = ctx->M() && ctx->V == V && ctx->W == W && ctx->H == H;
+    ctx->drop(Event::SetViews);  // colour results belong to the previous views
     ctx->views_ready = false;
     ctx->cameras_ready = false;
-    ctx->free_surface();  // colour results belong to the previous views
     if (!same) {
         ctx->free_views();
-        ctx->free_color();
+        ctx->pool_images.release();
     }
     ctx->images_ready = false;
     ctx->V = V;
@@ -596,10 +576,10 @@ static int views_common(Ctx *ctx, int V, const float *M, const float *campos, in
     ctx->satH = H + 1;
     ctx->satStride = ctx->satW * ctx->satH;
     if (!same) {
-        hipError_t e = hipMalloc(&ctx->d_M, (size_t)V * 12 * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&ctx->d_campos, (size_t)V * 3 * sizeof(float));
-        if (e == hipSuccess) e = hipMalloc(&ctx->d_bg, (size_t)V * ctx->bgWords * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&ctx->d_sat, (size_t)V * ctx->satStride * sizeof(uint16_t));
+        hipError_t e = ctx->pool_M.reserve((size_t)V * 12 * sizeof(float));
+        if (e == hipSuccess) e = ctx->pool_campos.reserve((size_t)V * 3 * sizeof(float));
+        if (e == hipSuccess) e = ctx->pool_bg.reserve((size_t)V * ctx->bgWords * sizeof(uint32_t));
+        if (e == hipSuccess) e = ctx->pool_sat.reserve((size_t)V * ctx->satStride * sizeof(uint16_t));
         if (e != hipSuccess) {
             ctx->free_views();  // whatever was allocated before the failure
             return arvx::fail_hip(e, "hipMalloc(views)", __FILE__, __LINE__);
@@ -612,7 +592,7 @@ static int views_common(Ctx *ctx, int V, const float *M, const float *campos, in
                         memcmp(ctx->h_M.data(), M, (size_t)V * 12 * sizeof(float)) == 0;
     if (!same_M) {
         ctx->h_M.assign(M, M + (size_t)V * 12);
-        ARVX_HIP(hipMemcpyAsync(ctx->d_M, ctx->h_M.data(), (size_t)V * 12 * sizeof(float),
+        ARVX_HIP(hipMemcpyAsync(ctx->M(), ctx->h_M.data(), (size_t)V * 12 * sizeof(float),
                                 hipMemcpyHostToDevice, ctx->stream));
     }
     ctx->has_campos = campos != nullptr;
@@ -621,7 +601,7 @@ static int views_common(Ctx *ctx, int V, const float *M, const float *campos, in
                             memcmp(ctx->h_campos.data(), campos, (size_t)V * 3 * sizeof(float)) == 0;
         if (!same_c) {
             ctx->h_campos.assign(campos, campos + (size_t)V * 3);
-            ARVX_HIP(hipMemcpyAsync(ctx->d_campos, ctx->h_campos.data(),
+            ARVX_HIP(hipMemcpyAsync(ctx->campos(), ctx->h_campos.data(),
                                     (size_t)V * 3 * sizeof(float), hipMemcpyHostToDevice,
                                     ctx->stream));
         }
@@ -655,12 +635,12 @@ static int views_preprocess(Ctx *ctx, const uint8_t *d_masks, int C) {
         unsigned long long *gran = (unsigned long long *)((uint8_t *)ctx->pool_vstrip.p + off_gran);
         if (C == 1)
             hipLaunchKernelGGL(arvx::views_strip_kernel<1>, dim3(TIs, ctx->V), dim3(64 * (ctx->W / 64 + 1)),
-                               0, ctx->stream, d_masks, ctx->W, ctx->H, TIs, ctx->d_bg, ctx->bgWords,
-                               ctx->d_sat, ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault);
+                               0, ctx->stream, d_masks, ctx->W, ctx->H, TIs, ctx->bg(), ctx->bgWords,
+                               ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault);
         else
             hipLaunchKernelGGL(arvx::views_strip_kernel<3>, dim3(TIs, ctx->V), dim3(64 * (ctx->W / 64 + 1)),
-                               0, ctx->stream, d_masks, ctx->W, ctx->H, TIs, ctx->d_bg, ctx->bgWords,
-                               ctx->d_sat, ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault);
+                               0, ctx->stream, d_masks, ctx->W, ctx->H, TIs, ctx->bg(), ctx->bgWords,
+                               ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault);
         ARVX_HIP(hipGetLastError());
         ctx->views_ready = true;
         ctx->cameras_ready = true;
@@ -668,32 +648,32 @@ static int views_preprocess(Ctx *ctx, const uint8_t *d_masks, int C) {
     }
     if (C == 1 && npix % 32 == 0 && ((uintptr_t)d_masks & 15u) == 0) {
         hipLaunchKernelGGL(arvx::views_bits16_kernel, dim3((npix / 16 + 255) / 256, ctx->V),
-                           dim3(256), 0, ctx->stream, d_masks, npix, ctx->d_bg, ctx->bgWords);
+                           dim3(256), 0, ctx->stream, d_masks, npix, ctx->bg(), ctx->bgWords);
     } else if (C == 1 || C == 3) {
         const dim3 g1(((npix + 3) / 4 + 255) / 256, ctx->V);
         if (C == 1)
             hipLaunchKernelGGL(arvx::views_bits_kernel<1>, g1, dim3(256), 0, ctx->stream, d_masks,
-                               npix, ctx->d_bg, ctx->bgWords);
+                               npix, ctx->bg(), ctx->bgWords);
         else
             hipLaunchKernelGGL(arvx::views_bits_kernel<3>, g1, dim3(256), 0, ctx->stream, d_masks,
-                               npix, ctx->d_bg, ctx->bgWords);
+                               npix, ctx->bg(), ctx->bgWords);
     } else {
         const dim3 g1((npix + 255) / 256, ctx->V);
         hipLaunchKernelGGL(arvx::views_bits_generic_kernel, g1, dim3(256), 0, ctx->stream, d_masks,
-                           C, npix, ctx->d_bg, ctx->bgWords);
+                           C, npix, ctx->bg(), ctx->bgWords);
     }
     ARVX_HIP(hipGetLastError());
     const int W = ctx->W, H = ctx->H, V = ctx->V;
     // tiles of 64 table columns x 64 image rows (views_kernels.h)
     const int TJ = (W + 1 + 63) / 64, TI = (H + arvx::kTileRows - 1) / arvx::kTileRows;
     const size_t n_rs = (size_t)V * H * TJ, n_T = (size_t)V * TI * TJ * 64, n_ts = (size_t)V * TI * TJ;
-    if (int rc = ensure_scratch(ctx, (n_rs + n_T + n_ts) * sizeof(int) + 64)) return rc;
-    int *d_rs = (int *)ctx->d_scratch, *d_T = d_rs + n_rs, *d_ts = d_T + n_T;
+    ARVX_HIP(ctx->pool_scratch.reserve((n_rs + n_T + n_ts) * sizeof(int) + 64));
+    int *d_rs = (int *)ctx->pool_scratch.p, *d_T = d_rs + n_rs, *d_ts = d_T + n_T;
     const unsigned tgrid = (unsigned)(((size_t)TJ * TI * V + 3) / 4);
     hipLaunchKernelGGL(arvx::views_tile_sums_kernel, dim3(tgrid), dim3(256), 0, ctx->stream,
-                       ctx->d_bg, ctx->bgWords, W, H, TJ, TI, V, d_rs, d_T, d_ts);
+                       ctx->bg(), ctx->bgWords, W, H, TJ, TI, V, d_rs, d_T, d_ts);
     hipLaunchKernelGGL(arvx::views_table_kernel, dim3(tgrid), dim3(256), 0, ctx->stream,
-                       ctx->d_bg, ctx->bgWords, W, H, TJ, TI, V, d_rs, d_T, d_ts, ctx->d_sat,
+                       ctx->bg(), ctx->bgWords, W, H, TJ, TI, V, d_rs, d_T, d_ts, ctx->sat(),
                        ctx->satStride, ctx->satW);
     ARVX_HIP(hipGetLastError());
     ctx->views_ready = true;
@@ -798,8 +778,8 @@ int arvx_undistort(arvx_ctx *ctx, int V, const uint8_t *const *src, int W, int H
     if (stride < rowb) return fail(ARVX_ERR_INVALID, "stride %zu < W*C", stride);
     for (int i = 0; i < V; ++i)
         if (!src[i] || !dst[i]) return fail(ARVX_ERR_INVALID, "null image %d", i);
-    if (int rc = ensure_scratch(ctx, 2 * img * V + 64)) return rc;
-    uint8_t *d_src = (uint8_t *)ctx->d_scratch, *d_dst = d_src + img * V;
+    ARVX_HIP(ctx->pool_scratch.reserve(2 * img * V + 64));
+    uint8_t *d_src = (uint8_t *)ctx->pool_scratch.p, *d_dst = d_src + img * V;
     for (int i = 0; i < V; ++i)
         ARVX_HIP(hipMemcpy2DAsync(d_src + img * i, rowb, src[i], stride, rowb, H,
                                   hipMemcpyHostToDevice, ctx->stream));
@@ -834,22 +814,18 @@ static void carve_geometry(const Ctx *ctx, arvx::CarveParams &p) {
     p.coarseX = (p.X + arvx::kCoarseX - 1) / arvx::kCoarseX;
     p.coarseY = (p.Y + (8 << p.cyShift) - 1) / (8 << p.cyShift);
     p.coarseZ = (p.Z + (8 << p.czShift) - 1) / (8 << p.czShift);
-    p.ccode = ctx->lazy ? (const uint8_t *)ctx->pool_ccode.p : nullptr;
+    p.ccode = ctx->form == Form::Lazy ? (const uint8_t *)ctx->pool_ccode.p : nullptr;
 }
 
 // a record buffer for this context's grid, every record "finished" when it is new
-static int ensure_records(Ctx *ctx, void **buf, size_t *cap) {
+static int ensure_records(Ctx *ctx, arvx::DevPool &buf) {
     arvx::CarveParams g;
     carve_geometry(ctx, g);
     const size_t need = arvx::rec_count(g) * arvx::kRecU16 * sizeof(uint16_t);
-    if (*cap >= need) return ARVX_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    ARVX_HIP(hipMalloc(buf, need));
-    *cap = need;
+    if (buf.cap >= need) return ARVX_OK;
+    ARVX_HIP(buf.reserve(need));
     hipLaunchKernelGGL(arvx::rec_init_kernel, dim3(2048), dim3(256), 0, ctx->stream,
-                       (uint32_t *)*buf, need / 4);
+                       (uint32_t *)buf.p, need / 4);
     ARVX_HIP(hipGetLastError());
     return ARVX_OK;
 }
@@ -858,35 +834,23 @@ static int ensure_records(Ctx *ctx, void **buf, size_t *cap) {
 // coarse tiles a fresh carve settled as a whole from their codes (CarveParams::ccode); everybody
 // else gets those tiles written out first -- the fill the carve itself skipped.
 static int need_rec(Ctx *ctx, bool lazy_ok) {
-    void *buf = ctx->d_rec;
-    if (int rc = ensure_records(ctx, &buf, &ctx->rec_bytes)) return rc;
-    ctx->d_rec = (uint16_t *)buf;
+    if (int rc = ensure_records(ctx, ctx->pool_rec)) return rc;
+    if (ctx->form == Form::Records || (ctx->form == Form::Lazy && lazy_ok)) return ARVX_OK;
     arvx::CarveParams g;
-    if (ctx->rec_valid) {
-        if (ctx->lazy && !lazy_ok) {
-            carve_geometry(ctx, g);
-            g.rec = ctx->d_rec;
-            g.ccode = nullptr;
-            g.coarseCarved = (uint8_t *)ctx->pool_ccode.p;
-            g.flags = 4u;  // codes 2 and 3 are those of a fresh model: written as such
-            hipLaunchKernelGGL(arvx::carve_fill_kernel,
-                               dim3((unsigned)((size_t)g.coarseX * g.coarseY * g.coarseZ)), dim3(256),
-                               0, ctx->stream, g);
-            ARVX_HIP(hipGetLastError());
-            ctx->lazy = false;
-        }
-        return ARVX_OK;
-    }
-    ctx->lazy = false;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
-    g.flags = 4u | 16u;  // a fresh model: all occupied, none seen
+    g.rec = ctx->rec();
+    if (ctx->form == Form::Lazy) {
+        g.ccode = nullptr;
+        g.coarseCarved = (uint8_t *)ctx->pool_ccode.p;
+        g.flags = 4u;  // codes 2 and 3 are those of a fresh model: written as such
+    } else {
+        g.flags = 4u | 16u;  // a fresh model: all occupied, none seen
+    }
     hipLaunchKernelGGL(arvx::carve_fill_kernel,
                        dim3((unsigned)((size_t)g.coarseX * g.coarseY * g.coarseZ)), dim3(256), 0,
                        ctx->stream, g);
     ARVX_HIP(hipGetLastError());
-    ctx->fresh_pending = false;
-    ctx->rec_valid = true;
+    ctx->form = Form::Records;
     return ARVX_OK;
 }
 
@@ -900,36 +864,22 @@ static int fills_without_colours(Ctx *ctx) {
     return ARVX_OK;
 }
 
-// every call that changes occupied / seen bits goes through here: results derived from the
-// old state are dropped
-static void state_changes(Ctx *ctx, bool keeps_paint) {
-    ++ctx->state_seq;
-    ctx->color_ready = false;
-    ctx->closure_ready = false;
-    ctx->closure_fills = false;
-    if (!keeps_paint) ctx->paint_valid = false;
-}
-// ... and one that may occupy or un-see voxels (everything but carving, the greedy carve and
-// handleUnseen, which leave a tile that is carved and seen / seen as a whole as it is) also
-// drops what earlier carves settled for whole coarse tiles (CarveParams::cstate)
-static void state_rewritten(Ctx *ctx) { ctx->cstate_tiles = 0; }
-
 // Bytes of local planes [zl0, zl0 + nz), already in the staging buffer, into the records
 // (+ bit2 into the paint plane).  Ends with a host synchronisation.
 static int bytes_into_records(Ctx *ctx, int zl0, int nz) {
     if (int rc = need_rec(ctx)) return rc;
     arvx::CarveParams g;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
+    g.rec = ctx->rec();
     const size_t pw = (size_t)((ctx->X + 63) / 64) * ctx->Y * (size_t)(ctx->ze1 - ctx->ze0);
     const bool had = ctx->pool_paint.cap >= pw * 8 && ctx->paint_valid;
     ARVX_HIP(ctx->pool_paint.reserve(pw * 8));
     if (!had) ARVX_HIP(hipMemsetAsync(ctx->pool_paint.p, 0, pw * 8, ctx->stream));
-    int *d_any = (int *)(ctx->d_stats + 8);
+    int *d_any = (int *)(ctx->stats() + 8);
     ARVX_HIP(hipMemsetAsync(d_any, 0, sizeof(int), ctx->stream));
     hipLaunchKernelGGL(arvx::rec_from_bytes_kernel,
                        dim3((unsigned)((size_t)g.tilesX * g.tilesY * g.tilesZ)), dim3(256), 0,
-                       ctx->stream, g, (const uint8_t *)ctx->d_state, zl0, nz,
+                       ctx->stream, g, (const uint8_t *)ctx->pool_state_bytes.p, zl0, nz,
                        (unsigned long long *)ctx->pool_paint.p, d_any);
     ARVX_HIP(hipGetLastError());
     int any = 0;
@@ -942,35 +892,29 @@ static int bytes_into_records(Ctx *ctx, int zl0, int nz) {
 // the byte staging buffer holds the current state of local planes [zl0, zl0 + nz)
 static int records_into_bytes(Ctx *ctx, int zl0, int nz) {
     if (int rc = need_rec(ctx, true)) return rc;  // (rec_to_bytes_kernel reads lazy tiles)
-    if (!ctx->d_state) ARVX_HIP(hipMalloc(&ctx->d_state, ctx->nvox_ext));
+    ARVX_HIP(ctx->pool_state_bytes.reserve(ctx->nvox_ext));
     arvx::CarveParams g;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
+    g.rec = ctx->rec();
     hipLaunchKernelGGL(arvx::rec_to_bytes_kernel,
                        dim3((unsigned)((size_t)g.tilesX * g.tilesY * g.tilesZ)), dim3(256), 0,
-                       ctx->stream, g, ctx->d_state, zl0, nz, paint_plane(ctx));
+                       ctx->stream, g, (uint8_t *)ctx->pool_state_bytes.p, zl0, nz, paint_plane(ctx));
     ARVX_HIP(hipGetLastError());
     return ARVX_OK;
 }
 
 int arvx_state_reset(arvx_ctx *ctx) {
     ARVX_CHECK_CTX(ctx);
-    state_changes(ctx, false);
-    state_rewritten(ctx);
-    ctx->fresh_pending = true;  // materialised by need_rec, or never (a carve of a fresh model
-    ctx->rec_valid = false;     // writes every record)
-    ctx->lazy = false;
+    ctx->drop(Event::Reset);
+    ctx->form = Form::Fresh;  // written out by need_rec, or never (a carve of a fresh model writes every record)
     return ARVX_OK;
 }
 
 int arvx_state_upload(arvx_ctx *ctx, const uint8_t *state) {
     ARVX_CHECK_CTX(ctx);
     if (!state) return fail(ARVX_ERR_INVALID, "null state");
-    if (!ctx->d_state) ARVX_HIP(hipMalloc(&ctx->d_state, ctx->nvox_ext));
-    // paint of the owned planes is replaced; what the halo planes hold stays
-    const bool halo_paint = ctx->paint_valid && ctx->nvox_ext != ctx->nvox;
-    state_changes(ctx, halo_paint);
-    state_rewritten(ctx);
+    ctx->drop(Event::UploadState);  // (paint of the owned planes is replaced; what the halo planes hold stays)
+    ARVX_HIP(ctx->pool_state_bytes.reserve(ctx->nvox_ext));
     ARVX_HIP(hipMemcpyAsync(ctx->owned(), state, ctx->nvox, hipMemcpyHostToDevice, ctx->stream));
     return bytes_into_records(ctx, ctx->z0 - ctx->ze0, ctx->z1 - ctx->z0);
 }
@@ -979,9 +923,8 @@ int arvx_state_upload_halo(arvx_ctx *ctx, const uint8_t *plane_below, const uint
     ARVX_CHECK_CTX(ctx);
     const size_t plane = (size_t)ctx->X * ctx->Y;
     if (ctx->stripe_world > 1) return fail(ARVX_ERR_STATE, "striped slabs keep no halo planes");
-    if (!ctx->d_state) ARVX_HIP(hipMalloc(&ctx->d_state, ctx->nvox_ext));
-    state_changes(ctx, true);
-    state_rewritten(ctx);
+    ctx->drop(Event::UploadHalo);
+    ARVX_HIP(ctx->pool_state_bytes.reserve(ctx->nvox_ext));
     if (plane_below && ctx->ze0 < ctx->z0) {  // plane z0 - 1
         ARVX_HIP(hipMemcpyAsync(ctx->owned() - plane, plane_below, plane, hipMemcpyHostToDevice,
                                 ctx->stream));
@@ -1007,18 +950,17 @@ int arvx_state_download(arvx_ctx *ctx, uint8_t *state) {
 int arvx_state_upload_planes(arvx_ctx *ctx, const uint32_t *occ, const uint32_t *seen) {
     ARVX_CHECK_CTX(ctx);
     if (!occ || !seen) return fail(ARVX_ERR_INVALID, "null plane");
+    ctx->drop(Event::UploadPlanes);
     if (int mrc = need_rec(ctx)) return mrc;  // (halo planes keep what they hold)
-    state_changes(ctx, false);
-    state_rewritten(ctx);
     const int nz = ctx->z1 - ctx->z0;
     const size_t nwords = (size_t)((ctx->X + 31) / 32) * ctx->Y * nz;
-    if (int rc = ensure_scratch(ctx, 2 * nwords * sizeof(uint32_t) + 64)) return rc;
-    uint32_t *d_occ = (uint32_t *)ctx->d_scratch, *d_seen = d_occ + nwords;
+    ARVX_HIP(ctx->pool_scratch.reserve(2 * nwords * sizeof(uint32_t) + 64));
+    uint32_t *d_occ = (uint32_t *)ctx->pool_scratch.p, *d_seen = d_occ + nwords;
     ARVX_HIP(hipMemcpyAsync(d_occ, occ, nwords * 4, hipMemcpyHostToDevice, ctx->stream));
     ARVX_HIP(hipMemcpyAsync(d_seen, seen, nwords * 4, hipMemcpyHostToDevice, ctx->stream));
     arvx::CarveParams g;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
+    g.rec = ctx->rec();
     hipLaunchKernelGGL(arvx::rec_from_planes_kernel, dim3((unsigned)((nwords + 255) / 256)),
                        dim3(256), 0, ctx->stream, g, ctx->z0 - ctx->ze0, nz, d_occ, d_seen);
     ARVX_HIP(hipGetLastError());
@@ -1032,11 +974,11 @@ int arvx_state_download_planes(arvx_ctx *ctx, uint32_t *occ, uint32_t *seen) {
     if (int mrc = need_rec(ctx, true)) return mrc;  // (planes_from_rec_kernel reads lazy tiles)
     const int nz = ctx->z1 - ctx->z0;
     const size_t nwords = (size_t)((ctx->X + 31) / 32) * ctx->Y * nz;
-    if (int rc = ensure_scratch(ctx, 2 * nwords * sizeof(uint32_t) + 64)) return rc;
-    uint32_t *d_occ = (uint32_t *)ctx->d_scratch, *d_seen = d_occ + nwords;
+    ARVX_HIP(ctx->pool_scratch.reserve(2 * nwords * sizeof(uint32_t) + 64));
+    uint32_t *d_occ = (uint32_t *)ctx->pool_scratch.p, *d_seen = d_occ + nwords;
     arvx::CarveParams g;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
+    g.rec = ctx->rec();
     hipLaunchKernelGGL(arvx::planes_from_rec_kernel, dim3((unsigned)((nwords + 255) / 256)),
                        dim3(256), 0, ctx->stream, g, ctx->z0 - ctx->ze0, nz, d_occ, d_seen);
     ARVX_HIP(hipGetLastError());
@@ -1070,20 +1012,20 @@ int arvx_state_download_packets(arvx_ctx *ctx, uint64_t *occ_packet, int64_t occ
     // the two packets at their worst-case size stay on the device until the state changes: a caller
     // whose buffers were too small asks again and only the copies run
     const size_t S = (size_t)(H + n);
-    if (!(ctx->packets_seq == ctx->state_seq && ctx->packets_valid && ctx->pool_state_packets.cap >= 2 * S * 8)) {
+    if (!(ctx->packets_seq == ctx->state_seq && ctx->pool_state_packets.cap >= 2 * S * 8)) {
         if (int mrc = need_rec(ctx, true)) return mrc;
         ARVX_HIP(ctx->pool_state_packets.reserve(2 * S * 8));
         arvx::CarveParams g;
         carve_geometry(ctx, g);
-        g.rec = ctx->d_rec;
+        g.rec = ctx->rec();
         const int zl0 = ctx->z0 - ctx->ze0;
         const int nwg = (int)((nb + arvx::kOccGroupsPerWg - 1) / arvx::kOccGroupsPerWg);
         arvx::OccGeom og;
         og.wpr = arvx::fast_div((unsigned)(ctx->X / 32));
         og.Y = arvx::fast_div((unsigned)ctx->Y);
         og.P64 = arvx::fast_div((unsigned)((size_t)ctx->X * ctx->Y / 64));
-        if (int rc = ensure_scratch(ctx, 2 * (size_t)nwg * sizeof(int) + 64)) return rc;
-        int *d_wgsum = (int *)ctx->d_scratch;
+        ARVX_HIP(ctx->pool_scratch.reserve(2 * (size_t)nwg * sizeof(int) + 64));
+        int *d_wgsum = (int *)ctx->pool_scratch.p;
         unsigned long long *pk = (unsigned long long *)ctx->pool_state_packets.p;
         hipLaunchKernelGGL(arvx::occ_pack_classify_kernel<false>, dim3(nwg), dim3(256), 0, ctx->stream, g, og,
                            zl0, n, pk, d_wgsum, (unsigned long long *)nullptr);
@@ -1101,7 +1043,6 @@ int arvx_state_download_packets(arvx_ctx *ctx, uint64_t *occ_packet, int64_t occ
         ctx->packet_need[0] = ctx->h_totals[4];
         ctx->packet_need[1] = ctx->h_totals[5];
         ctx->packets_seq = ctx->state_seq;
-        ctx->packets_valid = true;
     }
     const unsigned long long *pk = (const unsigned long long *)ctx->pool_state_packets.p;
     *occ_need = ctx->packet_need[0];
@@ -1120,18 +1061,14 @@ int arvx_handle_unseen(arvx_ctx *ctx) {
     // seen" and "untouched, not seen" are all unchanged by occ |= ~seen -- the records behind a
     // code are not read by anybody)
     if (int mrc = need_rec(ctx, true)) return mrc;
-    if (ctx->planes_ok && ctx->planes_seq == ctx->state_seq) {
-        // the colour pass's planes stay usable: occupied is now their occupancy | never-seen
-        ctx->planes_seq = ctx->state_seq + 1;
-        ctx->planes_unseen = true;
-    }
-    ++ctx->state_seq;
-    ctx->closure_ready = false;  // (colours and paint stay: only never-seen voxels change)
+    // (after need_rec, which may fail: the drop hands the colour pass's planes on to the state this
+    // call makes)
+    ctx->drop(Event::HandleUnseen);
     arvx::CarveParams g;
     carve_geometry(ctx, g);
     const size_t nrec = arvx::rec_count(g);
     hipLaunchKernelGGL(arvx::rec_handle_unseen_kernel, dim3((unsigned)((nrec * 32 + 255) / 256)),
-                       dim3(256), 0, ctx->stream, (uint32_t *)ctx->d_rec, nrec, g.ccode,
+                       dim3(256), 0, ctx->stream, (uint32_t *)ctx->rec(), nrec, g.ccode,
                        g.cyShift + g.czShift + 2);
     ARVX_HIP(hipGetLastError());
     return ARVX_OK;
@@ -1163,7 +1100,7 @@ static int launch_pack_tiles(Ctx *ctx, int global, void *dev_words) {
     if (int mrc = need_rec(ctx, true)) return mrc;
     arvx::CarveParams g;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
+    g.rec = ctx->rec();
     const int zl0 = ctx->z0 - ctx->ze0, nz = ctx->z1 - ctx->z0;
     const int ntz = ((zl0 + nz - 1) >> 3) - (zl0 >> 3) + 1;
     const size_t tiles = (size_t)g.tilesX * g.tilesY * ntz;
@@ -1183,7 +1120,7 @@ int arvx_pack_occupancy(arvx_ctx *ctx, void *dev_words) {
         if (int mrc = need_rec(ctx, true)) return mrc;
         arvx::CarveParams g;
         carve_geometry(ctx, g);
-        g.rec = ctx->d_rec;
+        g.rec = ctx->rec();
         const int nz = ctx->z1 - ctx->z0;
         const size_t nwords = (size_t)(ctx->X / 32) * ctx->Y * nz;
         hipLaunchKernelGGL(arvx::pack_occupancy_rec_kernel, dim3((unsigned)((nwords + 255) / 256)),
@@ -1196,7 +1133,7 @@ int arvx_pack_occupancy(arvx_ctx *ctx, void *dev_words) {
         if (int mrc = need_rec(ctx, true)) return mrc;
         arvx::CarveParams g;
         carve_geometry(ctx, g);
-        g.rec = ctx->d_rec;
+        g.rec = ctx->rec();
         const int nz = ctx->z1 - ctx->z0;
         const size_t nwords = ((size_t)ctx->X * ctx->Y * nz / 8 + 3) / 4;
         hipLaunchKernelGGL(arvx::pack_occupancy_rec8_kernel, dim3((unsigned)((nwords + 255) / 256)),
@@ -1237,7 +1174,7 @@ int arvx_pack_occupancy_global(arvx_ctx *ctx, void *dev_global_words) {
         if (int mrc = need_rec(ctx, true)) return mrc;
         arvx::CarveParams g;
         carve_geometry(ctx, g);
-        g.rec = ctx->d_rec;
+        g.rec = ctx->rec();
         const int nz = ctx->z1 - ctx->z0;
         const size_t nwords = (size_t)(ctx->X / 32) * ctx->Y * nz;
         hipLaunchKernelGGL(arvx::pack_occupancy_rec_kernel, dim3((unsigned)((nwords + 255) / 256)),
@@ -1250,7 +1187,7 @@ int arvx_pack_occupancy_global(arvx_ctx *ctx, void *dev_global_words) {
         if (int mrc = need_rec(ctx, true)) return mrc;
         arvx::CarveParams g;
         carve_geometry(ctx, g);
-        g.rec = ctx->d_rec;
+        g.rec = ctx->rec();
         const int nz = ctx->z1 - ctx->z0;
         const size_t nwords = (size_t)ctx->X * ctx->Y * nz / 32;
         hipLaunchKernelGGL(arvx::pack_occupancy_rec8_kernel, dim3((unsigned)((nwords + 255) / 256)),
@@ -1319,7 +1256,7 @@ int arvx_occupancy_pack_compress(arvx_ctx *ctx, void *dev_packet, int64_t cap_wo
     if (int mrc = need_rec(ctx, true)) return mrc;
     arvx::CarveParams g;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
+    g.rec = ctx->rec();
     const int zl0 = ctx->z0 - ctx->ze0, nz = ctx->z1 - ctx->z0;
     const long long n = (long long)(plane / 64) * nz, nb = (n + 63) / 64;
     if (2 * n >= (1ll << 32)) return fail(ARVX_ERR_INVALID, "slab too large for the fused packet (%lld words)", n);
@@ -1395,6 +1332,19 @@ int arvx_occupancy_expand_striped_others(arvx_ctx *ctx, const void *dev_packets,
 
 // ---- carve -------------------------------------------------------------------
 
+#ifdef ARVX_TIMELINE
+// the diagnostic timeline of the launch that follows: n records of `rec` bytes, zeroed
+static int timeline(Ctx *ctx, size_t n, int rec, arvx::CarveParams &p) {
+    ctx->pool_timeline.release();
+    ctx->timeline_n = (int64_t)n;
+    ctx->timeline_rec = rec;
+    ARVX_HIP(ctx->pool_timeline.reserve(n * rec));
+    ARVX_HIP(hipMemsetAsync(ctx->pool_timeline.p, 0, n * rec, ctx->stream));
+    p.timeline = (unsigned long long *)ctx->pool_timeline.p;
+    return ARVX_OK;
+}
+#endif
+
 // Launches the carve over planes [ze0, ze1) (owned + halo) of the records at `rec`.
 #ifdef ARVX_EXPERIMENTS
 // A fresh model carved by ONE persistent launch (carve_stream_kernels.h).  p: geometry, views and
@@ -1420,29 +1370,25 @@ static int launch_carve_stream(Ctx *ctx, arvx::CarveParams p, int ncu) {
     const size_t off_items =
         off_list + ((size_t)arvx::kStreamLists * p.listCap * p.listStride * 8 + 255) / 256 * 256;
     const size_t need = off_items + (size_t)arvx::kWorkLists * p.workCap * p.itemStride * 8 + 256;
-    if (ctx->stream_bytes < need) {
-        if (ctx->d_stream) (void)hipFree(ctx->d_stream);
-        ctx->d_stream = nullptr;
-        ctx->stream_bytes = 0;
+    if (ctx->pool_stream.cap < need) {
         ctx->stream_layout = 0;
-        ARVX_HIP(hipMalloc(&ctx->d_stream, need));
-        ctx->stream_bytes = need;
+        ARVX_HIP(ctx->pool_stream.reserve(need));
         // (stale granules are told by their tag; but the memory must not hold a FUTURE tag)
-        ARVX_HIP(hipMemsetAsync(ctx->d_stream, 0, need, ctx->stream));
+        ARVX_HIP(hipMemsetAsync(ctx->pool_stream.p, 0, need, ctx->stream));
         ctx->carve_epoch = 0;
     }
     if (ctx->stream_layout != need) {  // the control block: all zero before a launch
-        ARVX_HIP(hipMemsetAsync(ctx->d_stream, 0, off_list, ctx->stream));
+        ARVX_HIP(hipMemsetAsync(ctx->pool_stream.p, 0, off_list, ctx->stream));
         ctx->stream_layout = need;
     }
     if (++ctx->carve_epoch == 0u) {  // (2^32 launches: start the tags over on clean memory)
-        ARVX_HIP(hipMemsetAsync(ctx->d_stream, 0, need, ctx->stream));
+        ARVX_HIP(hipMemsetAsync(ctx->pool_stream.p, 0, need, ctx->stream));
         ctx->carve_epoch = 1u;
     }
-    p.sctl = (int *)ctx->d_stream;
+    p.sctl = (int *)ctx->pool_stream.p;
     p.poolNext = p.sctl + (size_t)arvx::kSC_Pool * arvx::kCounterStride;
-    p.listG = (unsigned long long *)((uint8_t *)ctx->d_stream + off_list);
-    p.itemG = (unsigned long long *)((uint8_t *)ctx->d_stream + off_items);
+    p.listG = (unsigned long long *)((uint8_t *)ctx->pool_stream.p + off_list);
+    p.itemG = (unsigned long long *)((uint8_t *)ctx->pool_stream.p + off_items);
     p.epoch = ctx->carve_epoch;
     p.fault = ctx->d_fault;
     p.nwaves = (int)G * 4;
@@ -1453,13 +1399,7 @@ static int launch_carve_stream(Ctx *ctx, arvx::CarveParams p, int ncu) {
     p.flags |= 128u;
     ctx->cstate_tiles = 0;
 #ifdef ARVX_TIMELINE
-    if (ctx->d_timeline) (void)hipFree(ctx->d_timeline);
-    ctx->d_timeline = nullptr;
-    ctx->timeline_n = (int64_t)G * 4;  // one record per wave
-    ctx->timeline_rec = 128;
-    ARVX_HIP(hipMalloc(&ctx->d_timeline, (size_t)G * 4 * 128));
-    ARVX_HIP(hipMemsetAsync(ctx->d_timeline, 0, (size_t)G * 4 * 128, ctx->stream));
-    p.timeline = (unsigned long long *)ctx->d_timeline;
+    if (int rc = timeline(ctx, (size_t)G * 4, 128, p)) return rc;  // one record per wave
 #endif
     // (the chunks of 64 views are a template parameter: up to 64 views, or up to 256)
     const bool left = ctx->assoc == ARVX_ASSOC_LEFT, one = p.nchunks == 1;
@@ -1472,7 +1412,7 @@ static int launch_carve_stream(Ctx *ctx, arvx::CarveParams p, int ncu) {
     else
         hipLaunchKernelGGL((arvx::carve_stream_kernel<false, arvx::kMaxChunks>), dim3(G), dim3(256), 0, ctx->stream, p);
     ARVX_HIP(hipGetLastError());
-    ctx->lazy = true;
+    ctx->form = Form::Lazy;
     ctx->cstate_tiles = ncoarse;
     return ARVX_OK;
 }
@@ -1488,10 +1428,10 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     arvx::CarveParams p;
     carve_geometry(ctx, p);
     p.rec = rec;
-    p.M = ctx->d_M;
-    p.bg = ctx->d_bg;
-    p.sat = ctx->d_sat;
-    p.stats = ctx->d_stats;
+    p.M = ctx->M();
+    p.bg = ctx->bg();
+    p.sat = ctx->sat();
+    p.stats = ctx->stats();
     p.W = ctx->W;
     p.H = ctx->H;
     p.bgWords = ctx->bgWords;
@@ -1503,7 +1443,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     p.ccode = nullptr;  // (the carve reads records only where it has written them)
     p.cstate = nullptr;
     p.nchunks = (count + 63) / 64;
-    if (flags & ARVX_CARVE_STATS) ARVX_HIP(hipMemsetAsync(ctx->d_stats, 0, 64, ctx->stream));
+    if (flags & ARVX_CARVE_STATS) ARVX_HIP(hipMemsetAsync(ctx->stats(), 0, 64, ctx->stream));
     // rows of tiles (along x) are dealt to the XCDs cyclically: see carve_fused_kernel
     const size_t rows8 = ((size_t)p.tilesY * p.tilesZ + 7) / 8 * 8;
     const unsigned grid = (unsigned)(rows8 * p.tilesX);
@@ -1519,14 +1459,13 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     const int ncu = ctx->ncu;
     size_t layout_when_done = 0;
     bool lazy = false;
-    if (rec == ctx->d_rec) ctx->lazy = false;  // (set again below once the launches are out)
     // a fresh model, the context's own records, up to 256 views: one persistent launch where the
     // caller asks for it (carve_stream_kernels.h; EXPERIMENTS.md, round 4: its sub-tile phase is
     // slower inside a launch of 128-register waves than as a launch of its own, so the three
     // launches below stay the default)
 #ifdef ARVX_EXPERIMENTS
     static const bool stream_default = experiment_flag("ARVX_STREAM_DEFAULT");
-    if (fresh && split && rec == ctx->d_rec && !(flags & (ARVX_CARVE_STATS | ARVX_CARVE_NO_STREAM)) &&
+    if (fresh && split && rec == ctx->rec() && !(flags & (ARVX_CARVE_STATS | ARVX_CARVE_NO_STREAM)) &&
         ((flags & ARVX_CARVE_STREAM) || (stream_default && (size_t)p.X * p.Y * p.Z >= ((size_t)1 << 26))) &&
         arvx::rec_count(p) < ((size_t)1 << 30) && p.tilesX < 65536 && p.tilesY < 65536 && p.tilesZ < 65536)
         return launch_carve_stream(ctx, p, ncu);
@@ -1553,14 +1492,8 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         const size_t off_items = off_work + (ints * sizeof(int) + 255) / 256 * 256;
         const size_t need =
             off_items + nitems * (1 + 2 * (size_t)p.nchunks) * sizeof(unsigned long long) + 64;
-        if (ctx->coarse_bytes < need) {
-            if (ctx->d_coarse) (void)hipFree(ctx->d_coarse);
-            ctx->d_coarse = nullptr;
-            ctx->coarse_bytes = 0;
-            ARVX_HIP(hipMalloc(&ctx->d_coarse, need));
-            ctx->coarse_bytes = need;
-        }
-        p.coarseMixed = (unsigned long long *)ctx->d_coarse;
+        ARVX_HIP(ctx->pool_coarse.reserve(need));
+        p.coarseMixed = (unsigned long long *)ctx->pool_coarse.p;
         p.coarseFg = p.coarseMixed + words;
         p.coarseCarved = (uint8_t *)(p.coarseFg + words);
         // Lazy state: a fresh model carved by the split launch into the context's own records
@@ -1568,9 +1501,9 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         // context, is their state (arvx_device.h; need_rec writes them out for the stages that
         // want records).
 #ifndef ARVX_NO_LAZY  // (A/B builds: always write the decided tiles)
-        lazy = fresh && split && (rec == ctx->d_rec || foreign_code);
+        lazy = fresh && split && (rec == ctx->rec() || foreign_code);
 #endif
-        if (lazy && rec == ctx->d_rec) {
+        if (lazy && rec == ctx->rec()) {
             ARVX_HIP(ctx->pool_ccode.reserve(ncoarse + 64));
             p.coarseCarved = (uint8_t *)ctx->pool_ccode.p;
             p.flags |= 128u;
@@ -1580,7 +1513,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         }
         // the model's own records: what this and earlier carves settle for whole coarse tiles
         // is remembered (CarveParams::cstate); a fresh carve rewrites every entry
-        if (split && rec == ctx->d_rec) {
+        if (split && rec == ctx->rec()) {
             ARVX_HIP(ctx->pool_cstate.reserve(ncoarse + 64));
             if (!fresh && ctx->cstate_tiles != ncoarse)
                 ARVX_HIP(hipMemsetAsync(ctx->pool_cstate.p, 0, ncoarse, ctx->stream));
@@ -1588,7 +1521,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
             ctx->cstate_tiles = 0;  // (valid again once the launches are out)
         }
         if (split) {
-            int *lst = (int *)((uint8_t *)ctx->d_coarse + off_list);
+            int *lst = (int *)((uint8_t *)ctx->pool_coarse.p + off_list);
             // two counters, 64 ints apart, used alternately (carve_coarse_kernel): both zero
             // before the first carve that uses this layout
             if (ctx->carve_layout != need) {
@@ -1603,12 +1536,12 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
             // between leaves the layout unset, so that the next carve zeroes both counters)
             ctx->carve_layout = 0;
             layout_when_done = need;
-            int *base = (int *)((uint8_t *)ctx->d_coarse + off_work);
+            int *base = (int *)((uint8_t *)ctx->pool_coarse.p + off_work);
             p.workCount = base;
             p.poolNext = base + nctr;
             p.nwaves = (int)nwaves;
             p.workCap = (int)cap;
-            p.itemInfo = (unsigned long long *)((uint8_t *)ctx->d_coarse + off_items);
+            p.itemInfo = (unsigned long long *)((uint8_t *)ctx->pool_coarse.p + off_items);
             p.itemMasks = p.itemInfo + nitems;
             // (carve_coarse_kernel zeroes the `ints` counters at base)
         }
@@ -1682,13 +1615,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         ARVX_HIP(hipGetLastError());
         const unsigned pgrid = (unsigned)(p.nwaves / 4);
 #ifdef ARVX_TIMELINE
-        if (ctx->d_timeline) (void)hipFree(ctx->d_timeline);
-        ctx->d_timeline = nullptr;
-        ctx->timeline_n = (int64_t)pgrid * 4;  // one record per WAVE of the persistent kernel
-        ctx->timeline_rec = 64;
-        ARVX_HIP(hipMalloc(&ctx->d_timeline, (size_t)pgrid * 4 * 64));
-        ARVX_HIP(hipMemsetAsync(ctx->d_timeline, 0, (size_t)pgrid * 4 * 64, ctx->stream));
-        p.timeline = (unsigned long long *)ctx->d_timeline;
+        if (int rc = timeline(ctx, (size_t)pgrid * 4, 64, p)) return rc;  // one record per WAVE of the persistent kernel
 #endif
         const bool left = ctx->assoc == ARVX_ASSOC_LEFT;
         const bool may_split = p.flags & 8u;
@@ -1743,18 +1670,12 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         ARVX_HIP(hipGetLastError());
         ctx->carve_layout = layout_when_done;
         ++ctx->carve_seq;
-        if (lazy && rec == ctx->d_rec) ctx->lazy = true;
+        if (lazy && rec == ctx->rec()) ctx->form = Form::Lazy;
         if (p.cstate) ctx->cstate_tiles = ncoarse;
         return ARVX_OK;
     }
 #ifdef ARVX_TIMELINE
-    if (ctx->d_timeline) (void)hipFree(ctx->d_timeline);
-    ctx->d_timeline = nullptr;
-    ctx->timeline_n = grid;
-    ctx->timeline_rec = 32;
-    ARVX_HIP(hipMalloc(&ctx->d_timeline, (size_t)grid * 32));
-    ARVX_HIP(hipMemsetAsync(ctx->d_timeline, 0, (size_t)grid * 32, ctx->stream));
-    p.timeline = (unsigned long long *)ctx->d_timeline;
+    if (int rc = timeline(ctx, grid, 32, p)) return rc;
 #endif
     if (ctx->assoc == ARVX_ASSOC_LEFT)
         hipLaunchKernelGGL(arvx::carve_fused_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, p);
@@ -1779,18 +1700,15 @@ int arvx_carve_views(arvx_ctx *ctx, int first, int count, unsigned flags) {
         return fail(ARVX_ERR_INVALID, "ARVX_CARVE_FILTER: the fp32 projection filter is only in "
                                       "-DARVX_EXPERIMENTS builds (libarvx_experiments.so)");
 #endif
-    state_changes(ctx, false);
-    const bool fresh = ctx->fresh_pending;
+    ctx->drop(Event::Carve);
+    const bool fresh = ctx->form == Form::Fresh;
     if (fresh) {  // the kernels write every record of the grid; nothing is read
-        void *buf = ctx->d_rec;
-        if (int rc = ensure_records(ctx, &buf, &ctx->rec_bytes)) return rc;
-        ctx->d_rec = (uint16_t *)buf;
+        if (int rc = ensure_records(ctx, ctx->pool_rec)) return rc;
     } else if (int rc = need_rec(ctx)) {
         return rc;
     }
-    ctx->fresh_pending = false;
-    ctx->rec_valid = true;
-    return launch_carve(ctx, ctx->d_rec, first, count, flags, fresh);
+    ctx->form = Form::Records;  // (Lazy once the launches are out, where the carve leaves codes)
+    return launch_carve(ctx, ctx->rec(), first, count, flags, fresh);
 }
 
 int arvx_carve(arvx_ctx *ctx, unsigned flags) {
@@ -1809,7 +1727,7 @@ int arvx_get_stats(arvx_ctx *ctx, arvx_stats *out) {
     ARVX_CHECK_CTX(ctx);
     if (!out) return fail(ARVX_ERR_INVALID, "null out");
     unsigned long long h[8];
-    ARVX_HIP(hipMemcpyAsync(h, ctx->d_stats, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_HIP(hipMemcpyAsync(h, ctx->stats(), sizeof h, hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);
     memset(out, 0, sizeof *out);
     out->subtiles = h[0];
@@ -1867,21 +1785,20 @@ int arvx_set_images(arvx_ctx *ctx, const uint8_t *const *images, size_t stride) 
     for (int i = 0; i < ctx->V; ++i)
         if (!images[i]) return fail(ARVX_ERR_INVALID, "null image %d", i);
     const size_t img = rowb * ctx->H;
-    if (!ctx->d_images) ARVX_HIP(hipMalloc(&ctx->d_images, img * ctx->V));
+    ctx->drop(Event::SetImages);
+    ARVX_HIP(ctx->pool_images.reserve(img * ctx->V));
     bool packed = stride == rowb;
     for (int i = 1; i < ctx->V && packed; ++i) packed = images[i] == images[i - 1] + img;
     if (packed) {
-        ARVX_HIP(hipMemcpyAsync(ctx->d_images, images[0], img * ctx->V, hipMemcpyHostToDevice,
+        ARVX_HIP(hipMemcpyAsync(ctx->images(), images[0], img * ctx->V, hipMemcpyHostToDevice,
                                 ctx->stream));
     } else {
         for (int i = 0; i < ctx->V; ++i)
-            ARVX_HIP(hipMemcpy2DAsync(ctx->d_images + img * i, rowb, images[i], stride, rowb,
+            ARVX_HIP(hipMemcpy2DAsync(ctx->images() + img * i, rowb, images[i], stride, rowb,
                                       ctx->H, hipMemcpyHostToDevice, ctx->stream));
     }
     ARVX_SYNC(ctx);
     ctx->images_ready = true;
-    ctx->color_ready = false;
-    ctx->closure_ready = false;
     return ARVX_OK;
 }
 
@@ -1894,7 +1811,7 @@ int arvx_color(arvx_ctx *ctx, int mode) {
         return fail(ARVX_ERR_INVALID, "colour mode %d", mode);
     if (ctx->stripe_world > 1)
         return fail(ARVX_ERR_STATE, "the colour pass needs contiguous slabs (neighbour planes)");
-    ctx->free_surface();
+    ctx->drop(Event::Color);
     // surface = occupied and not inner, on bit planes over the context's planes; colours are
     // voted for the planes [c_lo, c_hi) (stage_ranges): the owned ones and the halo planes
     // whose own neighbours the records hold
@@ -1915,10 +1832,9 @@ int arvx_color(arvx_ctx *ctx, int mode) {
     ARVX_HIP(ctx->pool_state_planes.reserve(2 * nw_ext * sizeof(unsigned long long)));  // (one allocation)
     unsigned long long *d_occ = (unsigned long long *)ctx->pool_state_planes.p;
     unsigned long long *d_surf = (unsigned long long *)ctx->pool_col_bits.p;
-    ctx->planes_ok = false;
+    ctx->planes_seq = 0;
     if (int rc = launch_bit_pack(ctx, gext, 0, 1, d_occ, d_occ + nw_ext)) return rc;
     ctx->planes_words = nw_ext;
-    ctx->planes_ok = true;
     ctx->planes_seq = ctx->state_seq;
     ctx->planes_unseen = false;
     // the surface plane of the planes [c_lo, c_hi) (zeros elsewhere) and, per chunk of the
@@ -1962,9 +1878,9 @@ int arvx_color(arvx_ctx *ctx, int mode) {
         vp.V = ctx->V;
         vp.W = ctx->W;
         vp.H = ctx->H;
-        vp.M = ctx->d_M;
-        vp.campos = ctx->d_campos;
-        vp.images = ctx->d_images;
+        vp.M = ctx->M();
+        vp.campos = ctx->campos();
+        vp.images = ctx->images();
         vp.mode = mode;
         vp.rgba = ctx->d_surf_rgba;
         vp.depth = ctx->d_surf_depth;
@@ -2013,8 +1929,8 @@ int arvx_color_samples(arvx_ctx *ctx, int64_t n, const int64_t *index, int views
             return fail(ARVX_ERR_INVALID, "voxel index %lld outside [0,%lld)", (long long)index[k],
                         (long long)nown);
     const size_t total = (size_t)n * ctx->V;
-    if (int rc = ensure_scratch(ctx, (size_t)n * sizeof(long long) + total * sizeof(uint2) + 64)) return rc;
-    uint2 *d_out = (uint2 *)ctx->d_scratch;
+    ARVX_HIP(ctx->pool_scratch.reserve((size_t)n * sizeof(long long) + total * sizeof(uint2) + 64));
+    uint2 *d_out = (uint2 *)ctx->pool_scratch.p;
     long long *d_idx = (long long *)(d_out + total);
     ARVX_HIP(hipMemcpyAsync(d_idx, index, (size_t)n * sizeof(long long), hipMemcpyHostToDevice,
                             ctx->stream));
@@ -2027,9 +1943,9 @@ int arvx_color_samples(arvx_ctx *ctx, int64_t n, const int64_t *index, int views
     vp.V = ctx->V;
     vp.W = ctx->W;
     vp.H = ctx->H;
-    vp.M = ctx->d_M;
-    vp.campos = ctx->d_campos;
-    vp.images = ctx->d_images;
+    vp.M = ctx->M();
+    vp.campos = ctx->campos();
+    vp.images = ctx->images();
     const unsigned grid = (unsigned)((total + 255) / 256);
     if (ctx->assoc == ARVX_ASSOC_LEFT)
         hipLaunchKernelGGL(arvx::color_samples_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, vp,
@@ -2136,7 +2052,7 @@ int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen) {
     if (!rgba) return fail(ARVX_ERR_INVALID, "null rgba");
     arvx::CarveParams g;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
+    g.rec = ctx->rec();
     const int zown = ctx->z0 - ctx->ze0;
     if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
         return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d",
@@ -2253,10 +2169,10 @@ int arvx_selftest_view_tables(arvx_ctx *ctx, int view, uint32_t *bg_bits, uint16
     *ld = ctx->satW;
     const size_t words = ((size_t)ctx->W * ctx->H + 31) / 32;
     if (bg_bits)
-        ARVX_HIP(hipMemcpyAsync(bg_bits, ctx->d_bg + (size_t)view * ctx->bgWords, words * sizeof(uint32_t),
+        ARVX_HIP(hipMemcpyAsync(bg_bits, ctx->bg() + (size_t)view * ctx->bgWords, words * sizeof(uint32_t),
                                 hipMemcpyDeviceToHost, ctx->stream));
     if (table)
-        ARVX_HIP(hipMemcpyAsync(table, ctx->d_sat + (size_t)view * ctx->satStride,
+        ARVX_HIP(hipMemcpyAsync(table, ctx->sat() + (size_t)view * ctx->satStride,
                                 (size_t)ctx->satStride * sizeof(uint16_t), hipMemcpyDeviceToHost,
                                 ctx->stream));
     ARVX_SYNC(ctx);
@@ -2267,8 +2183,8 @@ int arvx_selftest_round(arvx_ctx *ctx, int64_t *mismatches) {
     ARVX_CHECK_CTX(ctx);
     if (!mismatches) return fail(ARVX_ERR_INVALID, "null mismatches");
     *mismatches = -1;
-    if (int rc = ensure_scratch(ctx, 64)) return rc;
-    unsigned long long *d_bad = (unsigned long long *)ctx->d_scratch;
+    ARVX_HIP(ctx->pool_scratch.reserve(64));
+    unsigned long long *d_bad = (unsigned long long *)ctx->pool_scratch.p;
     ARVX_HIP(hipMemsetAsync(d_bad, 0, sizeof *d_bad, ctx->stream));
     // every float in [+0, 2^24] and in (-0.5, -0]: all quotients that can be inside an image
     const unsigned ranges[2][2] = {{0x00000000u, 0x4B800000u}, {0x80000000u, 0xBEFFFFFFu}};
@@ -2290,9 +2206,9 @@ int arvx_selftest_round(arvx_ctx *ctx, int64_t *mismatches) {
 extern "C" int arvx_debug_timeline(arvx_ctx *ctx, unsigned long long *out, int64_t *n) {
     ARVX_CHECK_CTX(ctx);
     *n = ctx->timeline_n;
-    if (out && ctx->d_timeline) {
+    if (out && ctx->pool_timeline.p) {
         ARVX_SYNC(ctx);
-        ARVX_HIP(hipMemcpy(out, ctx->d_timeline, (size_t)ctx->timeline_n * ctx->timeline_rec,
+        ARVX_HIP(hipMemcpy(out, ctx->pool_timeline.p, (size_t)ctx->timeline_n * ctx->timeline_rec,
                            hipMemcpyDeviceToHost));
     }
     return ARVX_OK;
@@ -2304,7 +2220,7 @@ extern "C" int arvx_debug_timeline(arvx_ctx *ctx, unsigned long long *out, int64
 int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const float *rgb) {
     ARVX_CHECK_CTX(ctx);
     if (n < 0 || (n > 0 && (!index || !rgb))) return fail(ARVX_ERR_INVALID, "bad colour list");
-    ctx->free_surface();
+    ctx->drop(Event::UploadColors);  // (before the indices are checked: a refused list drops the old one too)
     std::vector<int> idx((size_t)n);
     const long long own_base = (long long)ctx->X * ctx->Y * (ctx->z0 - ctx->ze0);
     for (int64_t k = 0; k < n; ++k) {
@@ -2328,11 +2244,11 @@ int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const flo
         ARVX_HIP(hipMemcpyAsync(ctx->d_surf_index, idx.data(), (size_t)n * sizeof(int),
                                 hipMemcpyHostToDevice, ctx->stream));
         // three floats per voxel from the host, (r, g, b, has = 1) on the device
-        if (int rc = ensure_scratch(ctx, (size_t)n * 3 * sizeof(float) + 64)) return rc;
-        ARVX_HIP(hipMemcpyAsync(ctx->d_scratch, rgb, (size_t)n * 3 * sizeof(float),
+        ARVX_HIP(ctx->pool_scratch.reserve((size_t)n * 3 * sizeof(float) + 64));
+        ARVX_HIP(hipMemcpyAsync(ctx->pool_scratch.p, rgb, (size_t)n * 3 * sizeof(float),
                                 hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(arvx::rgb_to_rgba_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           ctx->stream, (const float *)ctx->d_scratch, (long long)n,
+                           ctx->stream, (const float *)ctx->pool_scratch.p, (long long)n,
                            ctx->d_surf_rgba);
         ARVX_HIP(hipGetLastError());
         ARVX_SYNC(ctx);  // (the scratch buffer is reused below)
@@ -2345,11 +2261,10 @@ int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const flo
         const int nblk = (int)((nw + arvx::kBitBlock - 1) / arvx::kBitBlock);
         ARVX_HIP(ctx->pool_col_bits.reserve(nw * sizeof(unsigned long long)));
         ARVX_HIP(ctx->pool_col_rank.reserve(nw * sizeof(arvx::SparseWord)));
-        if (int rc = ensure_scratch(ctx, (size_t)(nblk + 1) * sizeof(long long) +
-                                             (size_t)nblk * sizeof(int) + 64))
-            return rc;
+        ARVX_HIP(ctx->pool_scratch.reserve((size_t)(nblk + 1) * sizeof(long long) +
+                                           (size_t)nblk * sizeof(int) + 64));
         unsigned long long *bits = (unsigned long long *)ctx->pool_col_bits.p;
-        long long *d_off = (long long *)ctx->d_scratch;
+        long long *d_off = (long long *)ctx->pool_scratch.p;
         int *d_cnt = (int *)(d_off + nblk + 1);
         ARVX_HIP(hipMemsetAsync(bits, 0, nw * sizeof(unsigned long long), ctx->stream));
         hipLaunchKernelGGL(arvx::bits_from_index_kernel, dim3((unsigned)((n + 255) / 256)),
@@ -2397,7 +2312,6 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     // further down, just before rec_or_bitgrid_kernel needs every record to exist -- written out
     // first, their non-temporal stores had emptied the caches of the records the planes are built from)
     if (int mrc = need_rec(ctx, true)) return mrc;
-    ctx->free_closure();
     // filled = dilate(occupied, box of radius r) and not occupied, on bit planes over the
     // context's planes
     const int XW = (ctx->X + 63) / 64;
@@ -2406,14 +2320,14 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     const size_t row_words = (size_t)XW * g.Y;
     const size_t nwords = row_words * g.Z;
     const bool paints = apply_unseen || ctx->paint_valid;  // somebody is UNSEEN_COLOR
-    if (int rc = ensure_scratch(ctx, 3 * nwords * sizeof(unsigned long long) + 64)) return rc;
+    ARVX_HIP(ctx->pool_scratch.reserve(3 * nwords * sizeof(unsigned long long) + 64));
     ARVX_HIP(ctx->pool_clo_bits.reserve(nwords * sizeof(unsigned long long)));
     ARVX_HIP(ctx->pool_clo_rank.reserve(nwords * sizeof(arvx::SparseWord)));
-    unsigned long long *d_occ = (unsigned long long *)ctx->d_scratch;
+    unsigned long long *d_occ = (unsigned long long *)ctx->pool_scratch.p;
     unsigned long long *d_unseen = d_occ + nwords, *d_b = d_unseen + nwords;
     unsigned long long *d_fill = (unsigned long long *)ctx->pool_clo_bits.p;
     const unsigned gw = (unsigned)((nwords + 255) / 256);
-    if (ctx->planes_ok && ctx->planes_seq == ctx->state_seq && !ctx->paint_valid && ctx->planes_words == nwords &&
+    if (ctx->planes_seq == ctx->state_seq && !ctx->paint_valid && ctx->planes_words == nwords &&
         ctx->pool_state_planes.cap >= 2 * nwords * 8) {
         // the colour pass's planes are the state's (nothing but handleUnseen ran since): what the
         // closure calls occupied is their occupancy, with the never-seen voxels once those are occupied
@@ -2438,13 +2352,13 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     if (int rc = chunk_counts(ctx, nwords, &d_counts)) return rc;
     arvx::CarveParams rp;
     carve_geometry(ctx, rp);
-    rp.rec = ctx->d_rec;
+    rp.rec = ctx->rec();
     // Coarse tiles that exist only as their code: the few that receive a voxel are marked by the fill
     // plane's producer and written out by rec_or_bitgrid_lazy_kernel, the others stay codes (grids
     // whose rows and planes fill whole tiles; else every tile is written out first, as in round 4)
     // (never a second closure on the lazy state: closure_fills is refused above, and
     // rec_or_bitgrid_lazy_kernel depends on that)
-    const bool lazy_or = ctx->lazy && ctx->Y % 8 == 0 && Zext % 8 == 0;
+    const bool lazy_or = ctx->form == Form::Lazy && ctx->Y % 8 == 0 && Zext % 8 == 0;
     arvx::CoarseMark mark{lazy_or ? (uint8_t *)ctx->pool_ccode.p : nullptr, rp.coarseX, rp.coarseY, rp.cyShift,
                           rp.czShift};
     hipLaunchKernelGGL(arvx::bit_dilate_z_count_kernel, dim3(gw), dim3(256), 0, ctx->stream, d_b, g,
@@ -2457,8 +2371,7 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     // happens to the rest of the call.
     if (!lazy_or)
         if (int mrc = need_rec(ctx)) return mrc;  // every record exists from here on
-    ++ctx->state_seq;
-    state_rewritten(ctx);  // (voxels of tiles an earlier carve emptied may be occupied again)
+    ctx->drop(Event::Closure);  // (the state changes here: tiles an earlier carve emptied may be occupied again)
     ctx->closure_fills = true;
     if (lazy_or)
         hipLaunchKernelGGL(arvx::rec_or_bitgrid_lazy_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, g.Z,
@@ -2586,16 +2499,15 @@ static int mc_cells_launch(Ctx *ctx, long long cap, const long long **d_total) {
     mp.ZW = (mp.cz1 - mp.cz0 + 1 + 63) / 64;
     const size_t nzw = (size_t)mp.ZW * ctx->X * ctx->Y;  // z-packed occupancy words
     const long long ncol = (long long)(ctx->X + 1) * (ctx->Y + 1);
-    if (int rc = ensure_scratch(ctx, nzw * sizeof(unsigned long long) +
-                                         2 * (size_t)(ncol + 1) * sizeof(int) + 64))
-        return rc;
-    mp.zbits = (unsigned long long *)ctx->d_scratch;
+    ARVX_HIP(ctx->pool_scratch.reserve(nzw * sizeof(unsigned long long) +
+                                       2 * (size_t)(ncol + 1) * sizeof(int) + 64));
+    mp.zbits = (unsigned long long *)ctx->pool_scratch.p;
     int *d_off = (int *)(mp.zbits + nzw);  // ncol column offsets
     int *d_cnt = d_off + ncol + 1;
     {
         arvx::CarveParams g;
         carve_geometry(ctx, g);
-        g.rec = ctx->d_rec;
+        g.rec = ctx->rec();
         hipLaunchKernelGGL(arvx::mc_zpack_rec_kernel,
                            dim3((unsigned)((size_t)g.tilesX * g.tilesY * mp.ZW)), dim3(256), 0,
                            ctx->stream, g, mp);
@@ -2701,7 +2613,7 @@ int arvx_mc_mesh(arvx_ctx *ctx, int apply_unseen, int64_t *triangles) {
         ARVX_HIP(ctx->pool_mesh_rgb.reserve((size_t)tcap * 6 * sizeof(unsigned)));  // face records
         arvx::McMeshParams mp;
         carve_geometry(ctx, mp.g);
-        mp.g.rec = ctx->d_rec;
+        mp.g.rec = ctx->rec();
         mp.paint = paint_plane(ctx);
         mp.apply_unseen = apply_unseen ? 1 : 0;
         mp.col = colour_list(ctx);
@@ -2818,7 +2730,7 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
         if (int rc = mc_cells_launch(ctx, ccap, &d_ncells)) return rc;
         arvx::McMeshParams mp;
         carve_geometry(ctx, mp.g);
-        mp.g.rec = ctx->d_rec;
+        mp.g.rec = ctx->rec();
         mp.paint = paint_plane(ctx);
         mp.apply_unseen = apply_unseen ? 1 : 0;
         mp.col = colour_list(ctx);
@@ -3021,15 +2933,13 @@ int arvx_fast_carve(arvx_ctx *ctx) {
     if (ctx->z0 != 0 || ctx->z1 != ctx->Z || ctx->stripe_world > 1)
         return fail(ARVX_ERR_STATE,
                     "arvx_fast_carve needs the whole grid in one context (connectivity is global)");
-    state_changes(ctx, false);
+    ctx->drop(Event::FastCarve);
     arvx::FloodParams fp;
     // a fresh model (the usual case: src/main.cpp calls fastCarve on a new Model) is neither
     // filled nor read: the kernels know its records, and flood_apply_rec_kernel writes them all
-    fp.fresh = ctx->fresh_pending ? 1 : 0;
+    fp.fresh = ctx->form == Form::Fresh ? 1 : 0;
     if (fp.fresh) {
-        void *buf = ctx->d_rec;
-        if (int rc = ensure_records(ctx, &buf, &ctx->rec_bytes)) return rc;
-        ctx->d_rec = (uint16_t *)buf;
+        if (int rc = ensure_records(ctx, ctx->pool_rec)) return rc;
     } else if (int mrc = need_rec(ctx)) {
         return mrc;
     }
@@ -3051,14 +2961,8 @@ int arvx_fast_carve(arvx_ctx *ctx) {
     const size_t o_dirty = o_tiles + up(2 * (size_t)tile_rows * sizeof(unsigned long long));
     const size_t o_changed = o_dirty + up(2 * (size_t)gflood);
     const size_t need = o_changed + 256;
-    if (ctx->flood_bytes < need) {
-        if (ctx->d_flood) (void)hipFree(ctx->d_flood);
-        ctx->d_flood = nullptr;
-        ctx->flood_bytes = 0;
-        ARVX_HIP(hipMalloc(&ctx->d_flood, need));
-        ctx->flood_bytes = need;
-    }
-    uint8_t *base = (uint8_t *)ctx->d_flood;
+    ARVX_HIP(ctx->pool_flood.reserve(need));
+    uint8_t *base = (uint8_t *)ctx->pool_flood.p;
     fp.open = (unsigned long long *)(base + o_bits);
     fp.reach = fp.open + nwords;
     unsigned long long *d_tiles = (unsigned long long *)(base + o_tiles);
@@ -3067,23 +2971,23 @@ int arvx_fast_carve(arvx_ctx *ctx) {
     fp.dirty_cur = fp.dirty_next = nullptr;  // set per launch of flood_step_kernel
 
     // carvable = what the dense carve clears on a fresh model: carved into records of its own
-    if (int rc = ensure_records(ctx, &ctx->d_flood_rec, &ctx->flood_rec_bytes)) return rc;
+    if (int rc = ensure_records(ctx, ctx->pool_flood_rec)) return rc;
     arvx::CarveParams g;
     carve_geometry(ctx, g);
-    g.rec = ctx->d_rec;
+    g.rec = ctx->rec();
     // (the coarse tiles that carve settles as a whole exist only as their codes, as in the model's
     // own lazy state: no N / 4 bytes of constants written here and read back by the conversion)
     const size_t ncoarse_f = (size_t)g.coarseX * g.coarseY * g.coarseZ;
     ARVX_HIP(ctx->pool_flood_code.reserve(ncoarse_f + 64));
     uint8_t *d_carv_code = (uint8_t *)ctx->pool_flood_code.p;
-    if (int rc = launch_carve(ctx, (uint16_t *)ctx->d_flood_rec, 0, ctx->V, 0, true, d_carv_code)) return rc;
+    if (int rc = launch_carve(ctx, (uint16_t *)ctx->pool_flood_rec.p, 0, ctx->V, 0, true, d_carv_code)) return rc;
     // (both conversions: one workgroup per row of tiles, 64 rows x (tiles along x + 1) words
     // of LDS, twice that for the way back)
     const int chunk = std::min(arvx::kFloodChunk, fp.XW);
     const size_t lds_words = (size_t)64 * (chunk + 1);
     hipLaunchKernelGGL(arvx::flood_open_from_rec_kernel, dim3((unsigned)(g.tilesY * g.tilesZ)),
                        dim3(256), lds_words * sizeof(unsigned long long), ctx->stream, g,
-                       (const uint16_t *)ctx->d_flood_rec, (const uint8_t *)d_carv_code, fp);
+                       (const uint16_t *)ctx->pool_flood_rec.p, (const uint8_t *)d_carv_code, fp);
     ARVX_HIP(hipGetLastError());
     // whole-tile pre-pass (fast_carve_kernels.h): seeds every completely open tile
     // that is connected to the origin tile through completely open tiles
@@ -3131,9 +3035,7 @@ int arvx_fast_carve(arvx_ctx *ctx) {
                            2 * lds_words * sizeof(unsigned long long), ctx->stream, g, fp);
     }
     ARVX_HIP(hipGetLastError());
-    ctx->fresh_pending = false;  // the records now hold every voxel's state
-    ctx->rec_valid = true;
-    ctx->lazy = false;
+    ctx->form = Form::Records;  // the records now hold every voxel's state
     ARVX_SYNC(ctx);
     return ARVX_OK;
 }

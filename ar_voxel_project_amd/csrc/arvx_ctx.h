@@ -18,17 +18,24 @@ int fail_msg(int code, const char *msg);
             return ::arvx::fail_hip(arvx_e_, #call, __FILE__, __LINE__);      \
     } while (0)
 
-// grow-only device buffer: results of repeated calls reuse the allocation
-// (hipMalloc / hipFree of tens of MB cost more than the kernels that fill them)
+// Grow-only device buffer: results of repeated calls reuse the allocation (hipMalloc / hipFree of
+// tens of MB cost more than the kernels that fill them).  It owns its memory: freed when the buffer
+// grows and when the context goes.  Headroom: a quarter more than asked for, for lists whose length
+// varies from call to call; Exact: what was asked for, for buffers whose size follows the grid, the
+// views or the call's arguments.
 struct DevPool {
+    enum Size { Headroom, Exact };
     void *p = nullptr;
     size_t cap = 0;
+    const bool exact;
+    explicit DevPool(Size size = Headroom) : exact(size == Exact) {}
+    DevPool(const DevPool &) = delete;
+    DevPool &operator=(const DevPool &) = delete;
+    ~DevPool() { release(); }
     hipError_t reserve(size_t bytes) {
         if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 4;
+        release();
+        const size_t want = exact ? bytes : bytes + bytes / 4;
         const hipError_t e = hipMalloc(&p, want);
         if (e == hipSuccess) cap = want;
         return e;
@@ -88,61 +95,59 @@ struct Ctx {
     // _download / _device_ptr) is a staging buffer, allocated on demand and converted from / to
     // the records inside those calls; bit2 of uploaded bytes (voxel painted UNSEEN_COLOR by a
     // host Model) is kept beside the records as one bit plane (`paint`).
-    uint16_t *d_rec = nullptr;   // records of planes ze0..ze1-1 (+ padding to whole coarse tiles)
-    size_t rec_bytes = 0;
-    bool rec_valid = false;      // d_rec holds the current state (else: fresh_pending)
-    // every call that changes occupied / seen bits counts here: what was derived from the state
-    // (the host hand-off's packets) is current while the count it was taken at still stands
+    // The state's form.  Fresh: a fresh model (all occupied, none seen) that exists only as this
+    // value -- need_rec writes it out, a carve of it writes every record without reading one.
+    // Records: pool_rec holds the state.  Lazy: as Records, but the coarse tiles the carve of a
+    // fresh model settled as a whole exist only as their code in pool_ccode (arvx_device.h);
+    // their records are not written.
+    enum class Form { Fresh, Records, Lazy };
+    Form form = Form::Fresh;
+    DevPool pool_rec{DevPool::Exact};  // records of planes ze0..ze1-1 (+ padding to whole coarse tiles)
+    uint16_t *rec() const { return (uint16_t *)pool_rec.p; }
+    DevPool pool_ccode;
+    // every call that changes occupied / seen bits counts here.  What is derived from the state
+    // carries the count it was built at as its stamp (0: none): it is current while that count
+    // still stands
     unsigned long long state_seq = 1;
     // the colour pass's bit planes of the state (occupied; seen by no view), kept for a closure that
-    // follows: valid while state_seq == planes_seq; planes_unseen: handleUnseen has run since (the
-    // records' occupancy is the occupancy plane | the never-seen plane)
+    // follows; planes_unseen: handleUnseen has run since (the records' occupancy is the occupancy
+    // plane | the never-seen plane: next_state)
     DevPool pool_state_planes;  // occupancy plane, then never-seen plane (planes_words words each)
     size_t planes_words = 0;
     unsigned long long planes_seq = 0;
-    bool planes_ok = false, planes_unseen = false;
+    bool planes_unseen = false;
     DevPool pool_state_packets;  // arvx_state_download_packets: occupancy | seen, worst-case size each
     unsigned long long packets_seq = 0;
-    bool packets_valid = false;
     long long packet_need[2] = {0, 0};
-    // lazy state (arvx_device.h): after the carve of a fresh model the coarse tiles it settled
-    // as a whole exist only as their code in `ccode`; their records are not written
-    DevPool pool_ccode;
     DevPool pool_cstate;         // per coarse tile: settled by earlier carves (CarveParams::cstate)
     size_t cstate_tiles = 0;     // ... valid for this many tiles of the current layout (0: not)
-    bool lazy = false;
-    uint8_t *d_state = nullptr;  // byte staging, planes ze0..ze1-1 (lazy)
-    uint8_t *owned() const { return d_state + (size_t)(z0 - ze0) * X * Y; }
+    DevPool pool_state_bytes{DevPool::Exact};  // byte staging, planes ze0..ze1-1 (allocated on demand)
+    uint8_t *owned() const { return (uint8_t *)pool_state_bytes.p + (size_t)(z0 - ze0) * X * Y; }
     DevPool pool_paint;          // bit plane (bitplane_kernels.h layout) over planes ze0..ze1-1
     bool paint_valid = false;    // some voxel is painted: the plane takes part in the stages
     int ncu = 0;                 // compute units of the device (cached)
     int carve_seq = 0;           // parity of the undecided-list counters (carve_coarse_kernel)
-    size_t carve_layout = 0;     // d_coarse layout those counters were zeroed for
+    size_t carve_layout = 0;     // pool_coarse layout those counters were zeroed for
     // the streaming carve (carve_stream_kernels.h): control block + list entries + item queues
-    void *d_stream = nullptr;
-    size_t stream_bytes = 0;
+    DevPool pool_stream{DevPool::Exact};
     size_t stream_layout = 0;    // layout the control block was zeroed for (0: zero it again)
     unsigned carve_epoch = 0;    // tag of the latest streaming launch's granules
-    void *d_timeline = nullptr;  // ARVX_TIMELINE diagnostic builds only
+    DevPool pool_timeline{DevPool::Exact};  // ARVX_TIMELINE diagnostic builds only
     int64_t timeline_n = 0;
     int timeline_rec = 32;  // bytes per record
-    bool fresh_pending = false;  // a fresh model that exists only as this flag (neither form valid)
-    void *d_flood_rec = nullptr;  // records of the "carvable" plane of arvx_fast_carve
+    DevPool pool_flood_rec{DevPool::Exact};  // records of the "carvable" plane of arvx_fast_carve
     DevPool pool_flood_code;      // ... and the codes of the coarse tiles that exist only as a code
-    size_t flood_rec_bytes = 0;
-    void *d_coarse = nullptr;    // coarse pre-pass masks of the carve kernel
-    size_t coarse_bytes = 0;
-    unsigned long long *d_stats = nullptr;
+    DevPool pool_coarse{DevPool::Exact};  // coarse pre-pass masks of the carve kernel
+    DevPool pool_stats{DevPool::Exact};   // 8 counters + flags
+    unsigned long long *stats() const { return (unsigned long long *)pool_stats.p; }
     // times a list total had to be fetched from the device because the page-locked word still
     // read -1 at the synchronisation (host_total, arvx_capi.hip); expected: never
     unsigned long long host_total_fallbacks = 0;
-    void *d_scratch = nullptr;  // work buffer of the calls on `stream`
-    size_t scratch_bytes = 0;
+    DevPool pool_scratch{DevPool::Exact};  // work buffer of the calls on `stream`
     // work buffer of the hand-off calls (arvx_occupancy_compress): they may run on `xstream`
-    // BESIDE a set_views / carve on `stream`, so they never touch d_scratch
+    // BESIDE a set_views / carve on `stream`, so they never touch pool_scratch
     DevPool pool_xscratch;
-    void *d_flood = nullptr;  // work buffer of arvx_fast_carve, kept between calls
-    size_t flood_bytes = 0;
+    DevPool pool_flood{DevPool::Exact};  // work buffer of arvx_fast_carve, kept between calls
 
     // views
     bool views_ready = false;    // matrices + bit planes + tables: the carve can run
@@ -151,14 +156,19 @@ struct Ctx {
     int V = 0, W = 0, H = 0;
     int bgWords = 0, satStride = 0;
     int satW = 0, satH = 0;  // summed-area table: satH = H + 1 rows of satW >= W + 1 entries
-    float *d_M = nullptr;
-    float *d_campos = nullptr;
-    uint32_t *d_bg = nullptr;
-    uint16_t *d_sat = nullptr;
+    // V x 12 matrices, V x 3 camera positions, V x bgWords background words, V x satStride table
+    // entries: allocated for one number and size of views
+    DevPool pool_M{DevPool::Exact}, pool_campos{DevPool::Exact}, pool_bg{DevPool::Exact},
+        pool_sat{DevPool::Exact};
+    float *M() const { return (float *)pool_M.p; }
+    float *campos() const { return (float *)pool_campos.p; }
+    uint32_t *bg() const { return (uint32_t *)pool_bg.p; }
+    uint16_t *sat() const { return (uint16_t *)pool_sat.p; }
     std::vector<float> h_M, h_campos;
 
     // colour pass
-    uint8_t *d_images = nullptr;  // V x H x W x 3, BGR
+    DevPool pool_images{DevPool::Exact};  // V x H x W x 3, BGR
+    uint8_t *images() const { return (uint8_t *)pool_images.p; }
     bool images_ready = false;
     int *d_surf_index = nullptr;      // compacted flat indices (slab-local)
     float4 *d_surf_rgba = nullptr;    // r, g, b, has-sample flag per surface voxel
@@ -172,7 +182,7 @@ struct Ctx {
     // the owned part, relative to the owned planes.
     std::vector<int> h_surf_index;    // host copy (ascending)
     std::vector<uint8_t> h_surf_has;
-    bool color_ready = false;
+    bool color_ready = false;         // the colour list: the fields above are read only while set
     // the list's plane and its index (bitplane_kernels.h, SparseWord) over the owned planes
     DevPool pool_col_bits, pool_col_rank;
 
@@ -180,20 +190,75 @@ struct Ctx {
     int *d_clo_index = nullptr;
     void *d_clo_rgba = nullptr;  // float4 per filled voxel
     int64_t clo_count = 0;
-    bool closure_ready = false;
+    bool closure_ready = false;  // the closure list: the fields around are read only while set
     int closure_unseen = 0;
-    // the state holds the fills of a closure (its list may have been dropped since): a second
-    // closure is refused until a carve, an upload or a reset replaces the state (arvx.h)
+    // the state holds the fills of a closure (its list may have been dropped since): colour calls
+    // and a second closure are refused until a carve, an upload or a reset replaces the state (arvx.h)
     bool closure_fills = false;
     int closure_radius = 0;
     std::vector<int> h_clo_index;
     DevPool pool_clo_bits, pool_clo_rank;  // the filled voxels' plane and index (SparseWord)
 
+    // ---- what each call drops --------------------------------------------------------------
+    // The rules of arvx.h ("What the context's results belong to") as one table: a row per event,
+    // named after the method of CtxModel (tests/stage_model.py) that restates it.  Every entry point
+    // calls drop() once, after its refusals and before its work, so that a refused call leaves the
+    // context as it was.  (The closure calls it where its fills go into the state: the colour pass's
+    // planes it starts from are those of the state before.)  The mesh products (mc_ready,
+    // weld_ready, smooth_*) are not here: each lives until the next call of its own stage.
+    enum class Event {
+        SetViews, SetImages, Color, UploadColors, ProjectionAssoc, HandleUnseen, Closure,
+        Carve, FastCarve, UploadState, UploadPlanes, UploadHalo, Reset
+    };
+    void drop(Event e) {
+        struct Row { uint8_t colours, closure, fills, paint, cstate, state; };
+        static constexpr Row kRows[] = {
+            //                    colour closure closure paint cstate state
+            //                    list   list    fills         tiles  changes
+            /* SetViews        */ {1,    1,      0,      0,    0,     0},
+            /* SetImages       */ {1,    1,      0,      0,    0,     0},
+            /* Color           */ {1,    1,      0,      0,    0,     0},
+            /* UploadColors    */ {1,    1,      0,      0,    0,     0},
+            /* ProjectionAssoc */ {1,    0,      0,      0,    0,     0},  // (a change of grouping)
+            /* HandleUnseen    */ {0,    1,      0,      0,    0,     2},
+            /* Closure         */ {0,    1,      0,      0,    1,     1},
+            /* Carve           */ {1,    1,      1,      1,    0,     1},
+            /* FastCarve       */ {1,    1,      1,      1,    0,     1},
+            /* UploadState     */ {1,    1,      1,      2,    1,     1},
+            /* UploadPlanes    */ {1,    1,      1,      1,    1,     1},
+            /* UploadHalo      */ {1,    1,      1,      0,    1,     1},
+            /* Reset           */ {1,    1,      1,      1,    1,     1},
+        };
+        // paint 2: the owned planes' paint is replaced; the plane stays where halo planes keep
+        // theirs.  state 2: only never-seen voxels become occupied (next_state).  cstate: a call
+        // that may occupy or un-see voxels drops what earlier carves settled for whole coarse
+        // tiles; carving and handleUnseen leave a tile that is carved and seen / seen as a whole
+        // as it is.
+        static_assert(sizeof kRows / sizeof kRows[0] == (size_t)Event::Reset + 1, "a row per event");
+        const Row &r = kRows[(int)e];
+        if (r.colours) color_ready = false;
+        if (r.closure) closure_ready = false;
+        if (r.fills) closure_fills = false;
+        if (r.paint == 1 || (r.paint == 2 && nvox_ext == nvox)) paint_valid = false;
+        if (r.cstate) cstate_tiles = 0;
+        if (r.state) next_state(r.state == 2);
+    }
+    // The state changes: whatever carries the old count as its stamp is stale -- but for
+    // handleUnseen (unseen_only) the colour pass's planes of the state before stay usable: its
+    // occupancy is their occupancy | their never-seen plane (planes_unseen).
+    void next_state(bool unseen_only) {
+        if (unseen_only && planes_seq == state_seq) {
+            planes_seq = state_seq + 1;
+            planes_unseen = true;
+        }
+        ++state_seq;
+    }
+
     // marching-cubes hand-off: active cells (x, y, z, cube index), reference order
     void *d_mc_cells = nullptr;
     int64_t mc_count = 0;
     bool mc_ready = false;
-    // storage behind the d_surf_* / d_clo_* / d_mc_cells views (kept until destroy)
+    // storage behind the d_surf_* / d_clo_* / d_mc_cells views
     DevPool pool_surf_index, pool_surf_rgb, pool_surf_depth, pool_surf_has, pool_clo_index,
         pool_clo_rgba, pool_mc_cells, pool_raw_masks, pool_mesh_verts, pool_mesh_rgb, pool_mesh_off;
     int64_t mesh_tris = 0;  // triangles of the last arvx_mc_mesh
@@ -210,96 +275,23 @@ struct Ctx {
         pool_smooth_normals;
     bool smooth_csr_ready = false, smooth_ready = false;
     int smooth_q = 0;  // where the smoothed positions are: 0 the welded mesh's, 1 / 2 a buffer
-    void release_pools() {
-        pool_surf_index.release();
-        pool_surf_rgb.release();
-        pool_surf_depth.release();
-        pool_surf_has.release();
-        pool_clo_index.release();
-        pool_clo_rgba.release();
-        pool_mc_cells.release();
-        pool_raw_masks.release();
-        pool_flood_code.release();
-        pool_mesh_verts.release();
-        pool_mesh_rgb.release();
-        pool_mesh_off.release();
-        pool_weld_planes.release();
-        pool_weld_rank.release();
-        pool_weld_index.release();
-        pool_weld_verts.release();
-        pool_weld_rgb.release();
-        pool_weld_faces.release();
-        weld_ready = false;
-        pool_smooth_csr.release();
-        pool_smooth_nbr.release();
-        pool_smooth_inc.release();
-        pool_smooth_verts.release();
-        pool_smooth_cross.release();
-        pool_smooth_normals.release();
-        smooth_csr_ready = smooth_ready = false;
-        pool_xscratch.release();
-        pool_vstrip.release();
-        vstrip_key = 0;
-        pool_compact.release();
-        pool_chunk_counts.release();
-        counts_stride = 0;
-        pool_state_packets.release();
-        pool_state_planes.release();
-        planes_ok = false;
-        packets_valid = false;
-        compact_tickets = 0;
-        pool_paint.release();
-        pool_ccode.release();
-        pool_cstate.release();
-        cstate_tiles = 0;
-        pool_col_bits.release();
-        pool_col_rank.release();
-        pool_clo_bits.release();
-        pool_clo_rank.release();
+
+    // (the device buffers are freed by their DevPool members, after this)
+    ~Ctx() {
+        if (h_fault) (void)hipHostFree(h_fault);
     }
     void free_mc() {
         d_mc_cells = nullptr;
         mc_count = 0;
         mc_ready = false;
     }
-
-    void free_closure() {
-        d_clo_index = nullptr;
-        d_clo_rgba = nullptr;
-        clo_count = 0;
-        closure_ready = false;
-        clo_host_count = -1;
-        h_clo_index.clear();
-    }
-
     void free_views() {
-        if (d_M) (void)hipFree(d_M);
-        if (d_campos) (void)hipFree(d_campos);
-        if (d_bg) (void)hipFree(d_bg);
-        if (d_sat) (void)hipFree(d_sat);
-        d_M = d_campos = nullptr;
-        d_bg = nullptr;
-        d_sat = nullptr;
+        pool_M.release();
+        pool_campos.release();
+        pool_bg.release();
+        pool_sat.release();
         views_ready = false;
         cameras_ready = false;
-    }
-    void free_surface() {
-        free_closure();
-        d_surf_index = nullptr;
-        d_surf_rgba = nullptr;
-        d_surf_depth = nullptr;
-        d_surf_has = nullptr;
-        color_ready = false;
-        surf_count = 0;
-        surf_host_count = -1;
-        h_surf_index.clear();
-        h_surf_has.clear();
-    }
-    void free_color() {
-        free_surface();
-        if (d_images) (void)hipFree(d_images);
-        d_images = nullptr;
-        images_ready = false;
     }
 };
 
