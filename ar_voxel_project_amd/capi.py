@@ -48,6 +48,7 @@ SYMBOLS = [
     "arvx_pack_occupancy", "arvx_pack_occupancy_global", "arvx_carve", "arvx_carve_views", "arvx_fast_carve",
     "arvx_color", "arvx_surface_count", "arvx_surface_download",
     "arvx_surface_depth_download", "arvx_color_samples",
+    "arvx_color_visible", "arvx_surface_visible_download", "arvx_view_depth_download",
     "arvx_colors_upload", "arvx_closure", "arvx_closure_count", "arvx_closure_download",
     "arvx_closure_download32",
     "arvx_mc_cells", "arvx_mc_cells_download", "arvx_mc_mesh", "arvx_mc_mesh_download",
@@ -177,6 +178,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "arvx_mc_mesh_smooth"):
         lib.arvx_mc_mesh_smooth.argtypes = [p, C.c_int, C.c_float, C.c_float]
         lib.arvx_mc_mesh_smooth_download.argtypes = [p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "arvx_color_visible"):
+        lib.arvx_color_visible.argtypes = [p, C.c_int, C.c_float]
+        lib.arvx_surface_visible_download.argtypes = [p, C.POINTER(C.c_int32)]
+        lib.arvx_view_depth_download.argtypes = [p, C.c_int, f32p]
     for name in SYMBOLS:
         if ab_build and not hasattr(lib, name):
             continue
@@ -548,6 +553,28 @@ class Context:
         if n.value:
             self._ck(self._lib.arvx_surface_depth_download(self._h, _fp(d)))
         return d
+
+    def color_visible(self, mode: int, tolerance: float) -> None:
+        """arvx_color_visible: the colour vote over the views in which each voxel is visible
+        (per-view depth buffers of the surface; tolerance in world units, >= 0, may be inf)."""
+        self._ck(self._lib.arvx_color_visible(self._h, int(mode), float(tolerance)))
+
+    def surface_visible(self) -> np.ndarray:
+        """arvx_surface_visible_download: views each coloured voxel is visible in (surface()'s
+        order; 0: the voxel took the plain vote)."""
+        n = C.c_int64()
+        self._ck(self._lib.arvx_surface_count(self._h, C.byref(n)))
+        out = np.empty(n.value, np.int32)
+        if n.value:
+            self._ck(self._lib.arvx_surface_visible_download(
+                self._h, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
+    def view_depth(self, view: int) -> np.ndarray:
+        """arvx_view_depth_download: the depth buffer of one view, (H, W) float32."""
+        out = np.empty((self.H, self.W), np.float32)
+        self._ck(self._lib.arvx_view_depth_download(self._h, int(view), _fp(out)))
+        return out
 
     SAMPLE_DTYPE = np.dtype([("r", np.uint8), ("g", np.uint8), ("b", np.uint8), ("valid", np.uint8),
                              ("depth", np.float32)])

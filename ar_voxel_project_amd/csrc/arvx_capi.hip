@@ -34,6 +34,7 @@
 #include "mc_mesh_kernels.h"
 #include "mc_weld_kernels.h"
 #include "mc_smooth_kernels.h"
+#include "visibility_kernels.h"
 #include "exchange_kernels.h"
 #include <algorithm>
 
@@ -1802,8 +1803,8 @@ int arvx_set_images(arvx_ctx *ctx, const uint8_t *const *images, size_t stride) 
     return ARVX_OK;
 }
 
-int arvx_color(arvx_ctx *ctx, int mode) {
-    ARVX_CHECK_CTX(ctx);
+// arvx_color's refusals (arvx_color_visible adds its own after them)
+static int color_refusals(Ctx *ctx, int mode) {
     if (!ctx->cameras_ready) return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
     if (!ctx->images_ready) return fail(ARVX_ERR_STATE, "arvx_set_images has not been called");
     if (!ctx->has_campos) return fail(ARVX_ERR_STATE, "arvx_set_views was given no campos");
@@ -1811,6 +1812,17 @@ int arvx_color(arvx_ctx *ctx, int mode) {
         return fail(ARVX_ERR_INVALID, "colour mode %d", mode);
     if (ctx->stripe_world > 1)
         return fail(ARVX_ERR_STATE, "the colour pass needs contiguous slabs (neighbour planes)");
+    return ARVX_OK;
+}
+
+static int launch_visible_vote(Ctx *ctx, const arvx::VoteParams &vp, float tol);
+// the page-locked word the large-footprint sweep leaves the number of large footprints in (slot 5
+// is otherwise used only inside arvx_state_download_packets)
+static constexpr int kVisNeedSlot = 5;
+
+// The colour pass of arvx_color (visible = false) and arvx_color_visible (visible = true: the
+// depth buffers, then the visible vote, in place of color_vote_kernel).
+static int color_pass(Ctx *ctx, int mode, bool visible, float tol) {
     ctx->drop(Event::Color);
     // surface = occupied and not inner, on bit planes over the context's planes; colours are
     // voted for the planes [c_lo, c_hi) (stage_ranges): the owned ones and the halo planes
@@ -1863,6 +1875,7 @@ int arvx_color(arvx_ctx *ctx, int mode) {
         ctx->d_surf_depth = (float *)ctx->pool_surf_depth.p;
         ARVX_HIP(ctx->pool_surf_has.reserve((size_t)cap));
         ctx->d_surf_has = (uint8_t *)ctx->pool_surf_has.p;
+        if (visible) ARVX_HIP(ctx->pool_vis_views.reserve((size_t)cap * sizeof(int)));
         const long long *d_total = nullptr;
         if (int rc = bit_compact(ctx, d_surf, nw_ext, gext, cap, ctx->d_surf_index,
                                  (arvx::SparseWord *)ctx->pool_col_rank.p, 0, &d_total))
@@ -1885,16 +1898,20 @@ int arvx_color(arvx_ctx *ctx, int mode) {
         vp.rgba = ctx->d_surf_rgba;
         vp.depth = ctx->d_surf_depth;
         vp.has = ctx->d_surf_has;
-        if (ctx->assoc == ARVX_ASSOC_LEFT)
+        if (visible) {
+            if (int rc = launch_visible_vote(ctx, vp, tol)) return rc;
+        } else if (ctx->assoc == ARVX_ASSOC_LEFT) {
             hipLaunchKernelGGL(arvx::color_vote_kernel<true>, dim3((unsigned)((cap + 255) / 256)),
                                dim3(256), 0, ctx->stream, vp);
-        else
+        } else {
             hipLaunchKernelGGL(arvx::color_vote_kernel<false>, dim3((unsigned)((cap + 255) / 256)),
                                dim3(256), 0, ctx->stream, vp);
+        }
         ARVX_HIP(hipGetLastError());
         ARVX_SYNC(ctx);
         total = host_total(ctx, 0);
         if (total < 0) return fail(ARVX_ERR_HIP, "the compaction left no count");
+        if (visible && ctx->h_totals[kVisNeedSlot] >= 0) ctx->vis_large_need = ctx->h_totals[kVisNeedSlot];
         if (total <= cap || attempt) break;
         cap = total + total / 8;  // (once more, with room for all)
     }
@@ -1907,8 +1924,85 @@ int arvx_color(arvx_ctx *ctx, int mode) {
         ctx->d_surf_has = nullptr;
     }
     ctx->color_ready = true;
+    ctx->color_visible = visible;
     // (arvx_get_stats' surface_voxels: the owned part of the list, counted when it is asked for)
     return ARVX_OK;
+}
+
+int arvx_color(arvx_ctx *ctx, int mode) {
+    ARVX_CHECK_CTX(ctx);
+    if (int rc = color_refusals(ctx, mode)) return rc;
+    return color_pass(ctx, mode, false, 0.f);
+}
+
+// The depth buffers of the views (clear, splat, large footprints) and the visible vote, on the list
+// vp describes (its length on the device): no synchronisation.
+static int launch_visible_vote(Ctx *ctx, const arvx::VoteParams &vp, float tol) {
+    ctx->h_totals[kVisNeedSlot] = -1;
+    const size_t plane = (size_t)ctx->W * ctx->H, nz = plane * ctx->V;
+    ARVX_HIP(ctx->pool_vis_depth.reserve(nz * sizeof(uint32_t)));
+    // large footprints: room for what the last call wanted to list (an eighth more), at least a
+    // quarter of the list and 64 Ki more; what does not fit is swept by the splat's own waves
+    const long long cap = vp.n;
+    const long long want = std::max((1ll << 16) + cap / 4, ctx->vis_large_need + ctx->vis_large_need / 8);
+    const unsigned large_cap = (unsigned)std::min<long long>({cap * ctx->V, want, (long long)UINT32_MAX});
+    ARVX_HIP(ctx->pool_vis_large.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
+    uint32_t *zbuf = (uint32_t *)ctx->pool_vis_depth.p;
+    unsigned *n_large = (unsigned *)ctx->pool_vis_large.p;
+    arvx::SplatRect *large = (arvx::SplatRect *)((uint8_t *)ctx->pool_vis_large.p + 64);
+    const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
+    hipLaunchKernelGGL(arvx::vis_clear_kernel, dim3((unsigned)std::min<size_t>((nz + 255) / 256, 8 * ncu)),
+                       dim3(256), 0, ctx->stream, zbuf, nz, n_large);
+    ARVX_HIP(hipGetLastError());
+    arvx::SplatParams sp;
+    sp.index = vp.index;
+    sp.cap = cap;
+    sp.n_dev = vp.n_dev;
+    sp.X = ctx->X;
+    sp.Y = ctx->Y;
+    sp.s = ctx->s;
+    sp.V = ctx->V;
+    sp.W = ctx->W;
+    sp.H = ctx->H;
+    sp.M = ctx->M();
+    sp.zbuf = zbuf;
+    sp.large = large;
+    sp.n_large = n_large;
+    sp.large_cap = large_cap;
+    // (the x grid strides over the list: its capacity can be several times its length)
+    const dim3 sgrid((unsigned)std::min<long long>((cap + 255) / 256, 1024), (unsigned)ctx->V);
+    if (ctx->assoc == ARVX_ASSOC_LEFT)
+        hipLaunchKernelGGL(arvx::vis_splat_kernel<true>, sgrid, dim3(256), 0, ctx->stream, sp);
+    else
+        hipLaunchKernelGGL(arvx::vis_splat_kernel<false>, sgrid, dim3(256), 0, ctx->stream, sp);
+    ARVX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(arvx::vis_splat_large_kernel, dim3((unsigned)(4 * ncu)), dim3(256), 0, ctx->stream,
+                       (const arvx::SplatRect *)large, (const unsigned *)n_large, large_cap, zbuf, ctx->W,
+                       ctx->H, ctx->d_totals_host + kVisNeedSlot);
+    ARVX_HIP(hipGetLastError());
+    arvx::VisVoteParams q;
+    q.vote = vp;
+    q.zbuf = zbuf;
+    q.tol = tol;
+    q.views = (int *)ctx->pool_vis_views.p;
+    if (ctx->assoc == ARVX_ASSOC_LEFT)
+        hipLaunchKernelGGL(arvx::vis_vote_kernel<true>, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0,
+                           ctx->stream, q);
+    else
+        hipLaunchKernelGGL(arvx::vis_vote_kernel<false>, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0,
+                           ctx->stream, q);
+    return ARVX_OK;
+}
+
+int arvx_color_visible(arvx_ctx *ctx, int mode, float tolerance) {
+    ARVX_CHECK_CTX(ctx);
+    if (int rc = color_refusals(ctx, mode)) return rc;
+    if (std::isnan(tolerance) || tolerance < 0.f)
+        return fail(ARVX_ERR_INVALID, "tolerance %g: must be >= 0 (finite or +inf)", (double)tolerance);
+    if (ctx->z0 != 0 || ctx->z1 != ctx->Z)
+        return fail(ARVX_ERR_STATE, "arvx_color_visible needs a whole-grid context (the depth buffers "
+                                    "need every surface voxel)");
+    return color_pass(ctx, mode, true, tolerance);
 }
 
 int arvx_color_samples(arvx_ctx *ctx, int64_t n, const int64_t *index, int views,
@@ -2041,6 +2135,44 @@ int arvx_surface_depth_download(arvx_ctx *ctx, float *depth) {
     size_t k = 0;
     for (size_t e = lo; e < hi; ++e)
         if (ctx->h_surf_has[e]) depth[k++] = hdepth[e];
+    return ARVX_OK;
+}
+
+static int visible_ready(const Ctx *ctx) {
+    if (!ctx->color_ready || !ctx->color_visible)
+        return fail(ARVX_ERR_STATE, "no visible colour result (call arvx_color_visible)");
+    return ARVX_OK;
+}
+
+int arvx_surface_visible_download(arvx_ctx *ctx, int32_t *views) {
+    ARVX_CHECK_CTX(ctx);
+    if (int rc = visible_ready(ctx)) return rc;
+    if (!views) return fail(ARVX_ERR_INVALID, "null argument");
+    if (int rc = surf_host(ctx)) return rc;
+    std::vector<int32_t> h((size_t)ctx->surf_count);
+    if (ctx->surf_count) {
+        ARVX_HIP(hipMemcpyAsync(h.data(), ctx->pool_vis_views.p, h.size() * sizeof(int32_t),
+                                hipMemcpyDeviceToHost, ctx->stream));
+        ARVX_SYNC(ctx);
+    }
+    size_t lo, hi;
+    long long base;
+    owned_part(ctx, ctx->h_surf_index, lo, hi, base);
+    size_t k = 0;
+    for (size_t e = lo; e < hi; ++e)
+        if (ctx->h_surf_has[e]) views[k++] = h[e];
+    return ARVX_OK;
+}
+
+int arvx_view_depth_download(arvx_ctx *ctx, int view, float *depth) {
+    ARVX_CHECK_CTX(ctx);
+    if (int rc = visible_ready(ctx)) return rc;
+    if (view < 0 || view >= ctx->V) return fail(ARVX_ERR_INVALID, "view %d outside [0,%d)", view, ctx->V);
+    if (!depth) return fail(ARVX_ERR_INVALID, "null argument");
+    const size_t plane = (size_t)ctx->W * ctx->H;
+    ARVX_HIP(hipMemcpyAsync(depth, (const uint32_t *)ctx->pool_vis_depth.p + plane * view,
+                            plane * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
     return ARVX_OK;
 }
 

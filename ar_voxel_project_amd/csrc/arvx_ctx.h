@@ -185,6 +185,12 @@ struct Ctx {
     bool color_ready = false;         // the colour list: the fields above are read only while set
     // the list's plane and its index (bitplane_kernels.h, SparseWord) over the owned planes
     DevPool pool_col_bits, pool_col_rank;
+    // arvx_color_visible: the colour list is its result (read only while color_ready is set too);
+    // the views' depth buffers (V x H x W), the large-footprint list behind its counter, and the
+    // number of views each list entry is visible in
+    bool color_visible = false;
+    long long vis_large_need = 0;  // large footprints the last call wanted to list (sizes the list)
+    DevPool pool_vis_depth{DevPool::Exact}, pool_vis_large{DevPool::Exact}, pool_vis_views;
 
     // closure (dilation) result: filled voxels, ascending index
     int *d_clo_index = nullptr;
@@ -236,7 +242,7 @@ struct Ctx {
         // as it is.
         static_assert(sizeof kRows / sizeof kRows[0] == (size_t)Event::Reset + 1, "a row per event");
         const Row &r = kRows[(int)e];
-        if (r.colours) color_ready = false;
+        if (r.colours) color_ready = color_visible = false;
         if (r.closure) closure_ready = false;
         if (r.fills) closure_fills = false;
         if (r.paint == 1 || (r.paint == 2 && nvox_ext == nvox)) paint_valid = false;

@@ -330,6 +330,49 @@ int arvx_surface_download(arvx_ctx *ctx, int64_t *index, float *rgb);
 /* Smallest sample depth of each coloured voxel (same order), as the reference
  * computes it: (float)cv::norm(cameras[i] - world), src/ColorReconstruction.h:59. */
 int arvx_surface_depth_download(arvx_ctx *ctx, float *depth);
+/* ---- visible colour (extension beyond the reference) ----------------------------------------
+ * The reference's colour pass never asks whether a camera sees a voxel.  arvx_color_visible is
+ * arvx_color with a visibility test: a voxel votes only with the views in which it is visible,
+ * decided by a per-view depth buffer of the carved surface.  Definition, on a whole-grid context,
+ * its state, its views M (with campos) and its images.  S = the voxels arvx_color colours
+ * (occupied and not inner), ascending flat index.  Every projection below is arvx_color's: fp64
+ * products of the fp32 operands, the row sum in the context's grouping
+ * (arvx_ctx_set_projection_assoc) rounded to fp32, then IEEE fp32 quotients.
+ *  1. Centre.  For voxel s = (x, y, z) and view v, a0, a1, a2 = the rows of M_v * toWord(x, y, z);
+ *     its pixel and "inside" test are the colour pass's (round half away of a0/a2, a1/a2).
+ *  2. Footprint.  For the eight corners (dx, dy, dz) in {-1, +1}^3 the world point
+ *     w0 = ((float)y + 0.5f*dy) * s, w1 = ((float)x + 0.5f*dx) * s, w2 = -(((float)z + 0.5f*dz) * s)
+ *     (each operation rounded once in fp32), projected the same way to (c0, c1, c2), with
+ *     qu = c0/c2, qv = c1/c2.  s SPLATS in view v iff the centre's a2 > 0, every corner's c2 > 0
+ *     and all 16 quotients are finite.  Its footprint is then the pixels (c, r) with 0 <= c < W,
+ *     0 <= r < H, round(min qu) <= c <= round(max qu), round(min qv) <= r <= round(max qv)
+ *     (round = std::round on the fp32 value); it may be empty.
+ *  3. Depth buffer.  Z_v[p] = the minimum of the centre a2 over the voxels of S that splat in v
+ *     with p in their footprint; +inf where there are none.  (A minimum of fp32 values: the order
+ *     in which voxels arrive cannot change it.)
+ *  4. Visibility.  s is visible in v iff its centre is inside image v, a2 > 0 and
+ *     a2 <= Z_v[pix] + tol (one fp32 addition).  tol: the caller's tolerance in world units,
+ *     >= 0, finite or +inf.
+ *  5. Vote.  arvx_color's rule (view order, strict < on the sample depth, the first view wins
+ *     ties; average: roundf(sum / n)) over the samples of the views in which s is visible.  A
+ *     voxel visible in no view gets exactly what arvx_color gives it.  So the coloured voxels,
+ *     their w and arvx_surface_depth_download (the minimum over ALL samples) are arvx_color's;
+ *     only RGB values change.  With tol = +inf and every voxel in front of every camera the
+ *     result is arvx_color's bit for bit.
+ * Same preconditions and refusals as arvx_color; slab and striped contexts: ARVX_ERR_STATE; a mode
+ * other than ARVX_COLOR_CLOSEST / ARVX_COLOR_AVERAGE or a NaN or negative tolerance:
+ * ARVX_ERR_INVALID.  It fills the colour list arvx_color fills, with the same lifetime, so
+ * arvx_surface_*, arvx_export_model, arvx_closure and the meshes take it as they take
+ * arvx_color's.  One host synchronisation, as arvx_color.  Device memory: the depth buffers,
+ * V * W * H * 4 bytes, allocated at the first call and kept until the context is destroyed. */
+int arvx_color_visible(arvx_ctx *ctx, int mode, float tolerance);
+/* For each coloured voxel, in arvx_surface_download's order, the number of views it is visible
+ * in (0: it took the fallback). */
+int arvx_surface_visible_download(arvx_ctx *ctx, int32_t *views);
+/* Z_view as H x W floats (row-major).  Both downloads need the colour list of an
+ * arvx_color_visible (ARVX_ERR_STATE otherwise, after a plain arvx_color too); a view outside
+ * [0, V): ARVX_ERR_INVALID. */
+int arvx_view_depth_download(arvx_ctx *ctx, int view, float *depth);
 /* The per-voxel colour lists behind the vote -- what the reference's voxel_pass appends with
  * Model::addColor (src/ColorReconstruction.h:44-60, src/Model.h:142-149) and getColors returns:
  * for each of n voxels (flat index over the context's own planes, any order) V samples in view

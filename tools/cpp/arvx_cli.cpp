@@ -178,7 +178,7 @@ int main(int argc, char *argv[]) {
         {"z", "100"}, {"size", "0.0028"}, {"color", "0"}, {"scale", "1.0"}, {"dx", "0.0"},
         {"dy", "0.0"}, {"dz", "0.0"}, {"model_debug", "false"}, {"postprocessing", "true"},
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
-        {"smooth", "0"}};
+        {"smooth", "0"}, {"visible", "false"}, {"visibleTol", "3"}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -186,7 +186,9 @@ int main(int argc, char *argv[]) {
                      "-calibration, -carve, -x -y -z -size, -color, -scale -dx -dy -dz,\n"
                      "  -postprocessing, -intermediateMesh, -outFile (flags of the reference's "
                      "src/main.cpp:16-39), -weld (shared mesh vertices),\n"
-                     "  -smooth=N (the welded mesh after N Taubin iterations, lambda 0.5, mu -0.53)\n";
+                     "  -smooth=N (the welded mesh after N Taubin iterations, lambda 0.5, mu -0.53),\n"
+                     "  -visible=true (-color=1|2 over the views in which each voxel is visible),\n"
+                     "  -visibleTol=T (its depth tolerance in voxel edges, default 3)\n";
         return 0;
     }
     const int choose = parser.i("c");
@@ -331,10 +333,24 @@ int main(int argc, char *argv[]) {
             std::cerr << "You need to select a predefined color reconstruction mode. (--color)";
             return 1;
         }
+        // -visible (an extension beyond the reference): the vote over the views in which each
+        // voxel is visible, depth tolerance -visibleTol voxel edges
+        const bool visible = parser.b("visible");
+        const float tol = parser.f("visibleTol");
         switch (color) {
             case 0: break;
-            case 1: arvx::reconstructClosestColor(in.intr, model, in.views); break;
-            case 2: arvx::reconstructAvgColor(in.intr, model, in.views); break;
+            case 1:
+                if (visible)
+                    arvx::reconstructClosestColorVisible(in.intr, model, in.views, tol);
+                else
+                    arvx::reconstructClosestColor(in.intr, model, in.views);
+                break;
+            case 2:
+                if (visible)
+                    arvx::reconstructAvgColorVisible(in.intr, model, in.views, tol);
+                else
+                    arvx::reconstructAvgColor(in.intr, model, in.views);
+                break;
             default: std::cerr << "Ups, something went wrong!" << std::endl;
         }
         model.handleUnseen();
