@@ -55,6 +55,7 @@ SYMBOLS = [
     "arvx_mc_cells", "arvx_mc_cells_download", "arvx_mc_mesh", "arvx_mc_mesh_download",
     "arvx_mc_mesh_download_faces", "arvx_mc_mesh_welded", "arvx_mc_mesh_welded_download",
     "arvx_mc_mesh_smooth", "arvx_mc_mesh_smooth_download",
+    "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
     "arvx_export_model", "arvx_get_stats", "arvx_selftest_divide", "arvx_selftest_round",
@@ -186,6 +187,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "arvx_photo_carve"):
         lib.arvx_photo_carve.argtypes = [p, C.c_float, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int),
                                          C.POINTER(C.c_int64)]
+    if hasattr(lib, "arvx_render"):
+        lib.arvx_render.argtypes = [p, f32p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+        lib.arvx_render_view.argtypes = [p, C.c_int]
+        lib.arvx_render_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.arvx_render_agreement.argtypes = [p, C.c_int, C.POINTER(C.c_int64)]
     for name in SYMBOLS:
         if ab_build and not hasattr(lib, name):
             continue
@@ -726,6 +732,48 @@ class Context:
         self._ck(self._lib.arvx_mc_mesh_smooth_download(
             self._h, v.ctypes.data if v is not None else None, n.ctypes.data if n is not None else None))
         return v, n
+
+    def render(self, M, W: int, H: int, background=None, download: bool = True):
+        """arvx_render: the welded mesh's vertex voxels drawn into the camera M (3 x 4, world ->
+        pixel) on a W x H image, over `background` ((H, W, 3) uint8 BGR, rows may be padded) or
+        black: (bgr (H, W, 3) uint8, depth (H, W) float32, id (H, W) int32 -- the index into the
+        welded vertex list, -1 where no voxel covers the pixel).  download=False: the call only."""
+        M = _f32(M).reshape(12)
+        bg, stride = None, 0
+        if background is not None:
+            bg = np.asarray(background)
+            assert bg.dtype == np.uint8 and bg.shape == (H, W, 3) and bg.strides[1:] == (3, 1)
+            stride = bg.strides[0]
+        self._ck(self._lib.arvx_render(self._h, _fp(M), int(W), int(H),
+                                       bg.ctypes.data if bg is not None else None, stride))
+        self._render_wh = (int(W), int(H))
+        return self.render_download() if download else None
+
+    def render_view(self, view: int, download: bool = True):
+        """arvx_render_view: render() with the camera and image size of the context's view `view`
+        and no background."""
+        self._ck(self._lib.arvx_render_view(self._h, int(view)))
+        self._render_wh = (self.W, self.H)
+        return self.render_download() if download else None
+
+    def render_download(self, bgr: bool = True, depth: bool = True, id: bool = True):
+        """arvx_render_download: (bgr, depth, id) of the last render, each an array or None."""
+        W, H = getattr(self, "_render_wh", (0, 0))
+        b = np.empty((H, W, 3), np.uint8) if bgr else None
+        d = np.empty((H, W), np.float32) if depth else None
+        i = np.empty((H, W), np.int32) if id else None
+        self._ck(self._lib.arvx_render_download(self._h, *(a.ctypes.data if a is not None else None
+                                                           for a in (b, d, i))))
+        return b, d, i
+
+    def render_agreement(self, view: int) -> Tuple[int, int, int]:
+        """arvx_render_agreement: renders view `view` (it becomes the current render) and counts its
+        pixels against the view's mask: (both: covered and foreground, model_only: covered and
+        background, mask_only: uncovered and foreground)."""
+        counts = (C.c_int64 * 3)()
+        self._ck(self._lib.arvx_render_agreement(self._h, int(view), counts))
+        self._render_wh = (self.W, self.H)
+        return int(counts[0]), int(counts[1]), int(counts[2])
 
     def mc_mesh_count(self, apply_unseen: bool = False) -> int:
         """arvx_mc_mesh without the download: the triangles stay on the device."""

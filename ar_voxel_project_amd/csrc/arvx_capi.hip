@@ -36,6 +36,7 @@
 #include "mc_smooth_kernels.h"
 #include "visibility_kernels.h"
 #include "photo_kernels.h"
+#include "render_kernels.h"
 #include "exchange_kernels.h"
 #include <algorithm>
 
@@ -446,12 +447,14 @@ int arvx_ctx_create_slab_halo(arvx_ctx **out, int device, int X, int Y, int Z, f
     // Coherent: without the flag a mapped allocation is non-coherent host memory -- the device's stores
     // to it need not be seen by a host that has the line in its cache (the totals' words are reset by
     // the host before every launch: a call then read its own -1 back, once in a few hundred calls)
-    e = hipHostMalloc((void **)&c->h_fault, 64, hipHostMallocMapped | hipHostMallocCoherent);
+    e = hipHostMalloc((void **)&c->h_fault, 128, hipHostMallocMapped | hipHostMallocCoherent);
     if (e == hipSuccess) {
-        memset(c->h_fault, 0, 64);
+        memset(c->h_fault, 0, 128);
         e = hipHostGetDevicePointer((void **)&c->d_fault, c->h_fault, 0);
         c->h_totals = (long long *)(c->h_fault + 2);  // six 8-byte words behind the fault word
         c->d_totals_host = (long long *)(c->d_fault + 2);
+        c->h_render = (long long *)(c->h_fault + 16);  // arvx_render's four words, in the second line
+        c->d_render_host = (long long *)(c->d_fault + 16);
     }
     if (e != hipSuccess) {
         arvx_ctx_destroy(c);
@@ -2969,6 +2972,7 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     ctx->free_mc();
     ctx->weld_ready = false;
     ctx->smooth_ready = ctx->smooth_csr_ready = false;  // (a new mesh: new CSRs)
+    ctx->render_ready = false;                           // (... and the old one's render goes)
     ctx->weld_verts = ctx->weld_tris = 0;
     *vertices = *triangles = 0;
     // the vertex plane: occupied voxels with an empty 6-neighbour, in the occupancy the cell walk
@@ -3179,6 +3183,166 @@ int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals) {
     if (int rc = check_fault(ctx)) {  // (a scan gave up: the CSRs are built again)
         ctx->smooth_ready = ctx->smooth_csr_ready = false;
         return rc;
+    }
+    return ARVX_OK;
+}
+
+// ---- render (render_kernels.h) ------------------------------------------------------------
+
+// the images' places in pool_render_img: id | depth | bgr
+static int *render_id(const Ctx *ctx) { return (int *)ctx->pool_render_img.p; }
+static float *render_depth(const Ctx *ctx) {
+    return (float *)ctx->pool_render_img.p + (size_t)ctx->render_W * ctx->render_H;
+}
+static uint8_t *render_bgr(const Ctx *ctx) {
+    return (uint8_t *)ctx->pool_render_img.p + (size_t)ctx->render_W * ctx->render_H * 8;
+}
+
+// The refusals every render call shares, then the camera's own.
+static int render_refusals(const Ctx *ctx, const float *M, int W, int H) {
+    if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
+    if (!M) return fail(ARVX_ERR_INVALID, "null M");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(M[k])) return fail(ARVX_ERR_INVALID, "M[%d] is not finite", k);
+    if (W < 1 || H < 1 || W > arvx::kMaxImageDim || H > arvx::kMaxImageDim)
+        return fail(ARVX_ERR_INVALID, "image size %dx%d out of range", W, H);
+    return ARVX_OK;
+}
+
+// Clear, background, splat, large footprints, resolve: launches only.  The caller has refused what
+// is to be refused; a failure in here leaves no render.
+static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *background, size_t bg_stride) {
+    ctx->render_ready = false;
+    const size_t npix = (size_t)W * H;
+    const long long n = ctx->weld_verts;
+    ARVX_HIP(ctx->pool_render_keys.reserve(npix * sizeof(unsigned long long)));
+    ARVX_HIP(ctx->pool_render_img.reserve(npix * 11));
+    // large footprints: room for what a render wanted to list (an eighth more), at least a quarter
+    // of the vertices and 64 Ki more, never more than there are vertices; what does not fit is
+    // swept by the splat's own waves, so the capacity changes the time and never the images.
+    // render_need is the page-locked word as it stood at the last synchronisation of a render call
+    // (arvx_render_download, arvx_render_agreement): renders launched back to back without one all
+    // use the same capacity, whatever the device has finished by then.
+    const long long need = ctx->render_need;
+    const long long want = std::max((1ll << 16) + n / 4, need + need / 8);
+    const unsigned large_cap = (unsigned)std::min<long long>({n, want, (long long)UINT32_MAX});
+    ARVX_HIP(ctx->pool_render_large.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
+    ctx->render_W = W;
+    ctx->render_H = H;
+    unsigned long long *keys = (unsigned long long *)ctx->pool_render_keys.p;
+    arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
+    arvx::SplatRect *large = (arvx::SplatRect *)((uint8_t *)ctx->pool_render_large.p + 64);
+    const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
+    hipLaunchKernelGGL(arvx::render_clear_kernel, dim3((unsigned)std::min<size_t>((npix + 255) / 256, 8 * ncu)),
+                       dim3(256), 0, ctx->stream, keys, npix, head);
+    ARVX_HIP(hipGetLastError());
+    // the background: the caller's rows, packed in the staging buffer, or zeros
+    if (background) {
+        if (!ctx->render_bg_done) ARVX_HIP(hipEventCreateWithFlags(&ctx->render_bg_done, hipEventDisableTiming));
+        else ARVX_HIP(hipEventSynchronize(ctx->render_bg_done));  // (the last copy out of the buffer)
+        if (ctx->render_bg_cap < npix * 3) {
+            if (ctx->h_render_bg) (void)hipHostFree(ctx->h_render_bg);
+            ctx->h_render_bg = nullptr;
+            ctx->render_bg_cap = 0;
+            ARVX_HIP(hipHostMalloc((void **)&ctx->h_render_bg, npix * 3, hipHostMallocDefault));
+            ctx->render_bg_cap = npix * 3;
+        }
+        for (int r = 0; r < H; ++r)
+            memcpy(ctx->h_render_bg + (size_t)r * W * 3, background + (size_t)r * bg_stride, (size_t)W * 3);
+        ARVX_HIP(hipMemcpyAsync(render_bgr(ctx), ctx->h_render_bg, npix * 3, hipMemcpyHostToDevice, ctx->stream));
+        ARVX_HIP(hipEventRecord(ctx->render_bg_done, ctx->stream));
+    } else {
+        ARVX_HIP(hipMemsetAsync(render_bgr(ctx), 0, npix * 3, ctx->stream));
+    }
+    if (n > 0) {
+        arvx::RenderSplatParams sp;
+        sp.index = (const int *)ctx->pool_weld_index.p;
+        sp.n = n;
+        sp.X = ctx->X;
+        sp.Y = ctx->Y;
+        sp.s = ctx->s;
+        sp.W = W;
+        sp.H = H;
+        memcpy(sp.M.m, M, 12 * sizeof(float));
+        sp.keys = keys;
+        sp.large = large;
+        sp.n_large = &head->n_large;
+        sp.large_cap = large_cap;
+        // (the grid strides over the list)
+        const dim3 sgrid((unsigned)std::min<long long>((n + 255) / 256, 8 * ncu));
+        if (ctx->assoc == ARVX_ASSOC_LEFT)
+            hipLaunchKernelGGL(arvx::render_splat_kernel<true>, sgrid, dim3(256), 0, ctx->stream, sp);
+        else
+            hipLaunchKernelGGL(arvx::render_splat_kernel<false>, sgrid, dim3(256), 0, ctx->stream, sp);
+        ARVX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(arvx::render_splat_large_kernel, dim3((unsigned)(4 * ncu)), dim3(256), 0, ctx->stream,
+                           (const arvx::SplatRect *)large, (const unsigned *)&head->n_large, large_cap, keys, W,
+                           ctx->d_render_host);
+        ARVX_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(arvx::render_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
+                       ctx->stream, (const unsigned long long *)keys, npix, (const float *)ctx->pool_weld_rgb.p,
+                       render_id(ctx), render_depth(ctx), render_bgr(ctx));
+    ARVX_HIP(hipGetLastError());
+    ctx->render_ready = true;
+    return ARVX_OK;
+}
+
+int arvx_render(arvx_ctx *ctx, const float M[12], int W, int H, const uint8_t *background, size_t bg_stride) {
+    ARVX_CHECK_CTX(ctx);
+    if (int rc = render_refusals(ctx, M, W, H)) return rc;
+    if (background && bg_stride < (size_t)W * 3) return fail(ARVX_ERR_INVALID, "bg_stride %zu < 3 * W", bg_stride);
+    return render_launch(ctx, M, W, H, background, bg_stride);
+}
+
+// arvx_render_view's refusals (arvx_render_agreement adds its own after them)
+static int render_view_refusals(const Ctx *ctx, int view) {
+    if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
+    if (!ctx->cameras_ready) return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
+    if (view < 0 || view >= ctx->V) return fail(ARVX_ERR_INVALID, "view %d outside [0,%d)", view, ctx->V);
+    return render_refusals(ctx, ctx->h_M.data() + 12 * (size_t)view, ctx->W, ctx->H);
+}
+
+int arvx_render_view(arvx_ctx *ctx, int view) {
+    ARVX_CHECK_CTX(ctx);
+    if (int rc = render_view_refusals(ctx, view)) return rc;
+    return render_launch(ctx, ctx->h_M.data() + 12 * (size_t)view, ctx->W, ctx->H, nullptr, 0);
+}
+
+int arvx_render_download(arvx_ctx *ctx, uint8_t *bgr, float *depth, int32_t *id) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->render_ready) return fail(ARVX_ERR_STATE, "no render (call arvx_render)");
+    const size_t npix = (size_t)ctx->render_W * ctx->render_H;
+    if (bgr) ARVX_HIP(hipMemcpyAsync(bgr, render_bgr(ctx), npix * 3, hipMemcpyDeviceToHost, ctx->stream));
+    if (depth)
+        ARVX_HIP(hipMemcpyAsync(depth, render_depth(ctx), npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (id) ARVX_HIP(hipMemcpyAsync(id, render_id(ctx), npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    ctx->render_need = std::max(ctx->h_render[0], 0ll);
+    return ARVX_OK;
+}
+
+int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]) {
+    ARVX_CHECK_CTX(ctx);
+    if (int rc = render_view_refusals(ctx, view)) return rc;
+    if (!ctx->views_ready) return fail(ARVX_ERR_STATE, "arvx_set_views was given no masks");
+    if (!counts) return fail(ARVX_ERR_INVALID, "null counts");
+    if (int rc = render_launch(ctx, ctx->h_M.data() + 12 * (size_t)view, ctx->W, ctx->H, nullptr, 0)) return rc;
+    const size_t npix = (size_t)ctx->W * ctx->H;
+    arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
+    for (int k = 1; k <= 3; ++k) ctx->h_render[k] = -1;
+    hipLaunchKernelGGL(arvx::render_agreement_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
+                       ctx->stream, (const int *)render_id(ctx), npix,
+                       (const uint32_t *)(ctx->bg() + (size_t)view * ctx->bgWords), head->counts);
+    ARVX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(arvx::render_counts_out_kernel, dim3(1), dim3(64), 0, ctx->stream,
+                       (const unsigned long long *)head->counts, ctx->d_render_host + 1);
+    ARVX_HIP(hipGetLastError());
+    ARVX_SYNC(ctx);
+    ctx->render_need = std::max(ctx->h_render[0], 0ll);
+    for (int k = 0; k < 3; ++k) {
+        if (ctx->h_render[k + 1] < 0) return fail(ARVX_ERR_HIP, "the agreement left no count");
+        counts[k] = ctx->h_render[k + 1];
     }
     return ARVX_OK;
 }

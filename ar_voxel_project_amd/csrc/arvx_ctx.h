@@ -214,30 +214,32 @@ struct Ctx {
     // calls drop() once, after its refusals and before its work, so that a refused call leaves the
     // context as it was.  (The closure calls it where its fills go into the state: the colour pass's
     // planes it starts from are those of the state before.)  The mesh products (mc_ready,
-    // weld_ready, smooth_*) are not here: each lives until the next call of its own stage.
+    // weld_ready, smooth_*) are not here: each lives until the next call of its own stage.  The
+    // render of the welded mesh (arvx_render) is: it shows the state the mesh was built from, so
+    // whatever replaces that state drops it (and so does the next arvx_mc_mesh_welded).
     enum class Event {
         SetViews, SetImages, Color, UploadColors, ProjectionAssoc, HandleUnseen, Closure,
         Carve, FastCarve, UploadState, UploadPlanes, UploadHalo, Reset, PhotoCarve
     };
     void drop(Event e) {
-        struct Row { uint8_t colours, closure, fills, paint, cstate, state; };
+        struct Row { uint8_t colours, closure, fills, paint, cstate, state, render; };
         static constexpr Row kRows[] = {
-            //                    colour closure closure paint cstate state
+            //                    colour closure closure paint cstate state   render
             //                    list   list    fills         tiles  changes
-            /* SetViews        */ {1,    1,      0,      0,    0,     0},
-            /* SetImages       */ {1,    1,      0,      0,    0,     0},
-            /* Color           */ {1,    1,      0,      0,    0,     0},
-            /* UploadColors    */ {1,    1,      0,      0,    0,     0},
-            /* ProjectionAssoc */ {1,    0,      0,      0,    0,     0},  // (a change of grouping)
-            /* HandleUnseen    */ {0,    1,      0,      0,    0,     2},
-            /* Closure         */ {0,    1,      0,      0,    1,     1},
-            /* Carve           */ {1,    1,      1,      1,    0,     1},
-            /* FastCarve       */ {1,    1,      1,      1,    0,     1},
-            /* UploadState     */ {1,    1,      1,      2,    1,     1},
-            /* UploadPlanes    */ {1,    1,      1,      1,    1,     1},
-            /* UploadHalo      */ {1,    1,      1,      0,    1,     1},
-            /* Reset           */ {1,    1,      1,      1,    1,     1},
-            /* PhotoCarve      */ {1,    1,      1,      1,    0,     1},
+            /* SetViews        */ {1,    1,      0,      0,    0,     0,      0},
+            /* SetImages       */ {1,    1,      0,      0,    0,     0,      0},
+            /* Color           */ {1,    1,      0,      0,    0,     0,      0},
+            /* UploadColors    */ {1,    1,      0,      0,    0,     0,      0},
+            /* ProjectionAssoc */ {1,    0,      0,      0,    0,     0,      0},  // (a change of grouping)
+            /* HandleUnseen    */ {0,    1,      0,      0,    0,     2,      0},
+            /* Closure         */ {0,    1,      0,      0,    1,     1,      0},
+            /* Carve           */ {1,    1,      1,      1,    0,     1,      1},
+            /* FastCarve       */ {1,    1,      1,      1,    0,     1,      1},
+            /* UploadState     */ {1,    1,      1,      2,    1,     1,      1},
+            /* UploadPlanes    */ {1,    1,      1,      1,    1,     1,      1},
+            /* UploadHalo      */ {1,    1,      1,      0,    1,     1,      1},
+            /* Reset           */ {1,    1,      1,      1,    1,     1,      1},
+            /* PhotoCarve      */ {1,    1,      1,      1,    0,     1,      1},
         };
         // paint 2: the owned planes' paint is replaced; the plane stays where halo planes keep
         // theirs.  state 2: only never-seen voxels become occupied (next_state).  cstate: a call
@@ -253,6 +255,7 @@ struct Ctx {
         if (r.paint == 1 || (r.paint == 2 && nvox_ext == nvox)) paint_valid = false;
         if (r.cstate) cstate_tiles = 0;
         if (r.state) next_state(r.state == 2);
+        if (r.render) render_ready = false;
     }
     // The state changes: whatever carries the old count as its stamp is stale -- but for
     // handleUnseen (unseen_only) the colour pass's planes of the state before stay usable: its
@@ -287,8 +290,28 @@ struct Ctx {
     bool smooth_csr_ready = false, smooth_ready = false;
     int smooth_q = 0;  // where the smoothed positions are: 0 the welded mesh's, 1 / 2 a buffer
 
+    // arvx_render: the W x H keys, the images (id | depth | bgr), the large-footprint list behind
+    // its header (render_kernels.h), all sized at first use and kept.  h_render: page-locked words
+    // behind the totals -- the large footprints the last render wanted to list, then the three
+    // agreement counts.  The first is copied to render_need at a render call's synchronisation
+    // (download, agreement) and sizes the next renders' lists from there; the word itself is never
+    // read while a kernel may be writing it.  A caller's background goes through a
+    // page-locked staging buffer: the copy out of it is not waited for, so the event after it is
+    // waited for before the buffer is written again.
+    DevPool pool_render_keys{DevPool::Exact}, pool_render_img{DevPool::Exact},
+        pool_render_large{DevPool::Exact};
+    int render_W = 0, render_H = 0;
+    bool render_ready = false;
+    long long *h_render = nullptr, *d_render_host = nullptr;  // 4 words (host / device address)
+    long long render_need = 0;
+    uint8_t *h_render_bg = nullptr;
+    size_t render_bg_cap = 0;
+    hipEvent_t render_bg_done = nullptr;
+
     // (the device buffers are freed by their DevPool members, after this)
     ~Ctx() {
+        if (render_bg_done) (void)hipEventDestroy(render_bg_done);
+        if (h_render_bg) (void)hipHostFree(h_render_bg);
         if (h_fault) (void)hipHostFree(h_fault);
     }
     void free_mc() {

@@ -545,6 +545,55 @@ int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, f
 int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu);
 int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals);
 
+/* ---- render (extension beyond the reference) -------------------------------------------------
+ * Draws the welded mesh's vertex voxels into a camera view: the model over a photograph, the voxel
+ * under a pixel, a carve checked against its own silhouettes.  Definition, on a whole-grid context
+ * that holds the mesh of the last arvx_mc_mesh_welded: its Vn vertex voxels k = 0 .. Vn-1 in
+ * ascending flat index, their colours col[k] (3 floats: what arvx_mc_mesh_welded_download returns
+ * as vertex_rgb), and the caller's camera: M, 12 fp32 values, row-major 3 x 4, world -> pixel, and
+ * the image size W x H, 1 <= W, H <= 16384 (the views' limit).  The camera has nothing to do with
+ * the context's views.
+ *  1. Footprint.  For vertex voxel k, steps 1 and 2 of arvx_color_visible's definition with
+ *     M, W, H in place of M_v, W, H (the same fp64 products of fp32 operands, the context's
+ *     row-sum grouping, IEEE fp32 quotients): the centre's a2, whether k splats, and its clipped
+ *     pixel rectangle, which may be empty.
+ *  2. Winner.  For pixel p, among the voxels that splat with p in their footprint, the one with
+ *     the lexicographically least (a2, k); there may be none.  a2 is a positive fp32, so the
+ *     winner is the minimum of the 64-bit words bits(a2) << 32 | k: the order in which voxels
+ *     arrive cannot change it.
+ *  3. Images, each H x W row-major:
+ *       id     int32: the winner's k (an index into the welded vertex list); -1 where there is none;
+ *       depth  fp32: the winner's a2; +inf where there is none;
+ *       bgr    u8, 3 channels, laid out like the input images: for the winner, channel
+ *              c = (uint8_t)roundf(fminf(fmaxf(col_c, 0.f), 255.f)), stored B, G, R; where there is
+ *              no winner, the pixel of the caller's background image if one was given, else
+ *              (0, 0, 0).
+ * Consequence: depth equals, bit for bit, the depth buffer Z of arvx_color_visible's step 3 computed
+ * over the same voxel set with the same camera.
+ * arvx_render takes the camera and an optional background (host memory, H rows of bg_stride >= 3 W
+ * bytes, BGR; it is copied before the call returns); arvx_render_view takes M_v, W, H of the
+ * context's view `view` and no background.  Neither synchronises; arvx_render_download does, and
+ * copies the tightly packed images out (any pointer may be null).  arvx_render_agreement renders
+ * view `view` as arvx_render_view does, leaves that render as the current one, and counts on the
+ * device, against the view's background bit plane (the one arvx_selftest_view_tables returns):
+ *   counts[0] = pixels covered and foreground, counts[1] = covered and background,
+ *   counts[2] = uncovered and foreground -- with ONE host synchronisation.
+ * An empty mesh (Vn == 0) renders the background.
+ * Refusals.  ARVX_ERR_STATE: no welded mesh (slab and striped contexts never have one);
+ * arvx_render_download before a render; arvx_render_view or arvx_render_agreement without views;
+ * arvx_render_agreement when the views were set with masks == NULL.  ARVX_ERR_INVALID: a null M or
+ * a non-finite entry of it, W or H out of range, bg_stride < 3 W, a view outside [0, V), null
+ * counts.  A refused call leaves the previous render as it was.
+ * The render lives until the next render, the next arvx_mc_mesh_welded, or a call that replaces the
+ * state the mesh was built from (carve, fast carve, photo carve, state upload, reset).  Device
+ * memory, sized at first use and kept: W * H * 8 bytes of keys, the three images (W * H * 11
+ * bytes) and the large-footprint list. */
+int arvx_render(arvx_ctx *ctx, const float M[12], int W, int H, const uint8_t *background,
+                size_t bg_stride);
+int arvx_render_view(arvx_ctx *ctx, int view);
+int arvx_render_download(arvx_ctx *ctx, uint8_t *bgr, float *depth, int32_t *id);
+int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]);
+
 /* Model::voxels as the reference would hold it after carve [+ colour]
  * [+ handleUnseen]: n*4 floats (RGBA), n = slab voxels. */
 int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen);

@@ -380,6 +380,54 @@ inline bool marchingCubesWelded(Model *model, float scale = 1.0f, Vec3f translat
                                         [](Model *m, float t) { return marchingCubesMeshWelded(m, t); });
 }
 
+// ---- render (an extension beyond the reference) -------------------------------------------------
+//
+// The welded mesh's vertex voxels drawn into a camera view on the device (arvx_render, defined in
+// include/arvx/arvx.h): M is the camera, row-major 3 x 4, world -> pixel; background, if given, is
+// a tightly packed H x W BGR image that shows where no voxel covers a pixel.  id holds indices into
+// the welded mesh's vertex list (-1: none), depth the winner's a2 (+inf: none).
+struct RenderedView {
+    std::vector<uint8_t> bgr;
+    std::vector<float> depth;
+    std::vector<int32_t> id;
+    int W = 0, H = 0;
+};
+
+// Renders the welded mesh the model's context holds; builds it first (as marchingCubesMeshWelded
+// does) ONLY if the context has none.  The context's welded mesh lives until the next welded mesh
+// is built, not until the model changes: after marchingCubesMeshWelded, a carve, handleUnseen, a
+// closure or a new colouring leaves it in place, and this call then draws that older mesh (ids and
+// colours are those of that mesh, which is what its downloaded arrays hold).  To draw the model as
+// it now is, call marchingCubesMeshWelded again first.  A model with fractional w has no welded
+// mesh on the device: the call throws.
+inline RenderedView renderWelded(Model *model, const float M[12], int W, int H,
+                                 const uint8_t *background = nullptr) {
+    arvx_ctx *ctx = model->device_for_reading();
+    const size_t stride = (size_t)(W > 0 ? W : 0) * 3;
+    int rc = arvx_render(ctx, M, W, H, background, stride);
+    if (rc == ARVX_ERR_STATE) {  // no welded mesh yet
+        bool on_device = false;
+        (void)model->inside_state(0.5f, on_device);
+        if (on_device) {
+            int apply_unseen = 0;
+            ctx = detail::mesh_context(model, apply_unseen);
+            int64_t nv = 0, nt = 0;
+            detail::check(arvx_mc_mesh_welded(ctx, apply_unseen, &nv, &nt), "arvx_mc_mesh_welded");
+            rc = arvx_render(ctx, M, W, H, background, stride);
+        }
+    }
+    detail::check(rc, "arvx_render");
+    RenderedView out;
+    out.W = W;
+    out.H = H;
+    out.bgr.resize((size_t)W * H * 3);
+    out.depth.resize((size_t)W * H);
+    out.id.resize((size_t)W * H);
+    detail::check(arvx_render_download(ctx, out.bgr.data(), out.depth.data(), out.id.data()),
+                  "arvx_render_download");
+    return out;
+}
+
 // ---- smoothed mesh (an extension beyond the reference) ------------------------------------------
 //
 // The definition of arvx_mc_mesh_smooth (include/arvx/arvx.h) applied to any welded mesh on the

@@ -166,6 +166,55 @@ bool load_poses(const std::string &path, std::vector<arvx::View> &views) {
     return true;
 }
 
+// -render=DIR: DIR/render%04d.ppm per view, and one line per view with the agreement counts
+bool render_views(const std::string &dir, const Inputs &in, arvx::Model &model) {
+    fs::create_directories(dir);
+    const int V = (int)in.views.size();
+    std::vector<uint8_t> bg, rgb;
+    for (int i = 0; i < V; ++i) {
+        const arvx::View &v = in.views[i];
+        float M[12];
+        if (v.has_M)
+            std::memcpy(M, v.M, sizeof M);
+        else
+            arvx::detail::check(arvx_compose_projection(in.intr.K, v.pose, M), "arvx_compose_projection");
+        const arvx::Image &im = v.image.data ? v.image : v.mask;
+        const int W = im.width, H = im.height;
+        const bool over = v.image.data && v.image.channels == 3;
+        if (over) {  // (tightly packed rows)
+            bg.resize((size_t)W * H * 3);
+            for (int r = 0; r < H; ++r)
+                std::memcpy(bg.data() + (size_t)r * W * 3, im.data + (size_t)r * im.stride, (size_t)W * 3);
+        }
+        const arvx::RenderedView out = arvx::renderWelded(&model, M, W, H, over ? bg.data() : nullptr);
+        rgb.resize(out.bgr.size());
+        for (size_t p = 0; p < out.bgr.size(); p += 3) {
+            rgb[p] = out.bgr[p + 2];
+            rgb[p + 1] = out.bgr[p + 1];
+            rgb[p + 2] = out.bgr[p];
+        }
+        char name[32];
+        std::snprintf(name, sizeof name, "render%04d.ppm", i);
+        std::ofstream f((fs::path(dir) / name).string(), std::ios::binary);
+        f << "P6\n" << W << " " << H << "\n255\n";
+        f.write((const char *)rgb.data(), (std::streamsize)rgb.size());
+        if (!f) {
+            std::cerr << "Could not write " << name << " (--render)" << std::endl;
+            return false;
+        }
+    }
+    // the masks again (the colour pass took the cameras only); the context's colour list goes
+    arvx_ctx *ctx = arvx::detail::bind_views(in.intr, model, in.views, false);
+    model.set_colors_on_device(false);
+    for (int i = 0; i < V; ++i) {
+        int64_t n[3];
+        arvx::detail::check(arvx_render_agreement(ctx, i, n), "arvx_render_agreement");
+        std::cout << "LOG - RENDER: view " << i << " both " << n[0] << " model_only " << n[1] << " mask_only "
+                  << n[2] << std::endl;
+    }
+    return true;
+}
+
 }  // namespace
 
 int main(int argc, char *argv[]) {
@@ -179,7 +228,7 @@ int main(int argc, char *argv[]) {
         {"dy", "0.0"}, {"dz", "0.0"}, {"model_debug", "false"}, {"postprocessing", "true"},
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
-        {"photoIters", "32"}};
+        {"photoIters", "32"}, {"render", ""}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -193,7 +242,9 @@ int main(int argc, char *argv[]) {
                      "  -photo=T (after carving: remove surface voxels whose visible views' colours\n"
                      "    differ by a summed channel standard deviation above T; 0, the default: off),\n"
                      "  -photoViews=N (views a voxel must be visible in to be judged, default 2),\n"
-                     "  -photoIters=N (sweeps at most, default 32; depth tolerance: -visibleTol)\n";
+                     "  -photoIters=N (sweeps at most, default 32; depth tolerance: -visibleTol),\n"
+                     "  -render=DIR (after the mesh: the welded model drawn over every input image,\n"
+                     "    DIR/renderNNNN.ppm, and its agreement with every mask)\n";
         return 0;
     }
     const int choose = parser.i("c");
@@ -378,6 +429,9 @@ int main(int argc, char *argv[]) {
                                       parser.str("outFile"));
         else
             arvx::marchingCubes(&model, parser.f("scale"), modelTranslation, 0.5f, parser.str("outFile"));
+        // -render=DIR (an extension beyond the reference): the welded mesh's vertex voxels drawn
+        // into every view over its input image, then each render's agreement with the view's mask
+        if (!parser.str("render").empty() && !render_views(parser.str("render"), in, model)) return 1;
     } catch (const arvx::Error &e) {
         return 3;  // (already logged)
     }
