@@ -24,6 +24,8 @@ CARVE_FUSED = 8
 CARVE_STREAM = 16
 CARVE_FILTER = 64
 CARVE_NO_STREAM = 32
+VOTES_COUNTS = 1
+VOTES_NO_CULL = 2
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
 # whole test module with the streaming carve forced on every fresh model (the library itself reads
 # no environment variable)
@@ -49,7 +51,7 @@ SYMBOLS = [
     "arvx_color", "arvx_surface_count", "arvx_surface_download",
     "arvx_surface_depth_download", "arvx_color_samples",
     "arvx_color_visible", "arvx_surface_visible_download", "arvx_view_depth_download",
-    "arvx_photo_carve",
+    "arvx_photo_carve", "arvx_carve_votes", "arvx_votes_download",
     "arvx_colors_upload", "arvx_closure", "arvx_closure_count", "arvx_closure_download",
     "arvx_closure_download32",
     "arvx_mc_cells", "arvx_mc_cells_download", "arvx_mc_mesh", "arvx_mc_mesh_download",
@@ -187,6 +189,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "arvx_photo_carve"):
         lib.arvx_photo_carve.argtypes = [p, C.c_float, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int),
                                          C.POINTER(C.c_int64)]
+    if hasattr(lib, "arvx_carve_votes"):
+        lib.arvx_carve_votes.argtypes = [p, C.c_int, C.c_uint]
+        lib.arvx_votes_download.argtypes = [p, C.c_void_p, C.c_void_p]
     if hasattr(lib, "arvx_render"):
         lib.arvx_render.argtypes = [p, f32p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         lib.arvx_render_view.argtypes = [p, C.c_int]
@@ -582,6 +587,22 @@ class Context:
         self._ck(self._lib.arvx_photo_carve(self._h, float(max_std), int(min_views), float(tolerance),
                                             int(max_iterations), C.byref(it), C.byref(removed)))
         return it.value, removed.value
+
+    def carve_votes(self, max_misses: int, counts: bool = False, cull: bool = True) -> None:
+        """arvx_carve_votes: empties the voxels that more than max_misses views see as background
+        (max_misses = 0: the plain carve).  counts: keep the per-voxel counts for votes(); cull =
+        False: project every voxel in every view."""
+        flags = (VOTES_COUNTS if counts else 0) | (0 if cull else VOTES_NO_CULL)
+        self._ck(self._lib.arvx_carve_votes(self._h, int(max_misses), flags))
+
+    def votes(self) -> Tuple[np.ndarray, np.ndarray]:
+        """arvx_votes_download: (background, inside), uint16 per voxel in flat index order -- the views
+        that see the voxel as background / whose image it projects into, of the last
+        carve_votes(..., counts=True)."""
+        bg = np.empty(self.nvox, np.uint16)
+        inside = np.empty(self.nvox, np.uint16)
+        self._ck(self._lib.arvx_votes_download(self._h, bg.ctypes.data, inside.ctypes.data))
+        return bg, inside
 
     def surface_visible(self) -> np.ndarray:
         """arvx_surface_visible_download: views each coloured voxel is visible in (surface()'s

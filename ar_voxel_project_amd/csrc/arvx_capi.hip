@@ -36,6 +36,7 @@
 #include "mc_smooth_kernels.h"
 #include "visibility_kernels.h"
 #include "photo_kernels.h"
+#include "vote_kernels.h"
 #include "render_kernels.h"
 #include "exchange_kernels.h"
 #include <algorithm>
@@ -1719,6 +1720,78 @@ int arvx_carve_views(arvx_ctx *ctx, int first, int count, unsigned flags) {
 int arvx_carve(arvx_ctx *ctx, unsigned flags) {
     if (!ctx) return fail(ARVX_ERR_INVALID, "null context");
     return arvx_carve_views(ctx, 0, ctx->V, flags);
+}
+
+// ---- vote carve (vote_kernels.h) ----------------------------------------------------------------
+
+int arvx_carve_votes(arvx_ctx *ctx, int max_misses, unsigned flags) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->views_ready) return fail(ARVX_ERR_STATE, "arvx_set_views (with masks) has not been called");
+    if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
+        return fail(ARVX_ERR_STATE, "arvx_carve_votes needs a whole-grid context");
+    if (max_misses < 0 || max_misses > 65535)
+        return fail(ARVX_ERR_INVALID, "max_misses %d: must be in [0, 65535]", max_misses);
+    if (ctx->V > 65535) return fail(ARVX_ERR_INVALID, "%d views: the counts are 16 bits wide", ctx->V);
+    if (flags & ~(ARVX_VOTES_COUNTS | ARVX_VOTES_NO_CULL))
+        return fail(ARVX_ERR_INVALID, "unknown flag bits 0x%x", flags & ~(ARVX_VOTES_COUNTS | ARVX_VOTES_NO_CULL));
+    const size_t half = (ctx->nvox * sizeof(uint16_t) + 255) / 256 * 256;
+    if (flags & ARVX_VOTES_COUNTS) ARVX_HIP(ctx->pool_votes.reserve(2 * half));
+    // A carve as far as the context's other results go: the call only empties voxels and sets seen
+    // bits, so what earlier carves settled for whole coarse tiles (cstate: all carved and seen / all
+    // seen) stays true and is kept, as arvx_carve keeps it.
+    ctx->drop(Event::Carve);
+    const bool fresh = ctx->form == Form::Fresh;
+    if (fresh) {  // the kernel writes every record of the grid; nothing is read
+        if (int rc = ensure_records(ctx, ctx->pool_rec)) return rc;
+    } else if (int rc = need_rec(ctx)) {  // (a lazily coded state is written out first)
+        return rc;
+    }
+    ctx->form = Form::Records;
+    arvx::VoteCarveParams q;
+    arvx::CarveParams &p = q.g;
+    carve_geometry(ctx, p);
+    p.rec = ctx->rec();
+    p.ccode = nullptr;
+    p.M = ctx->M();
+    p.bg = ctx->bg();
+    p.sat = ctx->sat();
+    p.W = ctx->W;
+    p.H = ctx->H;
+    p.bgWords = ctx->bgWords;
+    p.satStride = ctx->satStride;
+    p.satW = ctx->satW;
+    p.v0 = 0;
+    p.v1 = ctx->V;
+    p.flags = fresh ? 4u : 0u;
+    q.bg = (flags & ARVX_VOTES_COUNTS) ? (uint16_t *)ctx->pool_votes.p : nullptr;
+    q.in = (flags & ARVX_VOTES_COUNTS) ? (uint16_t *)((uint8_t *)ctx->pool_votes.p + half) : nullptr;
+    q.max_misses = max_misses;
+    q.cull = (flags & ARVX_VOTES_NO_CULL) ? 0 : 1;
+    const size_t rows8 = ((size_t)p.tilesY * p.tilesZ + 7) / 8 * 8;
+    const unsigned grid = (unsigned)(rows8 * p.tilesX);
+    if (ctx->assoc == ARVX_ASSOC_LEFT)
+        hipLaunchKernelGGL(arvx::carve_votes_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, q);
+    else
+        hipLaunchKernelGGL(arvx::carve_votes_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, q);
+    ARVX_HIP(hipGetLastError());
+    ctx->votes_ready = (flags & ARVX_VOTES_COUNTS) != 0;
+    return ARVX_OK;
+}
+
+int arvx_votes_download(arvx_ctx *ctx, uint16_t *background, uint16_t *inside) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->votes_ready)
+        return fail(ARVX_ERR_STATE, "no counts: arvx_carve_votes with ARVX_VOTES_COUNTS has not run since the "
+                                    "state or the views were last replaced");
+    const size_t bytes = ctx->nvox * sizeof(uint16_t);
+    const size_t half = (bytes + 255) / 256 * 256;
+    if (background)
+        ARVX_HIP(hipMemcpyAsync(background, ctx->pool_votes.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (inside)
+        ARVX_HIP(hipMemcpyAsync(inside, (const uint8_t *)ctx->pool_votes.p + half, bytes, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
 }
 
 static int surf_host(Ctx *ctx);

@@ -194,6 +194,10 @@ struct Ctx {
     // arvx_photo_carve: the removal counter (64 bytes) before one removal word per 64 list entries;
     // the removal plane (bitplane_kernels.h layout)
     DevPool pool_photo_rm, pool_photo_plane{DevPool::Exact};
+    // arvx_carve_votes with ARVX_VOTES_COUNTS: the per-voxel counts, u16 each in flat index order --
+    // background, then (from the next 256-byte boundary) inside; read only while votes_ready is set
+    DevPool pool_votes{DevPool::Exact};
+    bool votes_ready = false;
 
     // closure (dilation) result: filled voxels, ascending index
     int *d_clo_index = nullptr;
@@ -222,24 +226,24 @@ struct Ctx {
         Carve, FastCarve, UploadState, UploadPlanes, UploadHalo, Reset, PhotoCarve
     };
     void drop(Event e) {
-        struct Row { uint8_t colours, closure, fills, paint, cstate, state, render; };
+        struct Row { uint8_t colours, closure, fills, paint, cstate, state, render, votes; };
         static constexpr Row kRows[] = {
-            //                    colour closure closure paint cstate state   render
+            //                    colour closure closure paint cstate state   render votes
             //                    list   list    fills         tiles  changes
-            /* SetViews        */ {1,    1,      0,      0,    0,     0,      0},
-            /* SetImages       */ {1,    1,      0,      0,    0,     0,      0},
-            /* Color           */ {1,    1,      0,      0,    0,     0,      0},
-            /* UploadColors    */ {1,    1,      0,      0,    0,     0,      0},
-            /* ProjectionAssoc */ {1,    0,      0,      0,    0,     0,      0},  // (a change of grouping)
-            /* HandleUnseen    */ {0,    1,      0,      0,    0,     2,      0},
-            /* Closure         */ {0,    1,      0,      0,    1,     1,      0},
-            /* Carve           */ {1,    1,      1,      1,    0,     1,      1},
-            /* FastCarve       */ {1,    1,      1,      1,    0,     1,      1},
-            /* UploadState     */ {1,    1,      1,      2,    1,     1,      1},
-            /* UploadPlanes    */ {1,    1,      1,      1,    1,     1,      1},
-            /* UploadHalo      */ {1,    1,      1,      0,    1,     1,      1},
-            /* Reset           */ {1,    1,      1,      1,    1,     1,      1},
-            /* PhotoCarve      */ {1,    1,      1,      1,    0,     1,      1},
+            /* SetViews        */ {1,    1,      0,      0,    0,     0,      0,      1},
+            /* SetImages       */ {1,    1,      0,      0,    0,     0,      0,      0},
+            /* Color           */ {1,    1,      0,      0,    0,     0,      0,      0},
+            /* UploadColors    */ {1,    1,      0,      0,    0,     0,      0,      0},
+            /* ProjectionAssoc */ {1,    0,      0,      0,    0,     0,      0,      1},  // (a change of grouping)
+            /* HandleUnseen    */ {0,    1,      0,      0,    0,     2,      0,      1},
+            /* Closure         */ {0,    1,      0,      0,    1,     1,      0,      1},
+            /* Carve           */ {1,    1,      1,      1,    0,     1,      1,      1},
+            /* FastCarve       */ {1,    1,      1,      1,    0,     1,      1,      1},
+            /* UploadState     */ {1,    1,      1,      2,    1,     1,      1,      1},
+            /* UploadPlanes    */ {1,    1,      1,      1,    1,     1,      1,      1},
+            /* UploadHalo      */ {1,    1,      1,      0,    1,     1,      1,      1},
+            /* Reset           */ {1,    1,      1,      1,    1,     1,      1,      1},
+            /* PhotoCarve      */ {1,    1,      1,      1,    0,     1,      1,      1},
         };
         // paint 2: the owned planes' paint is replaced; the plane stays where halo planes keep
         // theirs.  state 2: only never-seen voxels become occupied (next_state).  cstate: a call
@@ -247,6 +251,8 @@ struct Ctx {
         // tiles; carving and handleUnseen leave a tile that is carved and seen / seen as a whole
         // as it is.  Photo-consistency carving only empties voxels and keeps every seen bit: a tile
         // carved and seen as a whole stays empty, one seen as a whole stays seen -- both stay settled.
+        // votes: the counts of arvx_carve_votes describe the state that call left under the views and
+        // the grouping it ran with; whatever replaces one of them drops the counts.
         static_assert(sizeof kRows / sizeof kRows[0] == (size_t)Event::PhotoCarve + 1, "a row per event");
         const Row &r = kRows[(int)e];
         if (r.colours) color_ready = color_visible = false;
@@ -256,6 +262,7 @@ struct Ctx {
         if (r.cstate) cstate_tiles = 0;
         if (r.state) next_state(r.state == 2);
         if (r.render) render_ready = false;
+        if (r.votes) votes_ready = false;
     }
     // The state changes: whatever carries the old count as its stamp is stale -- but for
     // handleUnseen (unseen_only) the colour pass's planes of the state before stay usable: its

@@ -403,6 +403,40 @@ int arvx_view_depth_download(arvx_ctx *ctx, int view, float *depth);
  * arvx_color_visible, a removal plane of one bit per voxel and one bit per surface voxel. */
 int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float tolerance, int max_iterations,
                      int *iterations, int64_t *removed);
+/* ---- vote carve (extension beyond the reference) ----------------------------------------------
+ * The reference's carve empties a voxel at the first view whose mask pixel is background
+ * (src/VoxelCarving.cpp:50-54): exact for perfect silhouettes, and one patch missing from one
+ * segmentation drills a tunnel through the model along that camera's rays.  arvx_carve_votes
+ * counts the views instead and empties a voxel only above a tolerance.  Definition, on a whole-grid
+ * context, its state and its V views with masks:
+ *  1. For voxel i = (x, y, z) and view v the pixel is the carve's: M_v * toWord(x, y, z) with the
+ *     fp64 products of the fp32 operands, the row sums in the context's grouping
+ *     (arvx_ctx_set_projection_assoc) rounded to fp32, IEEE fp32 quotients, std::round.
+ *     inside_v(i) iff the pixel lies in the image; miss_v(i) iff inside_v(i) and all C bytes of the
+ *     mask pixel are 0.
+ *  2. in(i) = sum over v of inside_v(i), bg(i) = sum over v of miss_v(i).
+ *  3. occ'(i) = occ(i) && bg(i) <= max_misses; seen'(i) = seen(i) || in(i) >= 1.
+ * So arvx_carve_votes(ctx, 0, .) is arvx_carve(ctx, 0) bit for bit, and with max_misses >= V no
+ * voxel is emptied and only seen bits are set.  The flags change the work, never the state:
+ *   ARVX_VOTES_COUNTS   bg and in are kept on the device, u16 per voxel in flat index order, until
+ *                       the next call that replaces the state (carve, fast carve, photo carve,
+ *                       handleUnseen, closure, upload, reset), the views or the grouping.  Both are
+ *                       the full sums over all V views whatever max_misses is: no early exit is
+ *                       taken.  arvx_votes_download copies them out (either pointer may be null; it
+ *                       synchronises); without such counts it returns ARVX_ERR_STATE.
+ *   ARVX_VOTES_NO_CULL  every voxel is projected in every view: no rectangle test decides anything
+ *                       and nothing stops early (ablation, and the yardstick of the tests).
+ * Refusals: views missing or set with masks == NULL, a slab or a striped context (out of scope of
+ * this call for now: the multi-GPU drivers keep the plain carve): ARVX_ERR_STATE; max_misses < 0 or
+ * > 65535, more than 65535 views, unknown flag bits: ARVX_ERR_INVALID.  A refused call changes
+ * nothing.  The call does not synchronise, like arvx_carve.  It replaces the state as a carve does:
+ * it drops what arvx_photo_carve drops (see "What the context's results belong to", arvx_closure)
+ * and keeps what earlier carves settled for whole coarse tiles, since it only empties voxels and
+ * sets seen bits.  Device memory with ARVX_VOTES_COUNTS: 4 bytes per voxel, kept. */
+#define ARVX_VOTES_COUNTS 1u  /* keep the two per-voxel counts for arvx_votes_download */
+#define ARVX_VOTES_NO_CULL 2u /* project every voxel in every view (ablation, yardstick) */
+int arvx_carve_votes(arvx_ctx *ctx, int max_misses, unsigned flags);
+int arvx_votes_download(arvx_ctx *ctx, uint16_t *background, uint16_t *inside);
 /* The per-voxel colour lists behind the vote -- what the reference's voxel_pass appends with
  * Model::addColor (src/ColorReconstruction.h:44-60, src/Model.h:142-149) and getColors returns:
  * for each of n voxels (flat index over the context's own planes, any order) V samples in view

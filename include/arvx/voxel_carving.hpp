@@ -2,6 +2,9 @@
 // GPU library (header only, C++17, links libarvx.so).
 //
 //   carve(...)                    reference src/VoxelCarving.h:19,  .cpp:60-72
+//   carveVotes(...)               an extension beyond the reference: carve() that empties a voxel
+//                                 only when more than max_misses views see it as background
+//                                 (arvx_carve_votes)
 //   fastCarve(...)                reference src/VoxelCarving.h:31,  .cpp:74-167
 //   reconstructClosestColor(...)  reference src/ColorReconstruction.h:131, .cpp:22-46
 //   reconstructAvgColor(...)      reference src/ColorReconstruction.h:142, .cpp:48-70
@@ -182,6 +185,22 @@ inline void carve(const Intrinsics &intr, Model &model, const std::vector<View> 
             }
         }
     }
+    detail::check(arvx_ctx_synchronize(ctx), "arvx_ctx_synchronize");
+    detail::timing(kStageCarving, false);
+    std::cout << "LOG - VC: carving complete." << std::endl;
+}
+
+// Extension beyond the reference: the vote carve (arvx_carve_votes).  carve() empties a voxel at the
+// first view whose mask calls its pixel background, so one patch missing from one segmentation
+// drills a tunnel through the model; here a voxel is emptied only when more than max_misses views
+// see it as background.  max_misses = 0 is carve() bit for bit.  Views are bound as carve() binds
+// them; the result stays on the device until somebody reads the model on the host.
+inline void carveVotes(const Intrinsics &intr, Model &model, const std::vector<View> &views, int max_misses) {
+    std::cout << "LOG - VC: starting carving process (version 1, up to " << max_misses << " misses)." << std::endl;
+    detail::timing(kStageCarving, true);
+    arvx_ctx *ctx = detail::bind_views(intr, model, views, false);
+    detail::check(arvx_carve_votes(ctx, max_misses, 0), "arvx_carve_votes");
+    model.device_changed();
     detail::check(arvx_ctx_synchronize(ctx), "arvx_ctx_synchronize");
     detail::timing(kStageCarving, false);
     std::cout << "LOG - VC: carving complete." << std::endl;

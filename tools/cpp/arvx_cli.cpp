@@ -228,7 +228,7 @@ int main(int argc, char *argv[]) {
         {"dy", "0.0"}, {"dz", "0.0"}, {"model_debug", "false"}, {"postprocessing", "true"},
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
-        {"photoIters", "32"}, {"render", ""}};
+        {"photoIters", "32"}, {"render", ""}, {"misses", "0"}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -239,6 +239,9 @@ int main(int argc, char *argv[]) {
                      "  -smooth=N (the welded mesh after N Taubin iterations, lambda 0.5, mu -0.53),\n"
                      "  -visible=true (-color=1|2 over the views in which each voxel is visible),\n"
                      "  -visibleTol=T (its depth tolerance in voxel edges, default 3),\n"
+                     "  -misses=K (-carve=1: empty a voxel only when more than K views see it as\n"
+                     "    background; 0, the default: the reference's carve; K > 0 writes no\n"
+                     "    intermediate meshes),\n"
                      "  -photo=T (after carving: remove surface voxels whose visible views' colours\n"
                      "    differ by a summed channel standard deviation above T; 0, the default: off),\n"
                      "  -photoViews=N (views a voxel must be visible in to be judged, default 2),\n"
@@ -261,6 +264,10 @@ int main(int argc, char *argv[]) {
         const int carveArg = parser.i("carve");
         if (carveArg < 1 || 2 < carveArg) {
             std::cerr << "Invalid carve argument.";
+            return 1;
+        }
+        if (parser.i("misses") < 0 || 65535 < parser.i("misses")) {
+            std::cerr << "Invalid misses argument.";
             return 1;
         }
     }
@@ -381,7 +388,13 @@ int main(int argc, char *argv[]) {
         // 100, 100, 100, 0.0028 ~ Caruco
         arvx::Model model(x, y, z, size);
         switch (parser.i("carve")) {
-            case 1: arvx::carve(in.intr, model, in.views, parser.b("intermediateMesh")); break;
+            case 1:
+                // -misses=K (an extension beyond the reference): the vote carve in place of carve()
+                if (parser.i("misses") > 0)
+                    arvx::carveVotes(in.intr, model, in.views, parser.i("misses"));
+                else
+                    arvx::carve(in.intr, model, in.views, parser.b("intermediateMesh"));
+                break;
             case 2: arvx::fastCarve(in.intr, model, in.views); break;
         }
         // -photo (an extension beyond the reference): photo-consistency carving before the colours
