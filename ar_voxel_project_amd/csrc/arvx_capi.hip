@@ -15,6 +15,7 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -204,14 +205,14 @@ static int bit_compact_count(Ctx *ctx, const unsigned long long *bits, size_t nw
 }
 
 // the control block of the one-launch compaction / scan kernels: ticket counter, device totals,
-// `nchunks` status words; *status: where they start
-static int compact_control(Ctx *ctx, size_t nchunks, uint8_t **base, unsigned long long **status) {
-    const size_t off_status = 128;  // [0] ticket counter, [8 + 8 k] device totals, then the status words
+// `nchunks` status words; *status (may be null): where they start
+static constexpr size_t kCompactStatus = 128;  // [0] ticket counter, [8 + 8 k] device totals, then the status words
+static int compact_control(Ctx *ctx, size_t nchunks, unsigned long long **status) {
     // (room for the longest array a context ever compacts or scans -- one entry per voxel, a chunk per
     // 4096 of them --, so that the block never moves between the launches of a call: the kernels of
     // a call read each other's totals from it)
     const size_t most = ctx->nvox_ext / 4096 + 4096;
-    const size_t need = off_status + std::max(nchunks, most) * sizeof(unsigned long long) + 64;
+    const size_t need = kCompactStatus + std::max(nchunks, most) * sizeof(unsigned long long) + 64;
     if (ctx->pool_compact.cap < need) {
         ARVX_HIP(ctx->pool_compact.reserve(need));
         ARVX_HIP(hipMemsetAsync(ctx->pool_compact.p, 0, ctx->pool_compact.cap, ctx->stream));
@@ -223,35 +224,40 @@ static int compact_control(Ctx *ctx, size_t nchunks, uint8_t **base, unsigned lo
         ctx->compact_tickets = 0;
         ctx->compact_epoch = 1u;
     }
-    *base = (uint8_t *)ctx->pool_compact.p;
-    *status = (unsigned long long *)(*base + off_status);
+    if (status) *status = (unsigned long long *)((uint8_t *)ctx->pool_compact.p + kCompactStatus);
     return ARVX_OK;
 }
 
+// the device's copy of a list length in that control block (words below Ctx::kDeviceTotals)
+static long long *device_total(const Ctx *ctx, Ctx::Word w) {
+    static_assert(8 + 8 * Ctx::kDeviceTotals <= kCompactStatus, "the device totals end before the status words");
+    return (long long *)((uint8_t *)ctx->pool_compact.p + 8 + 8 * (int)w);
+}
+
 // Exclusive scan of n counts in ONE launch (scan_lookback_kernel): offsets[i]; the sum goes to device
-// word *d_total_out and to ctx->h_totals[slot].  cells: the counts are the triangles of the
+// word *d_total_out and to the count word w.  cells: the counts are the triangles of the
 // marching-cubes cells of that list (n: its capacity, *n_dev: its length), not an array.
 static int scan_counts(Ctx *ctx, const int *counts, const int4 *cells, long long n, const long long *n_dev,
-                       int *d_offsets, int slot, const long long **d_total_out) {
+                       int *d_offsets, Ctx::Word w, const long long **d_total_out) {
     const size_t nchunks = (size_t)((n + arvx::kScanChunk - 1) / arvx::kScanChunk);
-    uint8_t *base = nullptr;
     unsigned long long *status = nullptr;
-    if (int rc = compact_control(ctx, nchunks, &base, &status)) return rc;
-    long long *d_total = (long long *)(base + 8 + 8 * slot);
-    ctx->h_totals[slot] = -1;
+    if (int rc = compact_control(ctx, nchunks, &status)) return rc;
+    unsigned *tickets = (unsigned *)ctx->pool_compact.p;
+    long long *d_total = device_total(ctx, w);
+    ctx->word(w) = -1;
     if (cells) {
         const int8_t *table = nullptr;  // (the triangle counts of Bourke's table, on the device)
         ARVX_HIP(hipGetSymbolAddress((void **)&table, HIP_SYMBOL(arvx::kMcTri)));
         table += offsetof(arvx::McTriTable, n);
         hipLaunchKernelGGL(arvx::scan_lookback_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream,
-                           (const int *)cells, table, n, n_dev, d_offsets, (unsigned *)base,
+                           (const int *)cells, table, n, n_dev, d_offsets, tickets,
                            (unsigned)ctx->compact_tickets, status, ctx->compact_epoch, d_total,
-                           ctx->d_totals_host + slot, ctx->d_fault);
+                           ctx->word_dev(w), ctx->d_fault);
     } else {
         hipLaunchKernelGGL(arvx::scan_lookback_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream,
                            counts, (const int8_t *)nullptr, n, (const long long *)nullptr, d_offsets,
-                           (unsigned *)base, (unsigned)ctx->compact_tickets, status, ctx->compact_epoch,
-                           d_total, ctx->d_totals_host + slot, ctx->d_fault);
+                           tickets, (unsigned)ctx->compact_tickets, status, ctx->compact_epoch,
+                           d_total, ctx->word_dev(w), ctx->d_fault);
     }
     ARVX_HIP(hipGetLastError());
     ctx->compact_tickets += nchunks;
@@ -262,24 +268,21 @@ static int scan_counts(Ctx *ctx, const int *counts, const int4 *cells, long long
 // The ordered compaction in ONE launch (bit_compact_counted_kernel) of a plane whose producer left the
 // set bits of every chunk of kBitChunk words in `counts`: up to `cap` entries of the list go to d_index,
 // every word's SparseWord to d_words; the list's true length is left in device word *d_total_out (for
-// the kernels that follow) and in the page-locked ctx->h_totals[slot], which the caller reads after
-// its synchronisation.
+// the kernels that follow) and in the count word w, which the caller reads after its synchronisation.
 static int bit_compact(Ctx *ctx, const unsigned long long *bits, size_t nwords, const arvx::BitGrid &g,
-                       long long cap, int *d_index, arvx::SparseWord *d_words, int slot,
+                       long long cap, int *d_index, arvx::SparseWord *d_words, Ctx::Word w,
                        const long long **d_total_out) {
     const size_t nchunks = (nwords + arvx::kBitChunk - 1) / arvx::kBitChunk;
-    uint8_t *base = nullptr;
-    unsigned long long *status = nullptr;
-    if (int rc = compact_control(ctx, 0, &base, &status)) return rc;  // (the device totals live there)
-    long long *d_total = (long long *)(base + 8 + 8 * slot);
-    ctx->h_totals[slot] = -1;
+    if (int rc = compact_control(ctx, 0, nullptr)) return rc;  // (the device totals live there)
+    long long *d_total = device_total(ctx, w);
+    ctx->word(w) = -1;
     // the counts the producer has just left in buffer `counts_cur`; the other buffer is cleared for
     // the next producer on the way
     int *cur = (int *)ctx->pool_chunk_counts.p + (size_t)ctx->counts_cur * ctx->counts_stride;
     int *other = (int *)ctx->pool_chunk_counts.p + (size_t)(ctx->counts_cur ^ 1) * ctx->counts_stride;
     hipLaunchKernelGGL(arvx::bit_compact_counted_kernel, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream,
                        bits, nwords, g, (const int *)cur, other, cap, d_index, d_words, d_total,
-                       ctx->d_totals_host + slot);
+                       ctx->word_dev(w));
     ARVX_HIP(hipGetLastError());
     ctx->counts_clean[ctx->counts_cur ^ 1] = true;
     if (d_total_out) *d_total_out = d_total;
@@ -307,17 +310,83 @@ static int chunk_counts(Ctx *ctx, size_t nwords, int **counts) {
 // The total a one-launch compaction / scan left for the host (after the call's synchronisation).  The
 // kernel stores it into the page-locked word; should the host not see that store, the device's own
 // copy of the word is fetched instead (-1: neither holds a count).
-static long long host_total(Ctx *ctx, int slot) {
-    const long long t = ctx->h_totals[slot];
+static long long host_total(Ctx *ctx, Ctx::Word w) {
+    const long long t = ctx->word(w);
     if (t >= 0 || !ctx->pool_compact.p) return t;
     // never expected since the word is allocated coherent (EXPERIMENTS.md round 4): counted, so that
     // a recurrence shows (arvx_get_stats: host_total_fallbacks; the list tests assert 0)
     ++ctx->host_total_fallbacks;
     long long dev = -1;
-    if (hipMemcpy(&dev, (const uint8_t *)ctx->pool_compact.p + 8 + 8 * slot, sizeof dev,
-                  hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&dev, device_total(ctx, w), sizeof dev, hipMemcpyDeviceToHost) != hipSuccess)
         return -1;
     return dev;
+}
+
+// ---- lists of unknown length: sized, launched, read, retried once -----------------------------
+
+// Room for a list of `entry`-byte entries before its length is known: what its pool held for the
+// last call, or -- the first call -- `first`: for the lists of surface voxels, a surface's share of
+// v voxels and never more than `most` entries.
+static long long list_cap(const arvx::DevPool &pool, size_t entry, long long first) {
+    return pool.cap >= entry ? (long long)(pool.cap / entry) : first;
+}
+static long long first_list_cap(double v, double most) {
+    return (long long)std::min<double>(most, 8.0 * std::cbrt(v) * std::cbrt(v) + 4096.0);
+}
+
+// Room for the large footprints of a splat over n entries, of which `all` exist at most: what the
+// last call wanted to list and an eighth more, at least a quarter of the entries and 64 Ki more.
+// What does not fit is swept by the splat's own waves: the room changes the time, never the result.
+static unsigned large_list_cap(long long n, long long need, long long all) {
+    const long long want = std::max((1ll << 16) + n / 4, need + need / 8);
+    return (unsigned)std::min<long long>({all, want, (long long)UINT32_MAX});
+}
+
+// One list of such a call: the count word its length comes back in, its room, its length.
+struct ListRoom {
+    Ctx::Word word;
+    long long cap, total;
+};
+struct NoSettle {
+    int operator()() const { return ARVX_OK; }
+};
+
+// The protocol: launch() reserves and enqueues everything at the lists' capacities; ONE
+// synchronisation; every list's length is read; settle() reads what else the kernels left; lists
+// that outgrew their room get an eighth more than they need and the call's launches run once more.
+// Never a third time: the second attempt had room for all.
+template <size_t N, class Launch, class Settle = NoSettle>
+static int run_lists(Ctx *ctx, ListRoom (&lists)[N], Launch launch, Settle settle = {}) {
+    for (int attempt = 0;; ++attempt) {
+        if (int rc = launch()) return rc;
+        ARVX_SYNC(ctx);
+        bool fits = true, counted = true;
+        for (ListRoom &l : lists) {
+            l.total = host_total(ctx, l.word);
+            counted = counted && l.total >= 0;
+            fits = fits && l.total <= l.cap;
+        }
+        if (!counted) return fail(ARVX_ERR_HIP, "a list's kernels left no count");
+        if (int rc = settle()) return rc;
+        if (fits || attempt) return ARVX_OK;
+        for (ListRoom &l : lists)
+            if (l.total > l.cap) l.cap = l.total + l.total / 8;
+    }
+}
+
+// The mesh's lists {cells, triangles, ...}: with too few cells the triangle count is of the cells
+// that fitted -- five per missing cell at most.  The meshes' settle hook: it runs before the lists grow.
+static int room_for_missing_cells(const ListRoom &cells, ListRoom &tris) {
+    if (cells.total > cells.cap) tris.cap = std::max(tris.cap, tris.total + 5 * (cells.total - cells.cap));
+    return ARVX_OK;
+}
+
+// f(std::true_type) or f(std::false_type) by the context's grouping: the kernels take it as a
+// template argument, `kernel<decltype(left)::value>`
+template <class F>
+static void by_assoc(const Ctx *ctx, F f) {
+    if (ctx->assoc == ARVX_ASSOC_LEFT) f(std::true_type{});
+    else f(std::false_type{});
 }
 
 static int bit_compact_write(Ctx *ctx, const unsigned long long *bits, size_t nwords,
@@ -448,14 +517,10 @@ int arvx_ctx_create_slab_halo(arvx_ctx **out, int device, int X, int Y, int Z, f
     // Coherent: without the flag a mapped allocation is non-coherent host memory -- the device's stores
     // to it need not be seen by a host that has the line in its cache (the totals' words are reset by
     // the host before every launch: a call then read its own -1 back, once in a few hundred calls)
-    e = hipHostMalloc((void **)&c->h_fault, 128, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) {
-        memset(c->h_fault, 0, 128);
+    e = hipHostMalloc((void **)&c->h_fault, Ctx::kHostBlockBytes, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess) {  // (the fault word, then the count words: arvx_ctx.h)
+        memset(c->h_fault, 0, Ctx::kHostBlockBytes);
         e = hipHostGetDevicePointer((void **)&c->d_fault, c->h_fault, 0);
-        c->h_totals = (long long *)(c->h_fault + 2);  // six 8-byte words behind the fault word
-        c->d_totals_host = (long long *)(c->d_fault + 2);
-        c->h_render = (long long *)(c->h_fault + 16);  // arvx_render's four words, in the second line
-        c->d_render_host = (long long *)(c->d_fault + 16);
     }
     if (e != hipSuccess) {
         arvx_ctx_destroy(c);
@@ -822,6 +887,17 @@ static void carve_geometry(const Ctx *ctx, arvx::CarveParams &p) {
     p.coarseZ = (p.Z + (8 << p.czShift) - 1) / (8 << p.czShift);
     p.ccode = ctx->form == Form::Lazy ? (const uint8_t *)ctx->pool_ccode.p : nullptr;
 }
+// the views' matrices and tables (arvx_set_views) as the carve kernels see them
+static void carve_views(const Ctx *ctx, arvx::CarveParams &p) {
+    p.M = ctx->M();
+    p.bg = ctx->bg();
+    p.sat = ctx->sat();
+    p.W = ctx->W;
+    p.H = ctx->H;
+    p.bgWords = ctx->bgWords;
+    p.satStride = ctx->satStride;
+    p.satW = ctx->satW;
+}
 
 // a record buffer for this context's grid, every record "finished" when it is new
 static int ensure_records(Ctx *ctx, arvx::DevPool &buf) {
@@ -1042,12 +1118,12 @@ int arvx_state_download_packets(arvx_ctx *ctx, uint64_t *occ_packet, int64_t occ
         hipLaunchKernelGGL(arvx::occ_pack_write_kernel<true>, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0,
                            ctx->stream, g, og, zl0, n, n, d_wgsum + nwg, nwg, pk + S);
         ARVX_HIP(hipGetLastError());
-        // the two counts first (16 bytes through the page-locked totals: slots 4 and 5)
-        ARVX_HIP(hipMemcpyAsync(ctx->h_totals + 4, pk, 8, hipMemcpyDeviceToHost, ctx->stream));
-        ARVX_HIP(hipMemcpyAsync(ctx->h_totals + 5, pk + S, 8, hipMemcpyDeviceToHost, ctx->stream));
+        // the two counts first (16 bytes through their page-locked count words)
+        ARVX_HIP(hipMemcpyAsync(&ctx->word(Ctx::kPacketOcc), pk, 8, hipMemcpyDeviceToHost, ctx->stream));
+        ARVX_HIP(hipMemcpyAsync(&ctx->word(Ctx::kPacketSeen), pk + S, 8, hipMemcpyDeviceToHost, ctx->stream));
         ARVX_SYNC(ctx);
-        ctx->packet_need[0] = ctx->h_totals[4];
-        ctx->packet_need[1] = ctx->h_totals[5];
+        ctx->packet_need[0] = ctx->word(Ctx::kPacketOcc);
+        ctx->packet_need[1] = ctx->word(Ctx::kPacketSeen);
         ctx->packets_seq = ctx->state_seq;
     }
     const unsigned long long *pk = (const unsigned long long *)ctx->pool_state_packets.p;
@@ -1434,15 +1510,8 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     arvx::CarveParams p;
     carve_geometry(ctx, p);
     p.rec = rec;
-    p.M = ctx->M();
-    p.bg = ctx->bg();
-    p.sat = ctx->sat();
+    carve_views(ctx, p);
     p.stats = ctx->stats();
-    p.W = ctx->W;
-    p.H = ctx->H;
-    p.bgWords = ctx->bgWords;
-    p.satStride = ctx->satStride;
-    p.satW = ctx->satW;
     p.v0 = first;
     p.v1 = first + count;
     p.flags = (flags & 3u) | (fresh ? 4u : 0u);
@@ -1752,14 +1821,7 @@ int arvx_carve_votes(arvx_ctx *ctx, int max_misses, unsigned flags) {
     carve_geometry(ctx, p);
     p.rec = ctx->rec();
     p.ccode = nullptr;
-    p.M = ctx->M();
-    p.bg = ctx->bg();
-    p.sat = ctx->sat();
-    p.W = ctx->W;
-    p.H = ctx->H;
-    p.bgWords = ctx->bgWords;
-    p.satStride = ctx->satStride;
-    p.satW = ctx->satW;
+    carve_views(ctx, p);
     p.v0 = 0;
     p.v1 = ctx->V;
     p.flags = fresh ? 4u : 0u;
@@ -1769,10 +1831,9 @@ int arvx_carve_votes(arvx_ctx *ctx, int max_misses, unsigned flags) {
     q.cull = (flags & ARVX_VOTES_NO_CULL) ? 0 : 1;
     const size_t rows8 = ((size_t)p.tilesY * p.tilesZ + 7) / 8 * 8;
     const unsigned grid = (unsigned)(rows8 * p.tilesX);
-    if (ctx->assoc == ARVX_ASSOC_LEFT)
-        hipLaunchKernelGGL(arvx::carve_votes_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, q);
-    else
-        hipLaunchKernelGGL(arvx::carve_votes_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, q);
+    by_assoc(ctx, [&](auto left) {
+        hipLaunchKernelGGL(arvx::carve_votes_kernel<decltype(left)::value>, dim3(grid), dim3(256), 0, ctx->stream, q);
+    });
     ARVX_HIP(hipGetLastError());
     ctx->votes_ready = (flags & ARVX_VOTES_COUNTS) != 0;
     return ARVX_OK;
@@ -1893,18 +1954,31 @@ static int color_refusals(Ctx *ctx, int mode) {
 }
 
 static int launch_visible_vote(Ctx *ctx, const arvx::VoteParams &vp, float tol);
-// the page-locked word the large-footprint sweep leaves the number of large footprints in (slot 5
-// is otherwise used only inside arvx_state_download_packets)
-static constexpr int kVisNeedSlot = 5;
+
+// The geometry, views and images of a colour vote over indices that start at global plane zglob0;
+// the list and the outputs are the caller's to fill.
+static arvx::VoteParams vote_params(const Ctx *ctx, int zglob0) {
+    arvx::VoteParams vp{};
+    vp.X = ctx->X;
+    vp.Y = ctx->Y;
+    vp.zglob0 = zglob0;
+    vp.s = ctx->s;
+    vp.V = ctx->V;
+    vp.W = ctx->W;
+    vp.H = ctx->H;
+    vp.M = ctx->M();
+    vp.campos = ctx->campos();
+    vp.images = ctx->images();
+    return vp;
+}
 
 // The colour pass's list of the current state (arvx_color and arvx_photo_carve's iterations):
 // surface = occupied and not inner, on bit planes over the context's planes, for the planes
 // [c_lo, c_hi) (stage_ranges): the owned ones and the halo planes whose own neighbours the records
 // hold; its ordered compaction goes to pool_surf_index, the plane and its ranks (SparseWord) stay in
 // pool_col_bits / pool_col_rank.  The list's length is not known before the compaction has run: the
-// buffers are sized for what the last pass needed (first call: a surface's share of the voxels), the
-// kernels stop at that capacity, and the true length is read at the ONE synchronisation; a list that
-// outgrew its buffers is compacted and worked on again with room for all of it.  Per attempt:
+// kernels stop at the capacity the buffers were sized for, and a list that outgrew it is compacted
+// and worked on again with room for all of it (run_lists).  Per attempt:
 // reserve(cap) sizes the caller's buffers, launch(vp) enqueues its kernels on the list vp describes
 // (length on the device, in vp.n_dev; vp.rgba / depth / has / mode are the caller's to fill), and
 // settle() reads what they left after the synchronisation.
@@ -1940,48 +2014,27 @@ static int surface_list(Ctx *ctx, Reserve reserve, Launch launch, Settle settle,
     hipLaunchKernelGGL(arvx::bit_surface_count_kernel, dim3((unsigned)((nw_ext + 255) / 256)), dim3(256), 0,
                        ctx->stream, d_occ, gext, c_lo - ctx->ze0, c_hi - ctx->ze0, d_surf, d_counts);
     ARVX_HIP(hipGetLastError());
-    long long cap = (long long)(ctx->pool_surf_index.cap / sizeof(int));
-    if (cap <= 0) {
-        const double v = (double)ctx->X * ctx->Y * Zext;
-        cap = (long long)std::min<double>(v, 8.0 * std::cbrt(v) * std::cbrt(v) + 4096.0);
-    }
-    long long total = 0;
-    for (int attempt = 0;; ++attempt) {
+    const double v = (double)ctx->X * ctx->Y * Zext;
+    ListRoom lists[] = {{Ctx::kSurface, list_cap(ctx->pool_surf_index, sizeof(int), first_list_cap(v, v)), 0}};
+    const long long &cap = lists[0].cap;
+    auto attempt = [&]() -> int {
         ARVX_HIP(ctx->pool_surf_index.reserve((size_t)cap * sizeof(int)));
         ctx->d_surf_index = (int *)ctx->pool_surf_index.p;
         if (int rc = reserve(cap)) return rc;
         const long long *d_total = nullptr;
         if (int rc = bit_compact(ctx, d_surf, nw_ext, gext, cap, ctx->d_surf_index,
-                                 (arvx::SparseWord *)ctx->pool_col_rank.p, 0, &d_total))
+                                 (arvx::SparseWord *)ctx->pool_col_rank.p, Ctx::kSurface, &d_total))
             return rc;
-        arvx::VoteParams vp;
+        arvx::VoteParams vp = vote_params(ctx, ctx->ze0);  // (list indices run over the context's planes)
         vp.index = ctx->d_surf_index;
         vp.n = cap;
         vp.n_dev = d_total;
-        vp.X = ctx->X;
-        vp.Y = ctx->Y;
-        vp.zglob0 = ctx->ze0;  // (list indices run over the context's planes)
-        vp.s = ctx->s;
-        vp.V = ctx->V;
-        vp.W = ctx->W;
-        vp.H = ctx->H;
-        vp.M = ctx->M();
-        vp.campos = ctx->campos();
-        vp.images = ctx->images();
-        vp.mode = 0;
-        vp.rgba = nullptr;
-        vp.depth = nullptr;
-        vp.has = nullptr;
         if (int rc = launch(vp)) return rc;
         ARVX_HIP(hipGetLastError());
-        ARVX_SYNC(ctx);
-        total = host_total(ctx, 0);
-        if (total < 0) return fail(ARVX_ERR_HIP, "the compaction left no count");
-        if (int rc = settle()) return rc;
-        if (total <= cap || attempt) break;
-        cap = total + total / 8;  // (once more, with room for all)
-    }
-    *total_out = total;
+        return ARVX_OK;
+    };
+    if (int rc = run_lists(ctx, lists, attempt, settle)) return rc;
+    *total_out = lists[0].total;
     return ARVX_OK;
 }
 }  // extern "C++"
@@ -2008,17 +2061,16 @@ static int color_pass(Ctx *ctx, int mode, bool visible, float tol) {
         vp.has = ctx->d_surf_has;
         if (visible) {
             if (int rc = launch_visible_vote(ctx, vp, tol)) return rc;
-        } else if (ctx->assoc == ARVX_ASSOC_LEFT) {
-            hipLaunchKernelGGL(arvx::color_vote_kernel<true>, dim3((unsigned)((cap + 255) / 256)),
-                               dim3(256), 0, ctx->stream, vp);
         } else {
-            hipLaunchKernelGGL(arvx::color_vote_kernel<false>, dim3((unsigned)((cap + 255) / 256)),
-                               dim3(256), 0, ctx->stream, vp);
+            by_assoc(ctx, [&](auto left) {
+                hipLaunchKernelGGL(arvx::color_vote_kernel<decltype(left)::value>,
+                                   dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, vp);
+            });
         }
         return ARVX_OK;
     };
     auto settle = [&]() -> int {
-        if (visible && ctx->h_totals[kVisNeedSlot] >= 0) ctx->vis_large_need = ctx->h_totals[kVisNeedSlot];
+        if (visible && ctx->word(Ctx::kVisNeed) >= 0) ctx->vis_large_need = ctx->word(Ctx::kVisNeed);
         return ARVX_OK;
     };
     long long total = 0;
@@ -2045,16 +2097,13 @@ int arvx_color(arvx_ctx *ctx, int mode) {
 
 // The depth buffers of the views (clear, splat, large footprints) of the list of `cap` entries at
 // `index` (its length on the device, *n_dev): no synchronisation.  The sweep leaves the number of
-// large footprints it wanted in h_totals[kVisNeedSlot] (the caller hands it on to vis_large_need).
+// large footprints it wanted in the count word kVisNeed (the caller hands it on to vis_large_need).
 static int launch_depth_buffers(Ctx *ctx, const int *index, long long cap, const long long *n_dev,
                                 uint32_t **zbuf_out) {
-    ctx->h_totals[kVisNeedSlot] = -1;
+    ctx->word(Ctx::kVisNeed) = -1;
     const size_t plane = (size_t)ctx->W * ctx->H, nz = plane * ctx->V;
     ARVX_HIP(ctx->pool_vis_depth.reserve(nz * sizeof(uint32_t)));
-    // large footprints: room for what the last call wanted to list (an eighth more), at least a
-    // quarter of the list and 64 Ki more; what does not fit is swept by the splat's own waves
-    const long long want = std::max((1ll << 16) + cap / 4, ctx->vis_large_need + ctx->vis_large_need / 8);
-    const unsigned large_cap = (unsigned)std::min<long long>({cap * ctx->V, want, (long long)UINT32_MAX});
+    const unsigned large_cap = large_list_cap(cap, ctx->vis_large_need, cap * ctx->V);
     ARVX_HIP(ctx->pool_vis_large.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
     uint32_t *zbuf = (uint32_t *)ctx->pool_vis_depth.p;
     unsigned *n_large = (unsigned *)ctx->pool_vis_large.p;
@@ -2080,14 +2129,13 @@ static int launch_depth_buffers(Ctx *ctx, const int *index, long long cap, const
     sp.large_cap = large_cap;
     // (the x grid strides over the list: its capacity can be several times its length)
     const dim3 sgrid((unsigned)std::min<long long>((cap + 255) / 256, 1024), (unsigned)ctx->V);
-    if (ctx->assoc == ARVX_ASSOC_LEFT)
-        hipLaunchKernelGGL(arvx::vis_splat_kernel<true>, sgrid, dim3(256), 0, ctx->stream, sp);
-    else
-        hipLaunchKernelGGL(arvx::vis_splat_kernel<false>, sgrid, dim3(256), 0, ctx->stream, sp);
+    by_assoc(ctx, [&](auto left) {
+        hipLaunchKernelGGL(arvx::vis_splat_kernel<decltype(left)::value>, sgrid, dim3(256), 0, ctx->stream, sp);
+    });
     ARVX_HIP(hipGetLastError());
     hipLaunchKernelGGL(arvx::vis_splat_large_kernel, dim3((unsigned)(4 * ncu)), dim3(256), 0, ctx->stream,
                        (const arvx::SplatRect *)large, (const unsigned *)n_large, large_cap, zbuf, ctx->W,
-                       ctx->H, ctx->d_totals_host + kVisNeedSlot);
+                       ctx->H, ctx->word_dev(Ctx::kVisNeed));
     ARVX_HIP(hipGetLastError());
     *zbuf_out = zbuf;
     return ARVX_OK;
@@ -2104,12 +2152,10 @@ static int launch_visible_vote(Ctx *ctx, const arvx::VoteParams &vp, float tol) 
     q.zbuf = zbuf;
     q.tol = tol;
     q.views = (int *)ctx->pool_vis_views.p;
-    if (ctx->assoc == ARVX_ASSOC_LEFT)
-        hipLaunchKernelGGL(arvx::vis_vote_kernel<true>, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0,
-                           ctx->stream, q);
-    else
-        hipLaunchKernelGGL(arvx::vis_vote_kernel<false>, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0,
-                           ctx->stream, q);
+    by_assoc(ctx, [&](auto left) {
+        hipLaunchKernelGGL(arvx::vis_vote_kernel<decltype(left)::value>, dim3((unsigned)((cap + 255) / 256)),
+                           dim3(256), 0, ctx->stream, q);
+    });
     return ARVX_OK;
 }
 
@@ -2123,10 +2169,6 @@ int arvx_color_visible(arvx_ctx *ctx, int mode, float tolerance) {
                                     "need every surface voxel)");
     return color_pass(ctx, mode, true, tolerance);
 }
-
-// the page-locked word photo_plane_kernel leaves an iteration's removal count in (slot 1 is
-// otherwise the closure's list length, never compacted inside arvx_photo_carve)
-static constexpr int kPhotoRemovedSlot = 1;
 
 int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float tolerance, int max_iterations,
                      int *iterations, int64_t *removed) {
@@ -2175,7 +2217,7 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
         return ARVX_OK;
     };
     auto launch = [&](const arvx::VoteParams &vp) -> int {
-        ctx->h_totals[kPhotoRemovedSlot] = -1;
+        ctx->word(Ctx::kPhotoRemoved) = -1;  // (photo_plane_kernel leaves the iteration's removals there)
         const long long cap = vp.n;
         uint32_t *zbuf = nullptr;
         if (int rc = launch_depth_buffers(ctx, vp.index, cap, vp.n_dev, &zbuf)) return rc;
@@ -2187,25 +2229,23 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
         q.min_views = min_views;
         q.removed = (unsigned long long *)ctx->pool_photo_rm.p;
         q.rm = (unsigned long long *)((uint8_t *)ctx->pool_photo_rm.p + 64);
-        if (ctx->assoc == ARVX_ASSOC_LEFT)
-            hipLaunchKernelGGL(arvx::photo_consist_kernel<true>, dim3((unsigned)((cap + 255) / 256)), dim3(256),
-                               0, ctx->stream, q);
-        else
-            hipLaunchKernelGGL(arvx::photo_consist_kernel<false>, dim3((unsigned)((cap + 255) / 256)), dim3(256),
-                               0, ctx->stream, q);
+        by_assoc(ctx, [&](auto left) {
+            hipLaunchKernelGGL(arvx::photo_consist_kernel<decltype(left)::value>,
+                               dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, q);
+        });
         ARVX_HIP(hipGetLastError());
         const unsigned gw = (unsigned)((nw_ext + 255) / 256);
         hipLaunchKernelGGL(arvx::photo_plane_kernel, dim3(gw), dim3(256), 0, ctx->stream,
                            (const arvx::SparseWord *)ctx->pool_col_rank.p, nw_ext, (const unsigned long long *)q.rm,
-                           cap, vp.n_dev, d_plane, q.removed, ctx->d_totals_host + kPhotoRemovedSlot);
+                           cap, vp.n_dev, d_plane, q.removed, ctx->word_dev(Ctx::kPhotoRemoved));
         ARVX_HIP(hipGetLastError());
         hipLaunchKernelGGL(arvx::rec_andnot_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, Zext,
                            (const unsigned long long *)d_plane);
         return ARVX_OK;
     };
     auto settle = [&]() -> int {
-        if (ctx->h_totals[kVisNeedSlot] >= 0) ctx->vis_large_need = ctx->h_totals[kVisNeedSlot];
-        removed_k = ctx->h_totals[kPhotoRemovedSlot];
+        if (ctx->word(Ctx::kVisNeed) >= 0) ctx->vis_large_need = ctx->word(Ctx::kVisNeed);
+        removed_k = ctx->word(Ctx::kPhotoRemoved);
         if (removed_k < 0) return fail(ARVX_ERR_HIP, "the consistency pass left no count");
         return ARVX_OK;
     };
@@ -2248,25 +2288,13 @@ int arvx_color_samples(arvx_ctx *ctx, int64_t n, const int64_t *index, int views
     long long *d_idx = (long long *)(d_out + total);
     ARVX_HIP(hipMemcpyAsync(d_idx, index, (size_t)n * sizeof(long long), hipMemcpyHostToDevice,
                             ctx->stream));
-    arvx::VoteParams vp{};
+    arvx::VoteParams vp = vote_params(ctx, ctx->z0);  // (indices run over the owned planes)
     vp.n = n;
-    vp.X = ctx->X;
-    vp.Y = ctx->Y;
-    vp.zglob0 = ctx->z0;  // (indices run over the owned planes)
-    vp.s = ctx->s;
-    vp.V = ctx->V;
-    vp.W = ctx->W;
-    vp.H = ctx->H;
-    vp.M = ctx->M();
-    vp.campos = ctx->campos();
-    vp.images = ctx->images();
     const unsigned grid = (unsigned)((total + 255) / 256);
-    if (ctx->assoc == ARVX_ASSOC_LEFT)
-        hipLaunchKernelGGL(arvx::color_samples_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, vp,
-                           d_idx, d_out);
-    else
-        hipLaunchKernelGGL(arvx::color_samples_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, vp,
-                           d_idx, d_out);
+    by_assoc(ctx, [&](auto left) {
+        hipLaunchKernelGGL(arvx::color_samples_kernel<decltype(left)::value>, dim3(grid), dim3(256), 0,
+                           ctx->stream, vp, d_idx, d_out);
+    });
     ARVX_HIP(hipGetLastError());
     ARVX_HIP(hipMemcpyAsync(out, d_out, total * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);
@@ -2491,12 +2519,10 @@ int arvx_selftest_project(arvx_ctx *ctx, int64_t n, const float M[12], float vox
     memcpy(m.m, M, sizeof m.m);
     const unsigned grid = (unsigned)((n + 255) / 256);
     return selftest_xyz(ctx, n, xyz, (size_t)n * 5, rows_uv, [&](int *d_xyz, float *d_out) {
-        if (ctx->assoc == ARVX_ASSOC_LEFT)
-            hipLaunchKernelGGL(arvx::selftest_project_kernel<true>, dim3(grid), dim3(256), 0,
+        by_assoc(ctx, [&](auto left) {
+            hipLaunchKernelGGL(arvx::selftest_project_kernel<decltype(left)::value>, dim3(grid), dim3(256), 0,
                                ctx->stream, m, voxel_size, d_xyz, (long long)n, d_out, d_out + 3 * n);
-        else
-            hipLaunchKernelGGL(arvx::selftest_project_kernel<false>, dim3(grid), dim3(256), 0,
-                               ctx->stream, m, voxel_size, d_xyz, (long long)n, d_out, d_out + 3 * n);
+        });
     });
 }
 
@@ -2732,23 +2758,18 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
         hipLaunchKernelGGL(arvx::rec_or_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, g.Z,
                            d_fill);
     ARVX_HIP(hipGetLastError());
-    // The list of the filled voxels: compacted in one launch into buffers sized for what the last
-    // closure needed (first call: a shell's share of the voxels); the true length is read at the
-    // call's ONE synchronisation, and a list that outgrew its buffers is written again.
-    long long cap = (long long)(ctx->pool_clo_index.cap / sizeof(int));
-    if (cap <= 0) {
-        const double v = (double)nwords * 64.0;
-        cap = (long long)std::min<double>(v, 8.0 * std::cbrt(v) * std::cbrt(v) + 4096.0);
-    }
-    long long total = 0;
-    for (int attempt = 0;; ++attempt) {
+    // The list of the filled voxels: compacted and coloured in buffers sized before its length is known (run_lists).
+    const double v = (double)nwords * 64.0;
+    ListRoom lists[] = {{Ctx::kClosure, list_cap(ctx->pool_clo_index, sizeof(int), first_list_cap(v, v)), 0}};
+    const long long &cap = lists[0].cap;
+    auto attempt = [&]() -> int {
         ARVX_HIP(ctx->pool_clo_index.reserve((size_t)cap * sizeof(int)));
         ctx->d_clo_index = (int *)ctx->pool_clo_index.p;
         ARVX_HIP(ctx->pool_clo_rgba.reserve((size_t)cap * sizeof(float4)));
         ctx->d_clo_rgba = (void *)ctx->pool_clo_rgba.p;
         const long long *d_total = nullptr;
         if (int rc = bit_compact(ctx, d_fill, nwords, g, cap, ctx->d_clo_index,
-                                 (arvx::SparseWord *)ctx->pool_clo_rank.p, 1, &d_total))
+                                 (arvx::SparseWord *)ctx->pool_clo_rank.p, Ctx::kClosure, &d_total))
             return rc;
         arvx::ClosureParams cp;
         cp.g = g;
@@ -2766,12 +2787,10 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
                                dim3(256), 0, ctx->stream, cp, ctx->d_clo_index, cap, d_total,
                                (float4 *)ctx->d_clo_rgba);
         ARVX_HIP(hipGetLastError());
-        ARVX_SYNC(ctx);
-        total = host_total(ctx, 1);
-        if (total < 0) return fail(ARVX_ERR_HIP, "the compaction left no count");
-        if (total <= cap || attempt) break;
-        cap = total + total / 8;  // (once more, with room for all)
-    }
+        return ARVX_OK;
+    };
+    if (int rc = run_lists(ctx, lists, attempt)) return rc;
+    const long long total = lists[0].total;
     ctx->clo_count = total;
     ctx->clo_host_count = -1;  // the list's host copy is fetched when somebody asks
     if (total == 0) ctx->closure_fills = false;  // (nothing was filled: the state is as before)
@@ -2835,7 +2854,7 @@ int arvx_closure_download(arvx_ctx *ctx, int64_t *index, float *rgba) {
 // ---- marching-cubes hand-off ----------------------------------------------------------
 
 // The cell list, launched without a synchronisation: up to `cap` cells into the context's buffer,
-// the list's true length in device word *d_total (and ctx->h_totals[2] after the next sync).
+// the list's true length in device word *d_total (and the count word kCells after the next sync).
 static int mc_cells_launch(Ctx *ctx, long long cap, const long long **d_total) {
     if (int mrc = need_rec(ctx, true)) return mrc;  // (mc_zpack_rec_kernel reads lazy tiles)
     arvx::McParams mp;
@@ -2869,7 +2888,7 @@ static int mc_cells_launch(Ctx *ctx, long long cap, const long long **d_total) {
     hipLaunchKernelGGL(arvx::mc_count_kernel, dim3(nblk), dim3(256), 0, ctx->stream, mp, d_cnt);
     ARVX_HIP(hipGetLastError());
     // the columns' offsets in the list: one launch
-    if (int rc = scan_counts(ctx, d_cnt, nullptr, ncol, nullptr, d_off, 2, d_total)) return rc;
+    if (int rc = scan_counts(ctx, d_cnt, nullptr, ncol, nullptr, d_off, Ctx::kCells, d_total)) return rc;
     ARVX_HIP(ctx->pool_mc_cells.reserve((size_t)cap * sizeof(int4)));
     ctx->d_mc_cells = (void *)ctx->pool_mc_cells.p;
     hipLaunchKernelGGL(arvx::mc_write_kernel, dim3(nblk), dim3(256), 0, ctx->stream, mp, d_off, cap,
@@ -2879,12 +2898,22 @@ static int mc_cells_launch(Ctx *ctx, long long cap, const long long **d_total) {
 }
 // room for the cell list before its length is known: what the last list needed, or a surface's share
 static long long mc_cells_cap(const Ctx *ctx) {
-    long long cap = (long long)(ctx->pool_mc_cells.cap / sizeof(int4));
-    if (cap <= 0) {
-        const double v = (double)ctx->nvox_ext;
-        cap = (long long)std::min<double>(v + 1e6, 8.0 * std::cbrt(v) * std::cbrt(v) + 4096.0);
-    }
-    return cap;
+    const double v = (double)ctx->nvox_ext;
+    return list_cap(ctx->pool_mc_cells, sizeof(int4), first_list_cap(v, v + 1e6));
+}
+
+// what the two meshes' kernels read of the state and its colours
+static arvx::McMeshParams mesh_params(const Ctx *ctx, int apply_unseen) {
+    arvx::McMeshParams mp;
+    carve_geometry(ctx, mp.g);
+    mp.g.rec = ctx->rec();
+    mp.paint = paint_plane(ctx);
+    mp.apply_unseen = apply_unseen ? 1 : 0;
+    mp.col = colour_list(ctx);
+    mp.col_rgba = ctx->d_surf_rgba;
+    mp.clo = closure_list(ctx);
+    mp.clo_rgba = (const float4 *)ctx->d_clo_rgba;
+    return mp;
 }
 
 int arvx_mc_cells(arvx_ctx *ctx, int64_t *count) {
@@ -2893,16 +2922,9 @@ int arvx_mc_cells(arvx_ctx *ctx, int64_t *count) {
     if (ctx->stripe_world > 1)
         return fail(ARVX_ERR_STATE, "the cell walk needs contiguous slabs (neighbour planes)");
     ctx->free_mc();
-    long long cap = mc_cells_cap(ctx), total = 0;
-    for (int attempt = 0;; ++attempt) {  // ONE synchronisation; a second round only if the list outgrew its room
-        const long long *d_total = nullptr;
-        if (int rc = mc_cells_launch(ctx, cap, &d_total)) return rc;
-        ARVX_SYNC(ctx);
-        total = host_total(ctx, 2);
-        if (total < 0) return fail(ARVX_ERR_HIP, "the scan left no count");
-        if (total <= cap || attempt) break;
-        cap = total + total / 8;
-    }
+    ListRoom lists[] = {{Ctx::kCells, mc_cells_cap(ctx), 0}};
+    if (int rc = run_lists(ctx, lists, [&] { return mc_cells_launch(ctx, lists[0].cap, nullptr); })) return rc;
+    const long long total = lists[0].total;
     if (total == 0) ctx->d_mc_cells = nullptr;
     ctx->mc_count = total;
     ctx->mc_ready = true;
@@ -2947,53 +2969,36 @@ int arvx_mc_mesh(arvx_ctx *ctx, int apply_unseen, int64_t *triangles) {
                                         "radius %d (it has %d): arvx_ctx_create_slab_halo",
                         ctx->closure_radius + 2, ctx->closure_radius, ctx->halo);
     }
-    // cells -> triangles per cell -> triangles, all launched before the call's ONE synchronisation:
-    // the lists' lengths are not known when their buffers are sized (what the last mesh needed, or
-    // a surface's share of the voxels), the kernels stop at the room they have, and a mesh that
-    // outgrew it is built once more with room for all.
+    // cells -> triangles per cell -> triangles, all launched before the call's ONE synchronisation;
+    // the kernels stop at the room they have, and a mesh that outgrew it is built once more (run_lists).
     ctx->free_mc();
     ctx->mesh_tris = 0;
     *triangles = 0;
-    long long ccap = mc_cells_cap(ctx);
-    long long tcap = (long long)(ctx->pool_mesh_verts.cap / (9 * sizeof(float)));
-    if (tcap <= 0) tcap = 2 * ccap;
-    long long ncells = 0, total = 0;
-    for (int attempt = 0;; ++attempt) {
+    const long long cells = mc_cells_cap(ctx);
+    ListRoom lists[] = {{Ctx::kCells, cells, 0},
+                        {Ctx::kTris, list_cap(ctx->pool_mesh_verts, 9 * sizeof(float), 2 * cells), 0}};
+    const long long &ccap = lists[0].cap, &tcap = lists[1].cap;
+    auto attempt = [&]() -> int {
         const long long *d_ncells = nullptr;
         if (int rc = mc_cells_launch(ctx, ccap, &d_ncells)) return rc;
         ARVX_HIP(ctx->pool_mesh_verts.reserve((size_t)tcap * 9 * sizeof(float)));
         ARVX_HIP(ctx->pool_mesh_rgb.reserve((size_t)tcap * 6 * sizeof(unsigned)));  // face records
-        arvx::McMeshParams mp;
-        carve_geometry(ctx, mp.g);
-        mp.g.rec = ctx->rec();
-        mp.paint = paint_plane(ctx);
-        mp.apply_unseen = apply_unseen ? 1 : 0;
-        mp.col = colour_list(ctx);
-        mp.col_rgba = ctx->d_surf_rgba;
-        mp.clo = closure_list(ctx);
-        mp.clo_rgba = (const float4 *)ctx->d_clo_rgba;
+        const arvx::McMeshParams mp = mesh_params(ctx, apply_unseen);
         // (the scratch buffer holds mc_cells_launch's arrays: the triangle offsets get their own)
         ARVX_HIP(ctx->pool_mesh_off.reserve((size_t)(ccap + 1) * sizeof(int)));
         int *d_off = (int *)ctx->pool_mesh_off.p;
         const long long *d_ntris = nullptr;
-        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, 3, &d_ntris))
+        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, Ctx::kTris, &d_ntris))
             return rc;
         hipLaunchKernelGGL(arvx::mc_mesh_kernel, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0,
                            ctx->stream, mp, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, tcap, d_off,
                            (float *)ctx->pool_mesh_verts.p, (unsigned *)ctx->pool_mesh_rgb.p);
         ARVX_HIP(hipGetLastError());
-        ARVX_SYNC(ctx);
-        ncells = host_total(ctx, 2);
-        total = host_total(ctx, 3);
-        if (ncells < 0 || total < 0) return fail(ARVX_ERR_HIP, "the scans left no count");
-        if ((ncells <= ccap && total <= tcap) || attempt) break;
-        // (with too few cells the triangle count is of the cells that fitted: five per cell at most)
-        if (ncells > ccap) {
-            tcap = std::max(tcap, total + 5 * (ncells - ccap));
-            ccap = ncells + ncells / 8;
-        }
-        if (total > tcap) tcap = total + total / 8;
-    }
+        return ARVX_OK;
+    };
+    if (int rc = run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }))
+        return rc;
+    const long long ncells = lists[0].total, total = lists[1].total;
     if (ncells == 0) ctx->d_mc_cells = nullptr;
     ctx->mc_count = ncells;
     ctx->mc_ready = true;
@@ -3064,35 +3069,26 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
                        ctx->stream, d_occ, g, 0, ctx->Z, d_vtx, d_counts);
     ARVX_HIP(hipGetLastError());
     // room: what the last welded mesh needed, or a surface's share of the voxels
-    long long ccap = mc_cells_cap(ctx);
-    long long tcap = (long long)(ctx->pool_weld_faces.cap / (6 * sizeof(unsigned)));
-    if (tcap <= 0) tcap = 2 * ccap;
-    long long vcap = (long long)(ctx->pool_weld_index.cap / sizeof(int));
-    if (vcap <= 0) vcap = ccap;
-    long long ncells = 0, ntris = 0, nverts = 0;
-    for (int attempt = 0;; ++attempt) {
+    const long long cells = mc_cells_cap(ctx);
+    ListRoom lists[] = {{Ctx::kCells, cells, 0},
+                        {Ctx::kTris, list_cap(ctx->pool_weld_faces, 6 * sizeof(unsigned), 2 * cells), 0},
+                        {Ctx::kVerts, list_cap(ctx->pool_weld_index, sizeof(int), cells), 0}};
+    const long long &ccap = lists[0].cap, &tcap = lists[1].cap, &vcap = lists[2].cap;
+    auto attempt = [&]() -> int {
         ARVX_HIP(ctx->pool_weld_index.reserve((size_t)vcap * sizeof(int)));
         ARVX_HIP(ctx->pool_weld_verts.reserve((size_t)vcap * 3 * sizeof(float)));
         ARVX_HIP(ctx->pool_weld_rgb.reserve((size_t)vcap * 3 * sizeof(float)));
         ARVX_HIP(ctx->pool_weld_faces.reserve((size_t)tcap * 6 * sizeof(unsigned)));
         const long long *d_nverts = nullptr;
-        if (int rc = bit_compact(ctx, d_vtx, nw, g, vcap, (int *)ctx->pool_weld_index.p, d_rank, 4,
-                                 &d_nverts))
+        if (int rc = bit_compact(ctx, d_vtx, nw, g, vcap, (int *)ctx->pool_weld_index.p, d_rank,
+                                 Ctx::kVerts, &d_nverts))
             return rc;
         const long long *d_ncells = nullptr;
         if (int rc = mc_cells_launch(ctx, ccap, &d_ncells)) return rc;
-        arvx::McMeshParams mp;
-        carve_geometry(ctx, mp.g);
-        mp.g.rec = ctx->rec();
-        mp.paint = paint_plane(ctx);
-        mp.apply_unseen = apply_unseen ? 1 : 0;
-        mp.col = colour_list(ctx);
-        mp.col_rgba = ctx->d_surf_rgba;
-        mp.clo = closure_list(ctx);
-        mp.clo_rgba = (const float4 *)ctx->d_clo_rgba;
+        const arvx::McMeshParams mp = mesh_params(ctx, apply_unseen);
         ARVX_HIP(ctx->pool_mesh_off.reserve((size_t)(ccap + 1) * sizeof(int)));
         int *d_off = (int *)ctx->pool_mesh_off.p;
-        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, 3, nullptr))
+        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, Ctx::kTris, nullptr))
             return rc;
         hipLaunchKernelGGL(arvx::mc_weld_tri_kernel, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0,
                            ctx->stream, mp, arvx::SparseList{d_rank}, (const int4 *)ctx->d_mc_cells, ccap,
@@ -3102,19 +3098,11 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
                            ctx->stream, mp, (const int *)ctx->pool_weld_index.p, vcap, d_nverts,
                            (float *)ctx->pool_weld_verts.p, (float *)ctx->pool_weld_rgb.p);
         ARVX_HIP(hipGetLastError());
-        ARVX_SYNC(ctx);
-        ncells = host_total(ctx, 2);
-        ntris = host_total(ctx, 3);
-        nverts = host_total(ctx, 4);
-        if (ncells < 0 || ntris < 0 || nverts < 0) return fail(ARVX_ERR_HIP, "the scans left no count");
-        if ((ncells <= ccap && ntris <= tcap && nverts <= vcap) || attempt) break;
-        if (ncells > ccap) {
-            tcap = std::max(tcap, ntris + 5 * (ncells - ccap));
-            ccap = ncells + ncells / 8;
-        }
-        if (ntris > tcap) tcap = ntris + ntris / 8;
-        if (nverts > vcap) vcap = nverts + nverts / 8;
-    }
+        return ARVX_OK;
+    };
+    if (int rc = run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }))
+        return rc;
+    const long long ncells = lists[0].total, ntris = lists[1].total, nverts = lists[2].total;
     if (ncells == 0) ctx->d_mc_cells = nullptr;
     ctx->mc_count = ncells;
     ctx->mc_ready = true;
@@ -3172,9 +3160,9 @@ static int smooth_csr(Ctx *ctx) {
     hipLaunchKernelGGL(arvx::mc_smooth_degree_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
                        (const unsigned *)masks, V, ncount);
     ARVX_HIP(hipGetLastError());
-    // (slot 5: a total no call reads)
-    if (int rc = scan_counts(ctx, ncount, nullptr, V + 1, nullptr, noff, 5, nullptr)) return rc;
-    if (int rc = scan_counts(ctx, icount, nullptr, V + 1, nullptr, ioff, 5, nullptr)) return rc;
+    // (a total no call reads)
+    if (int rc = scan_counts(ctx, ncount, nullptr, V + 1, nullptr, noff, Ctx::kSmoothScan, nullptr)) return rc;
+    if (int rc = scan_counts(ctx, icount, nullptr, V + 1, nullptr, ioff, Ctx::kSmoothScan, nullptr)) return rc;
     hipLaunchKernelGGL(arvx::mc_smooth_neighbours_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
                        (const unsigned *)masks, V, index, ctx->X, ctx->Y,
                        arvx::SparseList{(const arvx::SparseWord *)ctx->pool_weld_rank.p}, (const int *)noff,
@@ -3290,15 +3278,11 @@ static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *
     const long long n = ctx->weld_verts;
     ARVX_HIP(ctx->pool_render_keys.reserve(npix * sizeof(unsigned long long)));
     ARVX_HIP(ctx->pool_render_img.reserve(npix * 11));
-    // large footprints: room for what a render wanted to list (an eighth more), at least a quarter
-    // of the vertices and 64 Ki more, never more than there are vertices; what does not fit is
-    // swept by the splat's own waves, so the capacity changes the time and never the images.
-    // render_need is the page-locked word as it stood at the last synchronisation of a render call
+    // large footprints (large_list_cap): never more than there are vertices.
+    // render_need is the count word as it stood at the last synchronisation of a render call
     // (arvx_render_download, arvx_render_agreement): renders launched back to back without one all
     // use the same capacity, whatever the device has finished by then.
-    const long long need = ctx->render_need;
-    const long long want = std::max((1ll << 16) + n / 4, need + need / 8);
-    const unsigned large_cap = (unsigned)std::min<long long>({n, want, (long long)UINT32_MAX});
+    const unsigned large_cap = large_list_cap(n, ctx->render_need, n);
     ARVX_HIP(ctx->pool_render_large.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
     ctx->render_W = W;
     ctx->render_H = H;
@@ -3343,14 +3327,13 @@ static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *
         sp.large_cap = large_cap;
         // (the grid strides over the list)
         const dim3 sgrid((unsigned)std::min<long long>((n + 255) / 256, 8 * ncu));
-        if (ctx->assoc == ARVX_ASSOC_LEFT)
-            hipLaunchKernelGGL(arvx::render_splat_kernel<true>, sgrid, dim3(256), 0, ctx->stream, sp);
-        else
-            hipLaunchKernelGGL(arvx::render_splat_kernel<false>, sgrid, dim3(256), 0, ctx->stream, sp);
+        by_assoc(ctx, [&](auto left) {
+            hipLaunchKernelGGL(arvx::render_splat_kernel<decltype(left)::value>, sgrid, dim3(256), 0, ctx->stream, sp);
+        });
         ARVX_HIP(hipGetLastError());
         hipLaunchKernelGGL(arvx::render_splat_large_kernel, dim3((unsigned)(4 * ncu)), dim3(256), 0, ctx->stream,
                            (const arvx::SplatRect *)large, (const unsigned *)&head->n_large, large_cap, keys, W,
-                           ctx->d_render_host);
+                           ctx->word_dev(Ctx::kRenderNeed));
         ARVX_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(arvx::render_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
@@ -3391,7 +3374,7 @@ int arvx_render_download(arvx_ctx *ctx, uint8_t *bgr, float *depth, int32_t *id)
         ARVX_HIP(hipMemcpyAsync(depth, render_depth(ctx), npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (id) ARVX_HIP(hipMemcpyAsync(id, render_id(ctx), npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);
-    ctx->render_need = std::max(ctx->h_render[0], 0ll);
+    ctx->render_need = std::max(ctx->word(Ctx::kRenderNeed), 0ll);
     return ARVX_OK;
 }
 
@@ -3403,19 +3386,19 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]) {
     if (int rc = render_launch(ctx, ctx->h_M.data() + 12 * (size_t)view, ctx->W, ctx->H, nullptr, 0)) return rc;
     const size_t npix = (size_t)ctx->W * ctx->H;
     arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
-    for (int k = 1; k <= 3; ++k) ctx->h_render[k] = -1;
+    for (int k = 0; k < 3; ++k) ctx->word(Ctx::kRenderAgree + k) = -1;
     hipLaunchKernelGGL(arvx::render_agreement_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
                        ctx->stream, (const int *)render_id(ctx), npix,
                        (const uint32_t *)(ctx->bg() + (size_t)view * ctx->bgWords), head->counts);
     ARVX_HIP(hipGetLastError());
     hipLaunchKernelGGL(arvx::render_counts_out_kernel, dim3(1), dim3(64), 0, ctx->stream,
-                       (const unsigned long long *)head->counts, ctx->d_render_host + 1);
+                       (const unsigned long long *)head->counts, ctx->word_dev(Ctx::kRenderAgree));
     ARVX_HIP(hipGetLastError());
     ARVX_SYNC(ctx);
-    ctx->render_need = std::max(ctx->h_render[0], 0ll);
+    ctx->render_need = std::max(ctx->word(Ctx::kRenderNeed), 0ll);
     for (int k = 0; k < 3; ++k) {
-        if (ctx->h_render[k + 1] < 0) return fail(ARVX_ERR_HIP, "the agreement left no count");
-        counts[k] = ctx->h_render[k + 1];
+        if (ctx->word(Ctx::kRenderAgree + k) < 0) return fail(ARVX_ERR_HIP, "the agreement left no count");
+        counts[k] = ctx->word(Ctx::kRenderAgree + k);
     }
     return ARVX_OK;
 }

@@ -67,12 +67,29 @@ struct Ctx {
     // tests/test_fault_gpu.py through the experiment build's arvx_experiment_mark_fault.
     unsigned *h_fault = nullptr;  // host address
     unsigned *d_fault = nullptr;  // the same word as the device sees it
+    // The count words: 8-byte words of the same page-locked block, from byte 8 on, that kernels write
+    // a length or a count to and the host reads after the call's synchronisation.  One word per
+    // user, none shared.  The list lengths also have a copy on the device, for the kernels that
+    // follow in the same call (arvx_capi.hip, device_total): the words below kDeviceTotals.
+    enum Word {
+        kSurface, kClosure, kCells, kTris, kVerts,  // list lengths, in the device copies' order
+        kSmoothScan,                    // arvx_mc_mesh_smooth's offset scans: a total nobody reads
+        kDeviceTotals,
+        kPhotoRemoved = kDeviceTotals,  // voxels an iteration of arvx_photo_carve removed
+        kVisNeed,                       // large footprints the visible pass wanted to list
+        kPacketOcc, kPacketSeen,        // arvx_state_download_packets: the two packets' words
+        kRenderNeed, kRenderAgree,      // the render's large footprints; three agreement counts in a row
+        kWords = kRenderAgree + 3
+    };
+    static constexpr size_t kHostBlockBytes = 128;
+    static_assert(8 + 8 * (size_t)kWords <= kHostBlockBytes, "the count words fit the block");
+    long long &word(int w) const { return ((long long *)(h_fault + 2))[w]; }      // host value
+    long long *word_dev(int w) const { return (long long *)(d_fault + 2) + w; }  // device address
     DevPool pool_vstrip;          // views_strip_kernel: ticket counters + published column counts
     size_t vstrip_key = 0;        // layout (V, strips, granules) the pool was zeroed for
 
     // scan_lookback_kernel (bitplane_kernels.h): ticket counter, device totals, status granules; and
-    // what the host keeps beside it.  h_totals: page-locked words behind the fault word that the
-    // kernels write the lists' lengths to (read at the call's one synchronisation).
+    // what the host keeps beside it.
     DevPool pool_compact;
     // set bits per kBitChunk words of the plane being compacted: two buffers of counts_stride
     // ints used in turn (the compaction that reads one zeroes the other: arvx_capi.hip, chunk_counts)
@@ -82,7 +99,6 @@ struct Ctx {
     bool counts_clean[2] = {false, false};
     unsigned long long compact_tickets = 0;  // tickets all launches so far have taken
     uint32_t compact_epoch = 0;
-    long long *h_totals = nullptr, *d_totals_host = nullptr;  // 6 slots (host / device address)
     long long surf_host_count = -1;  // entries of h_surf_index / h_surf_has that are valid (-1: fetch)
     long long clo_host_count = -1;   // ... of h_clo_index
 
@@ -298,9 +314,8 @@ struct Ctx {
     int smooth_q = 0;  // where the smoothed positions are: 0 the welded mesh's, 1 / 2 a buffer
 
     // arvx_render: the W x H keys, the images (id | depth | bgr), the large-footprint list behind
-    // its header (render_kernels.h), all sized at first use and kept.  h_render: page-locked words
-    // behind the totals -- the large footprints the last render wanted to list, then the three
-    // agreement counts.  The first is copied to render_need at a render call's synchronisation
+    // its header (render_kernels.h), all sized at first use and kept.  Count words: kRenderNeed, then
+    // the three agreement counts.  The first is copied to render_need at a render call's synchronisation
     // (download, agreement) and sizes the next renders' lists from there; the word itself is never
     // read while a kernel may be writing it.  A caller's background goes through a
     // page-locked staging buffer: the copy out of it is not waited for, so the event after it is
@@ -309,7 +324,6 @@ struct Ctx {
         pool_render_large{DevPool::Exact};
     int render_W = 0, render_H = 0;
     bool render_ready = false;
-    long long *h_render = nullptr, *d_render_host = nullptr;  // 4 words (host / device address)
     long long render_need = 0;
     uint8_t *h_render_bg = nullptr;
     size_t render_bg_cap = 0;

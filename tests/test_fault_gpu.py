@@ -2,9 +2,11 @@
 word, csrc/arvx_ctx.h): the call that synchronises next fails with ARVX_ERR_HIP, and the calls after
 it are correct again -- ticket counters, status granules, chunk counts and packets start from clean
 memory.  The mark itself is injected (libarvx_experiments.so: arvx_experiment_mark_fault): no kernel
-has ever been seen to leave one.  And the lists that outgrow their buffers: a context
-that has colour / closure / mesh lists sized for a small model is handed a large one -- the calls'
-second attempt, deterministically."""
+has ever been seen to leave one.  And lists sized by one model reused for a larger one: a
+context that has run the colour / closure / mesh stages on a small model is handed a large one.  (Its
+pools already have room -- a fresh 128^3 context reserves 135 168 entries per list, the large scene
+needs 22 563 and 43 076 --, so no call repeats its launches here: tests/test_list_retry_gpu.py forces
+the second attempt.)"""
 import ctypes as C
 import os
 
@@ -60,8 +62,10 @@ def test_failed_call_and_recovery(arvx):
 
 
 def test_lists_outgrow_their_buffers(arvx):
-    """Small model first (its lists size the buffers), then a large one on the same context: colour
-    pass, closure and mesh each repeat once with room for all; the results equal a fresh context's."""
+    """Small model first, then a large one on the same context: the lists of the large model go into
+    the buffers the small model's calls sized, and the results equal a fresh context's.  The buffers
+    have room for both (first-capacity rule), so this is the single-attempt path on reused
+    pools; the second attempt is tests/test_list_retry_gpu.py's."""
     N, V = 128, 6
     small = scenes.syn.sphere_scene(N, V, W=320, H=240, with_images=True, radius_factor=0.06)
     large = scenes.syn.sphere_scene(N, V, W=320, H=240, with_images=True)
