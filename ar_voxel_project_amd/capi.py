@@ -24,6 +24,17 @@ CARVE_FUSED = 8
 CARVE_STREAM = 16
 CARVE_FILTER = 64
 CARVE_NO_STREAM = 32
+# the large grids' kernel choice on a grid of any size (include/arvx/arvx.h: path flags)
+CARVE_DENSE_CLASSIFY = 128
+CARVE_WHOLE_ITEMS = 256
+# bits of Context.last_carve_path()["bits"] (ARVX_PATH_*)
+PATH_DENSE_CLASSIFY = 1
+PATH_ITEM_SHARING = 2
+PATH_FRESH = 4
+PATH_LAZY_CODES = 8
+PATH_FUSED = 16
+PATH_BRUTE_FORCE = 32
+PATH_STREAM = 64
 VOTES_COUNTS = 1
 VOTES_NO_CULL = 2
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
@@ -60,7 +71,8 @@ SYMBOLS = [
     "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
-    "arvx_export_model", "arvx_get_stats", "arvx_selftest_divide", "arvx_selftest_round",
+    "arvx_export_model", "arvx_get_stats", "arvx_last_carve_path", "arvx_selftest_divide",
+    "arvx_selftest_round",
 ]
 
 
@@ -158,6 +170,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.arvx_closure_download.argtypes = [p, C.POINTER(C.c_int64), f32p]
     lib.arvx_export_model.argtypes = [p, f32p, C.c_int]
     lib.arvx_get_stats.argtypes = [p, C.POINTER(Stats)]
+    if hasattr(lib, "arvx_last_carve_path"):
+        lib.arvx_last_carve_path.argtypes = [p, C.POINTER(C.c_uint32)]
     ab_build = bool(os.environ.get("ARVX_LIB_PATH"))  # an older build may lack newer symbols
     if hasattr(lib, "arvx_selftest_divide") or not ab_build:
         lib.arvx_selftest_divide.argtypes = [p, C.c_int64, f32p, f32p, f32p, f32p]
@@ -544,6 +558,15 @@ class Context:
 
     def carve_views(self, first: int, count: int, flags: int = 0) -> None:
         self._ck(self._lib.arvx_carve_views(self._h, first, count, flags | _EXTRA_CARVE_FLAGS))
+
+    def last_carve_path(self) -> dict:
+        """Which kernels the last carve of this context launched (PATH_* bits) and how much work
+        its pre-passes handed on: coarse tiles listed, workgroups of the dense classify kernel
+        (0: the other kernel ran), sub-tiles queued for the exact kernel.  Synchronises."""
+        out = (C.c_uint32 * 4)()
+        self._ck(self._lib.arvx_last_carve_path(self._h, out))
+        return {"bits": int(out[0]), "listed": int(out[1]), "dense_grid": int(out[2]),
+                "items": int(out[3])}
 
     def fast_carve(self) -> None:
         self._ck(self._lib.arvx_fast_carve(self._h))

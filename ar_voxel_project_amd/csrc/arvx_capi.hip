@@ -1496,6 +1496,7 @@ static int launch_carve_stream(Ctx *ctx, arvx::CarveParams p, int ncu) {
     ARVX_HIP(hipGetLastError());
     ctx->form = Form::Lazy;
     ctx->cstate_tiles = ncoarse;
+    ctx->path_bits = ARVX_PATH_STREAM | ARVX_PATH_FRESH | ARVX_PATH_LAZY_CODES;
     return ARVX_OK;
 }
 #endif
@@ -1534,6 +1535,8 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     const int ncu = ctx->ncu;
     size_t layout_when_done = 0;
     bool lazy = false;
+    ctx->path_bits = ctx->path_dense_grid = 0;  // (arvx_last_carve_path)
+    ctx->path_off_listed = ctx->path_off_work = 0;
     // a fresh model, the context's own records, up to 256 views: one persistent launch where the
     // caller asks for it (carve_stream_kernels.h; EXPERIMENTS.md, round 4: its sub-tile phase is
     // slower inside a launch of 128-register waves than as a launch of its own, so the three
@@ -1652,7 +1655,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     // (up to 2^26 voxels: above that there are more items than half the waves and the kernel
     // never splits; ARVX_ITEM_SPLIT_LOG2 in an experiment build moves the limit)
     static const int split_log2 = experiment_int("ARVX_ITEM_SPLIT_LOG2");
-    if (blocks && !no_item_split &&
+    if (blocks && !no_item_split && !(flags & ARVX_CARVE_WHOLE_ITEMS) &&
         (size_t)p.X * p.Y * p.Z <= ((size_t)1 << (split_log2 > 0 ? split_log2 : 26)))
         p.flags |= 8u;
     static const bool force_split = experiment_flag("ARVX_FORCE_SPLIT2");  // every item in 2 parts
@@ -1678,7 +1681,8 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         // (the statistics counters live in the other kernel; below 2^26 voxels there are too few
         // listed coarse tiles for a workgroup each: 256^3 +2.5 % with the dense kernel, 512^3
         // -1.5 %, 768^3 -5 %, 1024^3 -11 %)
-        const bool dense = !(flags & ARVX_CARVE_STATS) && (size_t)p.X * p.Y * p.Z >= ((size_t)1 << 26);
+        const bool dense = !(flags & ARVX_CARVE_STATS) &&
+                           ((flags & ARVX_CARVE_DENSE_CLASSIFY) || (size_t)p.X * p.Y * p.Z >= ((size_t)1 << 26));
 #else
         const bool dense = false;
 #endif
@@ -1745,6 +1749,12 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         ARVX_HIP(hipGetLastError());
         ctx->carve_layout = layout_when_done;
         ++ctx->carve_seq;
+        // (arvx_last_carve_path: all of it once every launch is out, or nothing)
+        ctx->path_bits = (dense ? ARVX_PATH_DENSE_CLASSIFY : 0u) | (may_split ? ARVX_PATH_ITEM_SHARING : 0u) |
+                         (fresh ? ARVX_PATH_FRESH : 0u) | (lazy ? ARVX_PATH_LAZY_CODES : 0u);
+        ctx->path_dense_grid = dense ? (unsigned)ncu * (unsigned)ARVX_DENSE_WGS_PER_CU : 0u;
+        ctx->path_off_listed = (size_t)((uint8_t *)p.undecidedCount - (uint8_t *)ctx->pool_coarse.p);
+        ctx->path_off_work = (size_t)((uint8_t *)p.workCount - (uint8_t *)ctx->pool_coarse.p);
         if (lazy && rec == ctx->rec()) ctx->form = Form::Lazy;
         if (p.cstate) ctx->cstate_tiles = ncoarse;
         return ARVX_OK;
@@ -1757,6 +1767,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     else
         hipLaunchKernelGGL(arvx::carve_fused_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, p);
     ARVX_HIP(hipGetLastError());
+    ctx->path_bits = (cull ? ARVX_PATH_FUSED : ARVX_PATH_BRUTE_FORCE) | (fresh ? ARVX_PATH_FRESH : 0u);
     return ARVX_OK;
 }
 
@@ -1789,6 +1800,27 @@ int arvx_carve_views(arvx_ctx *ctx, int first, int count, unsigned flags) {
 int arvx_carve(arvx_ctx *ctx, unsigned flags) {
     if (!ctx) return fail(ARVX_ERR_INVALID, "null context");
     return arvx_carve_views(ctx, 0, ctx->V, flags);
+}
+
+int arvx_last_carve_path(arvx_ctx *ctx, uint32_t out[4]) {
+    ARVX_CHECK_CTX(ctx);
+    if (!out) return fail(ARVX_ERR_INVALID, "null out");
+    out[0] = ctx->path_bits;
+    out[1] = out[3] = 0;
+    out[2] = ctx->path_dense_grid;
+    ARVX_SYNC(ctx);
+    if (!ctx->path_off_listed) return ARVX_OK;  // no list, no queues (or no carve yet)
+    int listed = 0;
+    int counts[arvx::kWorkLists];  // (one padded counter per list: gathered by a strided copy)
+    const uint8_t *base = (const uint8_t *)ctx->pool_coarse.p;
+    ARVX_HIP(hipMemcpy(&listed, base + ctx->path_off_listed, sizeof listed, hipMemcpyDeviceToHost));
+    ARVX_HIP(hipMemcpy2D(counts, sizeof(int), base + ctx->path_off_work, arvx::kCounterStride * sizeof(int),
+                         sizeof(int), arvx::kWorkLists, hipMemcpyDeviceToHost));
+    uint64_t items = 0;
+    for (int l = 0; l < arvx::kWorkLists; ++l) items += (uint64_t)counts[l];
+    out[1] = (uint32_t)listed;
+    out[3] = (uint32_t)items;
+    return ARVX_OK;
 }
 
 // ---- vote carve (vote_kernels.h) ----------------------------------------------------------------

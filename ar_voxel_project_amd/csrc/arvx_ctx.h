@@ -144,6 +144,10 @@ struct Ctx {
     int ncu = 0;                 // compute units of the device (cached)
     int carve_seq = 0;           // parity of the undecided-list counters (carve_coarse_kernel)
     size_t carve_layout = 0;     // pool_coarse layout those counters were zeroed for
+    // arvx_last_carve_path: the last launch_carve's ARVX_PATH_* bits, its dense classify grid, and
+    // where in pool_coarse its list length and work-list counters are (0: it had none)
+    unsigned path_bits = 0, path_dense_grid = 0;
+    size_t path_off_listed = 0, path_off_work = 0;
     // the streaming carve (carve_stream_kernels.h): control block + list entries + item queues
     DevPool pool_stream{DevPool::Exact};
     size_t stream_layout = 0;    // layout the control block was zeroed for (0: zero it again)

@@ -66,6 +66,16 @@ enum {
                                     the filter's error of a rounding tie: the same model bit for bit, but
                                     1.16-1.23x SLOWER than the exact kernel (EXPERIMENTS.md round 5) --
                                     compiled only into -DARVX_EXPERIMENTS builds like ARVX_CARVE_STREAM */
+/* Path flags: the split carve chooses two of its kernels by the number of voxels.
+ * These take the large grids' choice on a grid of any size, so that small test scenes run the
+ * kernels that carve 512^3 and 1024^3.  The model is the same bit for bit under every combination.
+ * They are ignored where the split carve does not run or the choice does not exist: under
+ * ARVX_CARVE_NO_CULL, ARVX_CARVE_FUSED and ARVX_CARVE_STATS, and with more than 256 views. */
+#define ARVX_CARVE_DENSE_CLASSIFY 128u /* the sub-tile classification of grids of 2^26 voxels and more:
+                                          a workgroup per listed coarse tile (or quarter), lanes =
+                                          (sub-tile, view) pairs */
+#define ARVX_CARVE_WHOLE_ITEMS 256u    /* the exact kernel of grids above 2^26 voxels: an item is never
+                                          shared between waves */
 
 /* colour modes: reference -color=1 / -color=2 (src/main.cpp:276-288) */
 #define ARVX_COLOR_CLOSEST 0
@@ -633,6 +643,25 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]);
 int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen);
 
 int arvx_get_stats(arvx_ctx *ctx, arvx_stats *out);
+
+/* Diagnostic: which kernels the context's last arvx_carve / arvx_carve_views (or the carve inside
+ * arvx_fast_carve) launched, and how much work its pre-passes handed on.  For tests that must know
+ * they ran the path they meant to; synchronises, not for the hot path.
+ *   out[0]  ARVX_PATH_* bits, as the host chose them (0: the context has not carved yet)
+ *   out[1]  coarse tiles the carve listed for the sub-tile classification
+ *   out[2]  workgroups of the dense classify kernel's launch (0: the other kernel ran)
+ *   out[3]  sub-tiles queued for the exact kernel, over all work lists
+ * out[1] and out[3] are 0 where the split carve did not run (ARVX_PATH_FUSED, ARVX_PATH_BRUTE_FORCE,
+ * ARVX_PATH_STREAM).  They are read from the carve's work buffer, which the next carve of the
+ * context reuses: call this before it. */
+#define ARVX_PATH_DENSE_CLASSIFY 1u /* carve_classify_dense_kernel, not carve_classify_kernel */
+#define ARVX_PATH_ITEM_SHARING 2u   /* the exact kernel may hand an item's views to several waves */
+#define ARVX_PATH_FRESH 4u          /* the model was fresh: nothing read, every record written */
+#define ARVX_PATH_LAZY_CODES 8u     /* decided coarse tiles were left as codes, not written */
+#define ARVX_PATH_FUSED 16u         /* one kernel for rectangle tests and voxels (FUSED, > 256 views) */
+#define ARVX_PATH_BRUTE_FORCE 32u   /* no rectangle tests at all (ARVX_CARVE_NO_CULL) */
+#define ARVX_PATH_STREAM 64u        /* the one-launch streaming carve (-DARVX_EXPERIMENTS builds) */
+int arvx_last_carve_path(arvx_ctx *ctx, uint32_t out[4]);
 
 /* Self-test hook: evaluates the kernel's shared-reciprocal division and the IEEE
  * `/` on n host operand triples; out gets 4 floats per triple:

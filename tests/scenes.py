@@ -46,6 +46,45 @@ def random_cameras(V, extent, seed=0, W=160, H=120, inside=False):
     return K32, Rt32, syn.compose_m(K32, Rt32)
 
 
+def flat_view(X, Y, s):
+    """One view that looks along z: pixel (u, v) = voxel (x, y) (Model::toWord swaps x and y)."""
+    M = np.zeros((1, 3, 4), np.float32)
+    M[0, 0, 1] = 1.0 / s  # u = world[1] / s = x
+    M[0, 1, 0] = 1.0 / s  # v = world[0] / s = y
+    M[0, 2, 3] = 1.0
+    return M
+
+
+EXTREME_GEOMETRY_CASES = ["tiny_voxels", "huge_voxels", "long_focal", "short_focal", "far_camera",
+                          "offcentre_principal", "grazing"]
+
+
+def extreme_geometry(case):
+    """(N, V, W, H, s, M) of one of EXTREME_GEOMETRY_CASES: a cube grid and cameras that push what
+    the margins of the rectangle tests scale with -- |M|, |w| and 1/depth."""
+    N, V, W, H = 40, 5, 200, 150
+    rng = np.random.default_rng(sum(ord(c) for c in case))  # fixed per case
+    s = {"tiny_voxels": 1e-4, "huge_voxels": 7.5}.get(case, 0.512 / N)
+    E = s * N
+    f = {"long_focal": 6000.0, "short_focal": 25.0}.get(case, 160.0)
+    cxp, cyp = (W / 2, H / 2) if case != "offcentre_principal" else (-300.0, 900.0)
+    K = np.array([[f, 0, cxp], [0, f * 1.01, cyp], [0, 0, 1]], np.float64)
+    centre = np.array([E / 2, E / 2, -E / 2])
+    Rts = []
+    for i in range(V):
+        d = {"far_camera": 200.0, "grazing": 0.75}.get(case, 2.0) * E
+        dirv = rng.normal(size=3)
+        dirv /= np.linalg.norm(dirv)
+        cam = centre + d * dirv
+        target = centre + rng.normal(scale=0.2 * E, size=3)
+        if case == "grazing":  # look along a face of the grid: many voxels near depth 0
+            target = cam + np.array([1.0, 0.02, 0.01]) * E
+        Rts.append(syn.look_at_rt(cam, target, rng.normal(size=3)))
+    Rt = np.array(Rts).astype(np.float32)
+    M = syn.compose_m(K.astype(np.float32), Rt)
+    return N, V, W, H, s, M
+
+
 def assoc_kat(N=2):
     """One view on which the two groupings of the M*world row sum put voxel
     (1,1,1) on different pixels.  With s = 1 the voxel's world vector is (1, 1, -1, 1), so the

@@ -406,15 +406,6 @@ def test_cull_matches_no_cull_bench_scene_512(arvx):
     assert abs(float((a & 1).mean()) - 0.1806) < 0.001
 
 
-def _flat_views(X, Y, s):
-    """One view that looks along z: pixel (u, v) = voxel (x, y) (Model::toWord swaps x and y)."""
-    M = np.zeros((1, 3, 4), np.float32)
-    M[0, 0, 1] = 1.0 / s  # u = world[1] / s = x
-    M[0, 1, 0] = 1.0 / s  # v = world[0] / s = y
-    M[0, 2, 3] = 1.0
-    return M
-
-
 def test_tile_summary_is_dropped_when_something_else_writes_the_state(arvx, oracle):
     """A carve remembers which coarse tiles (64 x 32 x 32 voxels) it emptied as a whole and a
     later carve of the same model skips them (CarveParams::cstate).  Carving cannot undo that --
@@ -424,7 +415,7 @@ def test_tile_summary_is_dropped_when_something_else_writes_the_state(arvx, orac
       * the closure (a dilation: reference F10) puts voxels of row y = 31 back: carved again."""
     X, Y, Z = 64, 96, 64
     s = np.float32(0.01)
-    M = _flat_views(X, Y, s)
+    M = scenes.flat_view(X, Y, s)
     masks = np.full((1, Y, X), 255, np.uint8)
     masks[0, :32, :] = 0
     want1 = oracle.carve(X, Y, Z, s, M, masks)
@@ -532,30 +523,10 @@ def test_dataset_silhouettes_plumbing(arvx, oracle, which, N):
     assert 0.0 < (want & 1).mean() < 1.0
 
 
-@pytest.mark.parametrize("case", ["tiny_voxels", "huge_voxels", "long_focal", "short_focal",
-                                  "far_camera", "offcentre_principal", "grazing"])
+@pytest.mark.parametrize("case", scenes.EXTREME_GEOMETRY_CASES)
 def test_extreme_geometry(arvx, oracle, case):
     """Margins of the rectangle tests scale with |M|, |w| and 1/depth: push each."""
-    N, V, W, H = 40, 5, 200, 150
-    rng = np.random.default_rng(sum(ord(c) for c in case))  # fixed per case
-    s = {"tiny_voxels": 1e-4, "huge_voxels": 7.5}.get(case, 0.512 / N)
-    E = s * N
-    f = {"long_focal": 6000.0, "short_focal": 25.0}.get(case, 160.0)
-    cxp, cyp = (W / 2, H / 2) if case != "offcentre_principal" else (-300.0, 900.0)
-    K = np.array([[f, 0, cxp], [0, f * 1.01, cyp], [0, 0, 1]], np.float64)
-    centre = np.array([E / 2, E / 2, -E / 2])
-    Rts = []
-    for i in range(V):
-        d = {"far_camera": 200.0, "grazing": 0.75}.get(case, 2.0) * E
-        dirv = rng.normal(size=3)
-        dirv /= np.linalg.norm(dirv)
-        cam = centre + d * dirv
-        target = centre + rng.normal(scale=0.2 * E, size=3)
-        if case == "grazing":  # look along a face of the grid: many voxels near depth 0
-            target = cam + np.array([1.0, 0.02, 0.01]) * E
-        Rts.append(scenes.syn.look_at_rt(cam, target, rng.normal(size=3)))
-    Rt = np.array(Rts).astype(np.float32)
-    M = scenes.syn.compose_m(K.astype(np.float32), Rt)
+    N, V, W, H, s, M = scenes.extreme_geometry(case)
     for block in (1, 12):
         masks = scenes.noise_masks(V, H, W, block=block, p_bg=0.5, seed=block)
         want = oracle.carve(N, N, N, np.float32(s), M, masks)

@@ -23,6 +23,7 @@ t_end = time.time() + budget
 n = 0
 while time.time() < t_end:
     big = rng.random() < 0.25
+    flags = 0
     if big:  # around 2^26 voxels (dense classify kernel, whole coarse tiles or quarters)
         X = int(rng.choice([384, 400, 416, 448, 512])) + int(rng.integers(-3, 4))
         Y = int(rng.choice([384, 400, 416, 448])) + int(rng.integers(-3, 4))
@@ -33,6 +34,8 @@ while time.time() < t_end:
             zr = (z0, z0 + int(rng.integers(8, 40)))
     else:
         X, Y, Z = (int(v) for v in rng.integers(5, 200, 3))
+        # the large grids' kernels on a small grid (include/arvx/arvx.h: path flags)
+        flags = int(rng.choice([0, capi.CARVE_DENSE_CLASSIFY])) | int(rng.choice([0, capi.CARVE_WHOLE_ITEMS]))
         zr = None
         if rng.random() < 0.3 and Z > 12:
             z0 = int(rng.integers(0, Z - 4))
@@ -52,23 +55,23 @@ while time.time() < t_end:
     with capi.Context(X, Y, Z, s, z_range=zr) as ctx:
         ctx.set_views(M, masks)
         if mode == 0:
-            ctx.carve()
+            ctx.carve(flags)
         elif mode == 1:  # twice: the second carve on a model that is not fresh
-            ctx.carve()
-            ctx.carve()
+            ctx.carve(flags)
+            ctx.carve(flags)
         elif mode == 2:  # the views in two pieces, the later ones first
             k = int(rng.integers(0, V + 1))
             if V - k:
-                ctx.carve_views(k, V - k)
+                ctx.carve_views(k, V - k, flags)
             if k:
-                ctx.carve_views(0, k)
+                ctx.carve_views(0, k, flags)
         else:  # view by view
             for i in rng.permutation(V):
-                ctx.carve_views(int(i), 1)
+                ctx.carve_views(int(i), 1, flags)
         got = ctx.download_state()
     if not np.array_equal(got, want):
         bad = np.argwhere(got != want)
-        print(f"MISMATCH case {n}: {X}x{Y}x{Z} z{zr} V={V} {W}x{H} mode {mode}: {len(bad)} voxels, "
+        print(f"MISMATCH case {n}: {X}x{Y}x{Z} z{zr} V={V} {W}x{H} mode {mode} flags {flags}: {len(bad)} voxels, "
               f"first {bad[0]} gpu {got[tuple(bad[0])]} oracle {want[tuple(bad[0])]}", flush=True)
         sys.exit(1)
     n += 1
