@@ -1,10 +1,10 @@
 /*
  * arvx_oracle.c -- CPU restatement of the AR_Voxel_Project carving hot path.
  *
- * TEST INFRASTRUCTURE ONLY (see arvx_oracle.h).  PARITY PARTLY PINNED: marching cubes,
- * surface selection and closure geometry against the reference's own 1.off, the face-colour
- * rule against its 2.off / 3.off; the cv::gemm / cv::norm arithmetic of the carve path is
- * unpinned (the reference cannot be built here).
+ * TEST INFRASTRUCTURE ONLY (see arvx_oracle.h).  PARITY: every loop below is pinned by running
+ * the reference's own sources (oracle/_ref/arvx_ref, tests/test_reference_cpu.py); the
+ * cv::gemm / cv::norm arithmetic of the carve path is unpinned (the stand-ins that binary is
+ * built on state it as this file does).
  *
  * Every function cites the reference lines it follows (paths relative to the
  * reference checkout).  Two third-party calls sit on the path; their

@@ -5,18 +5,19 @@
  * may include, link or load this file.  Allowed users: tests/,
  * __graft_entry__.smoke() and bench.py's cpu_baseline leg.
  *
- * PARITY: PARTLY PINNED.  The reference has no unit tests or golden vectors at the level of
- * this path and cannot be built in this image (OpenCV + Eigen3 absent).
- * Pinned against the reference's own Data/box_dataset/generated_models/1.off (fixture
- * tests/golden/box_off1.npz, tools/make_off_fixture.py; tests/test_mc_off.py): the marching
- * cubes + OFF writer restatement reproduces the file byte for byte, the surface selection
- * (Model::isInner) is the file's vertex set, the closure is the one dilation the file's model
- * is the image of; 2.off / 3.off (box_off23.npz) decide the face-colour rule (third corner =
- * second corner's colour, then round(sum / 3)) and are reproduced byte for byte on a voxel
- * colouring they admit.  UNPINNED: the arithmetic of the two third-party calls on the carve path
- * (cv::gemm, cv::norm; opencv 4.6.x, unpinned in the reference's CMakeLists.txt:16), restated
- * from the published source, see arvx_oracle.c -- in particular the grouping of the M*world
- * row sums, for which both candidates are built and told apart by a test.
+ * PARITY: PINNED BY EXECUTION, third-party arithmetic excepted.  oracle/_ref/arvx_ref (oracle/Makefile,
+ * ref_driver.cpp) is the reference's own Model.cpp, VoxelCarving.cpp, ColorReconstruction.cpp,
+ * Postprocessing3d.cpp and MarchingCubes.cpp compiled against the functional OpenCV / Eigen stand-ins
+ * of oracle/ref_standins/; tests/test_reference_cpu.py runs it and this file on the same inputs and
+ * compares bit for bit: carve, fastCarve, addColor + closest / average, isInner, handleUnseen, the
+ * closure (geometry and colour means), voxels behind / at depth 0 of a camera, marching cubes and the
+ * OFF writer all agree.  Also pinned against the reference's own Data/box_dataset/generated_models/
+ * 1.off, 2.off, 3.off (tests/golden/box_off1.npz, box_off23.npz; tests/test_mc_off.py).
+ * UNPINNED: the arithmetic of the third-party calls -- cv::gemm (in particular the grouping of the
+ * M*world row sums, for which both candidates are built and told apart by a test), cv::norm,
+ * cv::undistort, cv::Rodrigues, Mat::inv (opencv 4.6.x, unpinned in the reference's
+ * CMakeLists.txt:16) and Eigen's fp32 coefficient ops.  The stand-ins state them exactly as
+ * arvx_oracle.c does (restated from the published sources), so the comparison cannot tell.
  *
  * State plane convention (one byte per voxel, index x + X*(y + Y*z), the
  * reference's Model::flatten, src/Model.h:104-106):
