@@ -35,6 +35,9 @@ PATH_LAZY_CODES = 8
 PATH_FUSED = 16
 PATH_BRUTE_FORCE = 32
 PATH_STREAM = 64
+# bits of Context.last_fast_carve_path()["bits"] (ARVX_FLOOD_*)
+FLOOD_PREPASS = 1
+FLOOD_FRESH = 2
 VOTES_COUNTS = 1
 VOTES_NO_CULL = 2
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
@@ -71,7 +74,8 @@ SYMBOLS = [
     "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
-    "arvx_export_model", "arvx_get_stats", "arvx_last_carve_path", "arvx_selftest_divide",
+    "arvx_export_model", "arvx_get_stats", "arvx_last_carve_path", "arvx_last_fast_carve_path",
+    "arvx_selftest_divide",
     "arvx_selftest_round",
 ]
 
@@ -172,6 +176,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.arvx_get_stats.argtypes = [p, C.POINTER(Stats)]
     if hasattr(lib, "arvx_last_carve_path"):
         lib.arvx_last_carve_path.argtypes = [p, C.POINTER(C.c_uint32)]
+    if hasattr(lib, "arvx_last_fast_carve_path"):
+        lib.arvx_last_fast_carve_path.argtypes = [p, C.POINTER(C.c_uint32)]
     ab_build = bool(os.environ.get("ARVX_LIB_PATH"))  # an older build may lack newer symbols
     if hasattr(lib, "arvx_selftest_divide") or not ab_build:
         lib.arvx_selftest_divide.argtypes = [p, C.c_int64, f32p, f32p, f32p, f32p]
@@ -570,6 +576,15 @@ class Context:
 
     def fast_carve(self) -> None:
         self._ck(self._lib.arvx_fast_carve(self._h))
+
+    def last_fast_carve_path(self) -> dict:
+        """How the last greedy carve of this context grew its component: FLOOD_* bits, the tiles
+        its whole-tile pre-pass seeded (0 without one), the launches of its step kernel and its
+        rows of tiles.  All zero before the first greedy carve.  Synchronises."""
+        out = (C.c_uint32 * 4)()
+        self._ck(self._lib.arvx_last_fast_carve_path(self._h, out))
+        return {"bits": int(out[0]), "seeded": int(out[1]), "launches": int(out[2]),
+                "tile_rows": int(out[3])}
 
     def color(self, mode: int) -> None:
         self._ck(self._lib.arvx_color(self._h, mode))

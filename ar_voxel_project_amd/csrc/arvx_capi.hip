@@ -3565,6 +3565,30 @@ int arvx_fast_carve(arvx_ctx *ctx) {
     ARVX_HIP(hipGetLastError());
     ctx->form = Form::Records;  // the records now hold every voxel's state
     ARVX_SYNC(ctx);
+    // (arvx_last_fast_carve_path: all of it once the carve is through, or nothing)
+    ctx->flood_bits = (prepass ? ARVX_FLOOD_PREPASS : 0u) | (fp.fresh ? ARVX_FLOOD_FRESH : 0u);
+    ctx->flood_launches = (unsigned)launched;
+    ctx->flood_tile_rows = (unsigned)tile_rows;
+    ctx->flood_off_reached = prepass ? o_tiles + (size_t)tile_rows * sizeof(unsigned long long) : 0;
+    return ARVX_OK;
+}
+
+int arvx_last_fast_carve_path(arvx_ctx *ctx, uint32_t out[4]) {
+    ARVX_CHECK_CTX(ctx);
+    if (!out) return fail(ARVX_ERR_INVALID, "null out");
+    out[0] = ctx->flood_bits;
+    out[1] = 0;
+    out[2] = ctx->flood_launches;
+    out[3] = ctx->flood_tile_rows;
+    if (!ctx->flood_off_reached) return ARVX_OK;  // no pre-pass (or no greedy carve yet)
+    // the rows the pre-pass left in the work buffer: bit xw of row (ty, tz) = tile seeded
+    std::vector<unsigned long long> rows(ctx->flood_tile_rows);
+    ARVX_SYNC(ctx);
+    ARVX_HIP(hipMemcpy(rows.data(), (const uint8_t *)ctx->pool_flood.p + ctx->flood_off_reached,
+                       rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    uint32_t seeded = 0;
+    for (unsigned long long w : rows) seeded += (uint32_t)__builtin_popcountll(w);
+    out[1] = seeded;
     return ARVX_OK;
 }
 

@@ -148,6 +148,12 @@ struct Ctx {
     // where in pool_coarse its list length and work-list counters are (0: it had none)
     unsigned path_bits = 0, path_dense_grid = 0;
     size_t path_off_listed = 0, path_off_work = 0;
+    // arvx_last_fast_carve_path: the last arvx_fast_carve's ARVX_FLOOD_* bits, its flood_step_kernel
+    // launches and its tile rows, and where in pool_flood the whole-tile pre-pass left its `reached`
+    // rows (0: it did not run).  All zero before the first greedy carve and once the state it left
+    // has been replaced (drop).
+    unsigned flood_bits = 0, flood_launches = 0, flood_tile_rows = 0;
+    size_t flood_off_reached = 0;
     // the streaming carve (carve_stream_kernels.h): control block + list entries + item queues
     DevPool pool_stream{DevPool::Exact};
     size_t stream_layout = 0;    // layout the control block was zeroed for (0: zero it again)
@@ -281,6 +287,10 @@ struct Ctx {
         if (r.paint == 1 || (r.paint == 2 && nvox_ext == nvox)) paint_valid = false;
         if (r.cstate) cstate_tiles = 0;
         if (r.state) next_state(r.state == 2);
+        if (r.state == 1) {  // (the greedy carve's report describes the carve that left the state)
+            flood_bits = flood_launches = flood_tile_rows = 0;
+            flood_off_reached = 0;
+        }
         if (r.render) render_ready = false;
         if (r.votes) votes_ready = false;
     }

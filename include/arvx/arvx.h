@@ -663,6 +663,20 @@ int arvx_get_stats(arvx_ctx *ctx, arvx_stats *out);
 #define ARVX_PATH_STREAM 64u        /* the one-launch streaming carve (-DARVX_EXPERIMENTS builds) */
 int arvx_last_carve_path(arvx_ctx *ctx, uint32_t out[4]);
 
+/* Diagnostic: how the context's last arvx_fast_carve grew its component.  Host bookkeeping; the
+ * greedy carve itself launches, copies and waits for nothing more on its account.
+ *   out[0]  ARVX_FLOOD_* bits
+ *   out[1]  64x16x16 tiles the whole-tile pre-pass seeded (0 without a pre-pass)
+ *   out[2]  launches of the word-level step kernel, in batches of 4, 4, 8, 8, ...
+ *   out[3]  rows of tiles, ceil(Y / 16) * ceil(Z / 16): the pre-pass runs up to 4096 of them
+ * out[1] is counted on request from the rows the pre-pass left in the greedy carve's work buffer
+ * (8 bytes per row of tiles, copied and counted on the host; synchronises).  All four are 0 before
+ * the first greedy carve and after a call that replaces the state it left (carve, photo carve,
+ * closure, state upload, reset). */
+#define ARVX_FLOOD_PREPASS 1u /* the whole-tile pre-pass ran (at most 64 words per row, 4096 tile rows) */
+#define ARVX_FLOOD_FRESH 2u   /* the model was fresh: its records were not read, all were written */
+int arvx_last_fast_carve_path(arvx_ctx *ctx, uint32_t out[4]);
+
 /* Self-test hook: evaluates the kernel's shared-reciprocal division and the IEEE
  * `/` on n host operand triples; out gets 4 floats per triple:
  * (a0/b fast, a1/b fast, a0/b IEEE, a1/b IEEE). */

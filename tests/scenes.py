@@ -105,3 +105,110 @@ def assoc_kat(N=2):
     yy, xx = np.mgrid[0:H, 0:W]
     masks = (((xx + yy) % 2 == 1) * 255).astype(np.uint8)[None]
     return N, N, N, np.float32(1.0), M, masks, (1, 1, 1), 3, 2
+
+
+# ---- axis views and wall images (the greedy carve's scenes) -------------------------------------
+# Exact for a voxel size that is a power of two: Model::toWord gives (y s, x s, -z s, 1), so a
+# row 1/s * world is the voxel coordinate itself.  A foreground line of one pixel in the image of
+# such a view is a wall through the whole grid along the third axis; a background image makes
+# every voxel carvable.  Images are indexed [v, u]: wall images below are B rows of A pixels,
+# a = the view's u axis, b = its v axis.
+
+def axis_view(axes, s):
+    """One view with pixel (u, v) = voxel (y, z), (x, z) or (x, y): axes "yz", "xz", "xy"."""
+    if axes == "xy":
+        return flat_view(0, 0, s)
+    M = np.zeros((1, 3, 4), np.float32)
+    M[0, 0, {"yz": 0, "xz": 1}[axes]] = 1.0 / s  # u = world[0] / s = y, or world[1] / s = x
+    M[0, 1, 2] = -1.0 / s                        # v = -world[2] / s = z
+    M[0, 2, 3] = 1.0
+    return M
+
+
+def image_shape(axes, X, Y, Z):
+    """(B, A) of the wall image of axis_view(axes) over an X x Y x Z grid."""
+    return {"yz": (Z, Y), "xz": (Z, X), "xy": (Y, X)}[axes]
+
+
+def _pair(v):
+    return (v, v) if np.isscalar(v) else tuple(v)
+
+
+def _segment(img, p, q):
+    (a0, b0), (a1, b1) = p, q
+    img[min(b0, b1):max(b0, b1) + 1, min(a0, a1):max(a0, a1) + 1] = 255
+
+
+def spiral_walls(A, B, pitch, off=7, turns=None):
+    """A rectangular spiral of one-pixel walls, wound inwards from the corner (0, 0): one polyline
+    whose k-th turn lies off + k * pitch inside the image, so the corridor between two turns is
+    pitch - 1 pixels wide and the way through it bends right, down, left and up, turn after turn,
+    until the next bend no longer fits.  With off = 7 and a pitch that is a multiple of the tile
+    edge no wall lies on the tile raster.  pitch and off may be (a, b) pairs; `turns` ends the
+    spiral after that many straight walls and leaves a room in the middle."""
+    (pa, pb), (oa, ob) = _pair(pitch), _pair(off)
+    img = np.zeros((B, A), np.uint8)
+    prev = (0, ob + pb)  # the first wall starts at the edge: the way back to the corner is shut
+    k = 1
+    while True:
+        da, db, db2 = oa + pa * k, ob + pb * k, ob + pb * (k + 1)
+        for i, nxt in enumerate([(A - 1 - da, db), (A - 1 - da, B - 1 - db), (da, B - 1 - db), (da, db2)]):
+            step = (nxt[0] - prev[0], nxt[1] - prev[1], prev[0] - nxt[0], prev[1] - nxt[1])[i]
+            if step <= 1 or turns == 0:
+                return img
+            _segment(img, prev, nxt)
+            prev = nxt
+            turns = None if turns is None else turns - 1
+        k += 1
+
+
+def serpentine_walls(A, B, pitch, gap, off=7):
+    """Parallel walls along a, at b = off + pitch, off + 2 pitch, ..., each open over `gap` pixels
+    at one end: the first at the far end of a, the next at a = 0, and so on."""
+    img = np.zeros((B, A), np.uint8)
+    for k, b in enumerate(range(off + pitch, B, pitch)):
+        if k % 2 == 0:
+            img[b, :A - gap] = 255
+        else:
+            img[b, gap:] = 255
+    return img
+
+
+def comb_walls(A, B):
+    """A wall on every odd column a, open over one pixel at alternating ends (b = B - 1, 0, ...):
+    the only way through runs down one even column and up the next, B - 1 steps each."""
+    img = np.zeros((B, A), np.uint8)
+    img[:, 1::2] = 255
+    img[B - 1, 1::4] = 0
+    img[0, 3::4] = 0
+    return img
+
+
+def sealed_box(img, rect):
+    """Draw the closed outline of rect = (a0, b0, a1, b1), corners included, into img."""
+    a0, b0, a1, b1 = rect
+    for p, q in (((a0, b0), (a1, b0)), ((a1, b0), (a1, b1)), ((a1, b1), (a0, b1)), ((a0, b1), (a0, b0))):
+        _segment(img, p, q)
+    return img
+
+
+def pinhole(img, at):
+    """Open the one wall pixel at = (a, b) of img."""
+    a, b = at
+    assert img[b, a], "no wall to open there"
+    img[b, a] = 0
+    return img
+
+
+def walls_as_state(img, axes, X, Y, Z):
+    """The wall image as pre-seen voxels of an X x Y x Z model: state 3 (occupied, seen) on the
+    walls, which run through the grid along the axis the image does not have, 1 elsewhere."""
+    wall = img != 0
+    st = np.ones((Z, Y, X), np.uint8)
+    if axes == "yz":
+        st[wall] = 3                       # wall[z, y], every x
+    elif axes == "xz":
+        st[np.broadcast_to(wall[:, None, :], st.shape)] = 3
+    else:
+        st[np.broadcast_to(wall[None], st.shape)] = 3
+    return st
