@@ -40,6 +40,7 @@ FLOOD_PREPASS = 1
 FLOOD_FRESH = 2
 VOTES_COUNTS = 1
 VOTES_NO_CULL = 2
+COMPONENTS_LARGEST = 1
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
 # whole test module with the streaming carve forced on every fresh model (the library itself reads
 # no environment variable)
@@ -66,6 +67,8 @@ SYMBOLS = [
     "arvx_surface_depth_download", "arvx_color_samples",
     "arvx_color_visible", "arvx_surface_visible_download", "arvx_view_depth_download",
     "arvx_photo_carve", "arvx_carve_votes", "arvx_votes_download",
+    "arvx_components", "arvx_components_download", "arvx_components_labels_download",
+    "arvx_components_keep",
     "arvx_colors_upload", "arvx_closure", "arvx_closure_count", "arvx_closure_download",
     "arvx_closure_download32",
     "arvx_mc_cells", "arvx_mc_cells_download", "arvx_mc_mesh", "arvx_mc_mesh_download",
@@ -212,6 +215,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "arvx_carve_votes"):
         lib.arvx_carve_votes.argtypes = [p, C.c_int, C.c_uint]
         lib.arvx_votes_download.argtypes = [p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "arvx_components"):
+        lib.arvx_components.argtypes = [p, C.c_int, C.POINTER(C.c_int64)]
+        lib.arvx_components_download.argtypes = [p, C.c_void_p, C.c_void_p]
+        lib.arvx_components_labels_download.argtypes = [p, C.c_void_p]
+        lib.arvx_components_keep.argtypes = [p, C.c_int, C.c_int64, C.c_uint, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64)]
     if hasattr(lib, "arvx_render"):
         lib.arvx_render.argtypes = [p, f32p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         lib.arvx_render_view.argtypes = [p, C.c_int]
@@ -641,6 +650,36 @@ class Context:
         inside = np.empty(self.nvox, np.uint16)
         self._ck(self._lib.arvx_votes_download(self._h, bg.ctypes.data, inside.ctypes.data))
         return bg, inside
+
+    def components(self, connectivity: int = 6) -> Tuple[np.ndarray, np.ndarray]:
+        """arvx_components + arvx_components_download: labels the occupied voxels' connected
+        components (connectivity 6 or 26) -> (labels, sizes), int32 each, labels ascending; a label
+        is the least flat index of its component.  The state is unchanged."""
+        n = C.c_int64()
+        self._ck(self._lib.arvx_components(self._h, int(connectivity), C.byref(n)))
+        labels = np.empty(n.value, np.int32)
+        sizes = np.empty(n.value, np.int32)
+        self._ck(self._lib.arvx_components_download(self._h, labels.ctypes.data, sizes.ctypes.data))
+        return labels, sizes
+
+    def component_labels(self) -> np.ndarray:
+        """arvx_components_labels_download: int32 per voxel in flat index order, the label of its
+        component in the last components(), -1 where empty."""
+        out = np.empty(self.nvox, np.int32)
+        self._ck(self._lib.arvx_components_labels_download(self._h, out.ctypes.data))
+        return out
+
+    def keep_components(self, min_voxels: int = 1, largest: bool = False,
+                        connectivity: int = 6) -> Tuple[int, int]:
+        """arvx_components_keep: empties every component of fewer than min_voxels voxels and, with
+        largest, every component but the largest (the least label among equals).
+        -> (components kept, voxels removed)."""
+        kept = C.c_int64()
+        removed = C.c_int64()
+        self._ck(self._lib.arvx_components_keep(self._h, int(connectivity), int(min_voxels),
+                                                COMPONENTS_LARGEST if largest else 0,
+                                                C.byref(kept), C.byref(removed)))
+        return kept.value, removed.value
 
     def surface_visible(self) -> np.ndarray:
         """arvx_surface_visible_download: views each coloured voxel is visible in (surface()'s

@@ -37,6 +37,7 @@
 #include "mc_smooth_kernels.h"
 #include "visibility_kernels.h"
 #include "photo_kernels.h"
+#include "components_kernels.h"
 #include "vote_kernels.h"
 #include "render_kernels.h"
 #include "exchange_kernels.h"
@@ -2294,6 +2295,167 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
     ctx->d_surf_index = nullptr;  // (the list is no colour list: color_ready stays clear)
     if (iterations) *iterations = it;
     if (removed) *removed = (int64_t)removed_all;
+    return ARVX_OK;
+}
+
+// ---- connected components (components_kernels.h) -------------------------------------------------
+
+static int components_refusals(const Ctx *ctx, int connectivity) {
+    if (connectivity != 6 && connectivity != 26)
+        return fail(ARVX_ERR_INVALID, "connectivity %d: must be 6 or 26", connectivity);
+    if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
+        return fail(ARVX_ERR_STATE, "the components need a whole-grid context (a component may cross "
+                                    "any plane)");
+    return ARVX_OK;
+}
+
+// the rule of arvx_components_keep (null: label only)
+struct ComponentsRule {
+    long long min_voxels;
+    int largest;
+};
+
+// Labels the current state: the per-voxel labels, the table (one list, by the list stages' protocol)
+// and, with a rule, the removal: the plane of the components that go, taken off the records.  An
+// attempt whose table outgrew its room counts no size and removes nothing.
+static int components_run(Ctx *ctx, int connectivity, const ComponentsRule *rule, long long *count,
+                          long long *kept, long long *removed) {
+    ctx->comp_ready = false;  // (the buffers of an earlier labelling are written over)
+    const arvx::BitGrid g{ctx->X, ctx->Y, ctx->Z, (ctx->X + 63) / 64};
+    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
+    ARVX_HIP(ctx->pool_comp_planes.reserve(3 * nwords * sizeof(unsigned long long)));
+    ARVX_HIP(ctx->pool_comp_label.reserve(ctx->nvox * sizeof(int)));
+    ARVX_HIP(ctx->pool_comp_rank.reserve(nwords * sizeof(arvx::SparseWord)));
+    ARVX_HIP(ctx->pool_comp_ctl.reserve(64));
+    unsigned long long *occ = (unsigned long long *)ctx->pool_comp_planes.p, *roots = occ + nwords,
+                       *gone = roots + nwords;
+    int *L = (int *)ctx->pool_comp_label.p;
+    arvx::SparseWord *rank = (arvx::SparseWord *)ctx->pool_comp_rank.p;
+    unsigned long long *ctl = (unsigned long long *)ctx->pool_comp_ctl.p;
+    constexpr size_t kEntry = 2 * sizeof(int) + 4;  // label, size, keep byte (padded)
+    ListRoom lists[1] = {{Ctx::kComponents, list_cap(ctx->pool_comp_table, kEntry, 1024), 0}};
+    long long cap = 0;
+    auto launch = [&]() -> int {
+        cap = lists[0].cap;
+        ARVX_HIP(ctx->pool_comp_table.reserve((size_t)cap * kEntry));
+        int *label = (int *)ctx->pool_comp_table.p, *size = label + cap;
+        uint8_t *keep = (uint8_t *)(size + cap);
+        if (int rc = launch_bit_pack(ctx, g, 0, 0, occ, nullptr)) return rc;
+        const unsigned gv = (unsigned)((ctx->nvox + 255) / 256), gw = (unsigned)((nwords + 255) / 256);
+        hipLaunchKernelGGL(arvx::comp_init_kernel, dim3(gv), dim3(256), 0, ctx->stream,
+                           (const unsigned long long *)occ, g, L);
+        ARVX_HIP(hipGetLastError());
+        if (connectivity == 6)
+            hipLaunchKernelGGL(arvx::comp_link_kernel<6>, dim3(gv), dim3(256), 0, ctx->stream,
+                               (const unsigned long long *)occ, g, L);
+        else
+            hipLaunchKernelGGL(arvx::comp_link_kernel<26>, dim3(gv), dim3(256), 0, ctx->stream,
+                               (const unsigned long long *)occ, g, L);
+        ARVX_HIP(hipGetLastError());
+        int *counts = nullptr;
+        if (int rc = chunk_counts(ctx, nwords, &counts)) return rc;
+        hipLaunchKernelGGL(arvx::comp_roots_kernel, dim3(gw), dim3(256), 0, ctx->stream,
+                           (const unsigned long long *)occ, g, L, roots, counts);
+        ARVX_HIP(hipGetLastError());
+        ARVX_HIP(hipMemsetAsync(size, 0, (size_t)cap * sizeof(int), ctx->stream));
+        ARVX_HIP(hipMemsetAsync(ctl, 0, 64, ctx->stream));
+        const long long *d_total = nullptr;
+        if (int rc = bit_compact(ctx, roots, nwords, g, cap, label, rank, Ctx::kComponents, &d_total)) return rc;
+        hipLaunchKernelGGL(arvx::comp_sizes_kernel, dim3(gw), dim3(256), 0, ctx->stream,
+                           (const unsigned long long *)occ, g, (const int *)L, (const arvx::SparseWord *)rank,
+                           d_total, cap, size);
+        ARVX_HIP(hipGetLastError());
+        if (!rule) return ARVX_OK;
+        ctx->word(Ctx::kCompKept) = ctx->word(Ctx::kCompRemoved) = -1;
+        const unsigned gk = (unsigned)((cap + 255) / 256);
+        if (rule->largest) {
+            hipLaunchKernelGGL(arvx::comp_best_kernel, dim3(gk), dim3(256), 0, ctx->stream, (const int *)label,
+                               (const int *)size, d_total, cap, ctl);
+            ARVX_HIP(hipGetLastError());
+        }
+        hipLaunchKernelGGL(arvx::comp_decide_kernel, dim3(gk), dim3(256), 0, ctx->stream, (const int *)label,
+                           (const int *)size, d_total, cap, rule->min_voxels, rule->largest, ctl, keep);
+        ARVX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(arvx::comp_remove_kernel, dim3(gw), dim3(256), 0, ctx->stream,
+                           (const unsigned long long *)occ, g, (const int *)L, (const arvx::SparseWord *)rank,
+                           (const uint8_t *)keep, d_total, cap, gone);
+        ARVX_HIP(hipGetLastError());
+        arvx::CarveParams rp;
+        carve_geometry(ctx, rp);
+        rp.rec = ctx->rec();
+        hipLaunchKernelGGL(arvx::rec_andnot_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, g.Z,
+                           (const unsigned long long *)gone);
+        ARVX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(arvx::comp_publish_kernel, dim3(1), dim3(1), 0, ctx->stream,
+                           (const unsigned long long *)ctl, ctx->word_dev(Ctx::kCompKept),
+                           ctx->word_dev(Ctx::kCompRemoved));
+        ARVX_HIP(hipGetLastError());
+        return ARVX_OK;
+    };
+    // one synchronisation (two when the table outgrows its room: the truncated attempt removes nothing)
+    if (int rc = run_lists(ctx, lists, launch)) return rc;
+    ctx->comp_count = lists[0].total;
+    ctx->comp_cap = cap;
+    ctx->comp_conn = connectivity;
+    if (count) *count = lists[0].total;
+    if (rule) {
+        const long long k = ctx->word(Ctx::kCompKept), r = ctx->word(Ctx::kCompRemoved);
+        if (k < 0 || r < 0) return fail(ARVX_ERR_HIP, "the components' kernels left no count");
+        if (kept) *kept = k;
+        if (removed) *removed = r;
+    }
+    return ARVX_OK;
+}
+
+int arvx_components(arvx_ctx *ctx, int connectivity, int64_t *count) {
+    ARVX_CHECK_CTX(ctx);
+    if (!count) return fail(ARVX_ERR_INVALID, "null count");
+    if (int rc = components_refusals(ctx, connectivity)) return rc;
+    long long n = 0;
+    if (int rc = components_run(ctx, connectivity, nullptr, &n, nullptr, nullptr)) return rc;
+    ctx->comp_ready = true;
+    *count = (int64_t)n;
+    return ARVX_OK;
+}
+
+int arvx_components_download(arvx_ctx *ctx, int32_t *label, int32_t *size) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->comp_ready) return fail(ARVX_ERR_STATE, "no labelling: arvx_components has not run on this state");
+    const size_t bytes = (size_t)ctx->comp_count * sizeof(int32_t);
+    const int *d_label = (const int *)ctx->pool_comp_table.p;
+    if (label && bytes) ARVX_HIP(hipMemcpyAsync(label, d_label, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (size && bytes)
+        ARVX_HIP(hipMemcpyAsync(size, d_label + ctx->comp_cap, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+int arvx_components_labels_download(arvx_ctx *ctx, int32_t *voxel_label) {
+    ARVX_CHECK_CTX(ctx);
+    if (!voxel_label) return fail(ARVX_ERR_INVALID, "null voxel_label");
+    if (!ctx->comp_ready) return fail(ARVX_ERR_STATE, "no labelling: arvx_components has not run on this state");
+    ARVX_HIP(hipMemcpyAsync(voxel_label, ctx->pool_comp_label.p, ctx->nvox * sizeof(int32_t),
+                            hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+int arvx_components_keep(arvx_ctx *ctx, int connectivity, int64_t min_voxels, unsigned flags, int64_t *kept,
+                         int64_t *removed) {
+    ARVX_CHECK_CTX(ctx);
+    if (min_voxels < 1) return fail(ARVX_ERR_INVALID, "min_voxels %lld: must be >= 1", (long long)min_voxels);
+    if (flags & ~ARVX_COMPONENTS_LARGEST) return fail(ARVX_ERR_INVALID, "unknown flag bits 0x%x", flags);
+    if (int rc = components_refusals(ctx, connectivity)) return rc;
+    if (int frc = fills_without_colours(ctx)) return frc;
+    // every record exists before a bit is cleared (rec_andnot_bitgrid_kernel writes records only): a
+    // lazy state ends here, as in arvx_photo_carve
+    if (int mrc = need_rec(ctx)) return mrc;
+    ctx->drop(Event::ComponentsKeep);
+    const ComponentsRule rule{(long long)min_voxels, (flags & ARVX_COMPONENTS_LARGEST) ? 1 : 0};
+    long long k = 0, r = 0;
+    if (int rc = components_run(ctx, connectivity, &rule, nullptr, &k, &r)) return rc;
+    if (kept) *kept = (int64_t)k;
+    if (removed) *removed = (int64_t)r;
     return ARVX_OK;
 }
 

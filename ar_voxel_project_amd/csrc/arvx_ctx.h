@@ -74,14 +74,16 @@ struct Ctx {
     enum Word {
         kSurface, kClosure, kCells, kTris, kVerts,  // list lengths, in the device copies' order
         kSmoothScan,                    // arvx_mc_mesh_smooth's offset scans: a total nobody reads
+        kComponents,                    // the component table's length (arvx_components[_keep])
         kDeviceTotals,
         kPhotoRemoved = kDeviceTotals,  // voxels an iteration of arvx_photo_carve removed
         kVisNeed,                       // large footprints the visible pass wanted to list
         kPacketOcc, kPacketSeen,        // arvx_state_download_packets: the two packets' words
+        kCompKept, kCompRemoved,        // arvx_components_keep: components left, voxels emptied
         kRenderNeed, kRenderAgree,      // the render's large footprints; three agreement counts in a row
         kWords = kRenderAgree + 3
     };
-    static constexpr size_t kHostBlockBytes = 128;
+    static constexpr size_t kHostBlockBytes = 192;
     static_assert(8 + 8 * (size_t)kWords <= kHostBlockBytes, "the count words fit the block");
     long long &word(int w) const { return ((long long *)(h_fault + 2))[w]; }      // host value
     long long *word_dev(int w) const { return (long long *)(d_fault + 2) + w; }  // device address
@@ -225,6 +227,17 @@ struct Ctx {
     DevPool pool_votes{DevPool::Exact};
     bool votes_ready = false;
 
+    // arvx_components: the per-voxel labels (int32, flat index order; -1 where empty); the occupancy
+    // plane, the roots' plane and arvx_components_keep's removal plane (bitplane_kernels.h layout);
+    // the roots' plane's index (SparseWord); the table -- comp_cap labels, then comp_cap sizes, then
+    // comp_cap keep bytes --; and the control block (components_kernels.h, ctl).  The labels and the
+    // table are read only while comp_ready is set.
+    DevPool pool_comp_label{DevPool::Exact}, pool_comp_planes{DevPool::Exact}, pool_comp_rank{DevPool::Exact},
+        pool_comp_table, pool_comp_ctl;
+    bool comp_ready = false;
+    int comp_conn = 0;
+    long long comp_count = 0, comp_cap = 0;
+
     // closure (dilation) result: filled voxels, ascending index
     int *d_clo_index = nullptr;
     void *d_clo_rgba = nullptr;  // float4 per filled voxel
@@ -249,27 +262,28 @@ struct Ctx {
     // whatever replaces that state drops it (and so does the next arvx_mc_mesh_welded).
     enum class Event {
         SetViews, SetImages, Color, UploadColors, ProjectionAssoc, HandleUnseen, Closure,
-        Carve, FastCarve, UploadState, UploadPlanes, UploadHalo, Reset, PhotoCarve
+        Carve, FastCarve, UploadState, UploadPlanes, UploadHalo, Reset, PhotoCarve, ComponentsKeep
     };
     void drop(Event e) {
-        struct Row { uint8_t colours, closure, fills, paint, cstate, state, render, votes; };
+        struct Row { uint8_t colours, closure, fills, paint, cstate, state, render, votes, comps; };
         static constexpr Row kRows[] = {
-            //                    colour closure closure paint cstate state   render votes
-            //                    list   list    fills         tiles  changes
-            /* SetViews        */ {1,    1,      0,      0,    0,     0,      0,      1},
-            /* SetImages       */ {1,    1,      0,      0,    0,     0,      0,      0},
-            /* Color           */ {1,    1,      0,      0,    0,     0,      0,      0},
-            /* UploadColors    */ {1,    1,      0,      0,    0,     0,      0,      0},
-            /* ProjectionAssoc */ {1,    0,      0,      0,    0,     0,      0,      1},  // (a change of grouping)
-            /* HandleUnseen    */ {0,    1,      0,      0,    0,     2,      0,      1},
-            /* Closure         */ {0,    1,      0,      0,    1,     1,      0,      1},
-            /* Carve           */ {1,    1,      1,      1,    0,     1,      1,      1},
-            /* FastCarve       */ {1,    1,      1,      1,    0,     1,      1,      1},
-            /* UploadState     */ {1,    1,      1,      2,    1,     1,      1,      1},
-            /* UploadPlanes    */ {1,    1,      1,      1,    1,     1,      1,      1},
-            /* UploadHalo      */ {1,    1,      1,      0,    1,     1,      1,      1},
-            /* Reset           */ {1,    1,      1,      1,    1,     1,      1,      1},
-            /* PhotoCarve      */ {1,    1,      1,      1,    0,     1,      1,      1},
+            //                    colour closure closure paint cstate state   render votes  component
+            //                    list   list    fills         tiles  changes                labels
+            /* SetViews        */ {1,    1,      0,      0,    0,     0,      0,      1,     0},
+            /* SetImages       */ {1,    1,      0,      0,    0,     0,      0,      0,     0},
+            /* Color           */ {1,    1,      0,      0,    0,     0,      0,      0,     0},
+            /* UploadColors    */ {1,    1,      0,      0,    0,     0,      0,      0,     0},
+            /* ProjectionAssoc */ {1,    0,      0,      0,    0,     0,      0,      1,     0},  // (a change of grouping)
+            /* HandleUnseen    */ {0,    1,      0,      0,    0,     2,      0,      1,     1},
+            /* Closure         */ {0,    1,      0,      0,    1,     1,      0,      1,     1},
+            /* Carve           */ {1,    1,      1,      1,    0,     1,      1,      1,     1},
+            /* FastCarve       */ {1,    1,      1,      1,    0,     1,      1,      1,     1},
+            /* UploadState     */ {1,    1,      1,      2,    1,     1,      1,      1,     1},
+            /* UploadPlanes    */ {1,    1,      1,      1,    1,     1,      1,      1,     1},
+            /* UploadHalo      */ {1,    1,      1,      0,    1,     1,      1,      1,     1},
+            /* Reset           */ {1,    1,      1,      1,    1,     1,      1,      1,     1},
+            /* PhotoCarve      */ {1,    1,      1,      1,    0,     1,      1,      1,     1},
+            /* ComponentsKeep  */ {1,    1,      1,      1,    0,     1,      1,      1,     1},
         };
         // paint 2: the owned planes' paint is replaced; the plane stays where halo planes keep
         // theirs.  state 2: only never-seen voxels become occupied (next_state).  cstate: a call
@@ -279,7 +293,10 @@ struct Ctx {
         // carved and seen as a whole stays empty, one seen as a whole stays seen -- both stay settled.
         // votes: the counts of arvx_carve_votes describe the state that call left under the views and
         // the grouping it ran with; whatever replaces one of them drops the counts.
-        static_assert(sizeof kRows / sizeof kRows[0] == (size_t)Event::PhotoCarve + 1, "a row per event");
+        // component labels: the labelling of arvx_components describes the occupancy it read; every
+        // call that changes the state drops it.  arvx_components_keep drops what photo carving drops,
+        // for the same reasons: it only empties voxels and keeps every seen bit.
+        static_assert(sizeof kRows / sizeof kRows[0] == (size_t)Event::ComponentsKeep + 1, "a row per event");
         const Row &r = kRows[(int)e];
         if (r.colours) color_ready = color_visible = false;
         if (r.closure) closure_ready = false;
@@ -293,6 +310,7 @@ struct Ctx {
         }
         if (r.render) render_ready = false;
         if (r.votes) votes_ready = false;
+        if (r.comps) comp_ready = false;
     }
     // The state changes: whatever carries the old count as its stamp is stale -- but for
     // handleUnseen (unseen_only) the colour pass's planes of the state before stay usable: its

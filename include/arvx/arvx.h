@@ -430,7 +430,8 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
  * voxel is emptied and only seen bits are set.  The flags change the work, never the state:
  *   ARVX_VOTES_COUNTS   bg and in are kept on the device, u16 per voxel in flat index order, until
  *                       the next call that replaces the state (carve, fast carve, photo carve,
- *                       handleUnseen, closure, upload, reset), the views or the grouping.  Both are
+ *                       arvx_components_keep, handleUnseen, closure, upload, reset), the views or the
+ *                       grouping.  Both are
  *                       the full sums over all V views whatever max_misses is: no early exit is
  *                       taken.  arvx_votes_download copies them out (either pointer may be null; it
  *                       synchronises); without such counts it returns ARVX_ERR_STATE.
@@ -447,6 +448,55 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
 #define ARVX_VOTES_NO_CULL 2u /* project every voxel in every view (ablation, yardstick) */
 int arvx_carve_votes(arvx_ctx *ctx, int max_misses, unsigned flags);
 int arvx_votes_download(arvx_ctx *ctx, uint16_t *background, uint16_t *inside);
+/* ---- connected components (extension beyond the reference) ------------------------------------
+ * Every carve decides a voxel on its own; none asks whether it is attached to anything.  Where the
+ * false foreground specks of a few silhouettes intersect, a clump of voxels survives in mid-air
+ * (the vote carve, which tolerates misses, keeps more of them), and the reference has no answer:
+ * its fastCarve follows connectivity only through empty space.  arvx_components labels the model,
+ * arvx_components_keep drops the floaters.  Definition, on a whole-grid context, its current state:
+ *  - a voxel is OCCUPIED iff bit0 of the byte arvx_state_download would return for it is set (a
+ *    closure's fills included); the paint bit and the seen bit play no part;
+ *  - two occupied voxels are ADJACENT under connectivity 6 iff they differ by 1 in exactly one
+ *    coordinate, under connectivity 26 iff they differ by at most 1 in every coordinate and are not
+ *    the same voxel; out-of-grid counts as empty;
+ *  - a COMPONENT is a class of the transitive closure of that adjacency; its LABEL is the least flat
+ *    index x + X*(y + Y*z) among its voxels, its SIZE the number of its voxels.
+ * Everything is an integer: the result depends on no thread order and is compared bit for bit.
+ *   arvx_components            labels; *count = number of components C.  The state is unchanged
+ *                              and nothing is dropped.
+ *   arvx_components_download   the table: the C labels ascending, and their sizes (either pointer
+ *                              may be null).
+ *   arvx_components_labels_download  per voxel, flat index order: the label of its component, -1
+ *                              where empty.
+ *   arvx_components_keep       keeps component c iff size(c) >= min_voxels and (ARVX_COMPONENTS_LARGEST
+ *                              not set, or c has the greatest size -- the least label among equals);
+ *                              every voxel of the other components becomes empty: occupied bit
+ *                              cleared, seen bit kept.  *kept = components left, *removed = voxels
+ *                              emptied (either may be null).
+ * The labelling of arvx_components lives until any call that replaces the state (carve, vote carve,
+ * fast carve, photo carve, arvx_handle_unseen, closure, state uploads, reset, arvx_components_keep);
+ * before a labelling and after such a call the two downloads answer ARVX_ERR_STATE.
+ * arvx_components_keep labels on its own account and leaves no labelling behind.  It replaces the
+ * state as arvx_photo_carve does: it drops what photo carving drops even when it removes nothing
+ * (see "What the context's results belong to", arvx_closure), ends a lazy state first, leaves what
+ * earlier carves settled for whole coarse tiles valid, since it only empties voxels, and refuses a
+ * state holding a closure's fills whose list is gone (ARVX_ERR_STATE).
+ * Refusals: a slab or a striped context: ARVX_ERR_STATE; a connectivity other than 6 or 26,
+ * min_voxels < 1, unknown flag bits, a null count (a null voxel_label): ARVX_ERR_INVALID.  A refused
+ * call changes nothing.  An empty model is no error: 0 components, nothing removed.
+ * One host synchronisation per call (the counts); a second one when the table outgrows its room
+ * (first 1024 components, then what the last call held): that attempt counts no size and removes
+ * nothing, and the call's launches run once more.  The downloads synchronise.
+ * Device memory, allocated at first use and kept: 4 bytes per voxel (the labels), three bit planes
+ * (occupancy, roots, removal: 3/8 byte per voxel), 16 bytes per 64 voxels (the roots' plane's index)
+ * and 12 bytes per component of the table's room.
+ * Out of scope: slabs and multi-GPU, connectivity 18, selecting components by an arbitrary list. */
+#define ARVX_COMPONENTS_LARGEST 1u /* keep only the component of the greatest size */
+int arvx_components(arvx_ctx *ctx, int connectivity, int64_t *count);
+int arvx_components_download(arvx_ctx *ctx, int32_t *label, int32_t *size);
+int arvx_components_labels_download(arvx_ctx *ctx, int32_t *voxel_label);
+int arvx_components_keep(arvx_ctx *ctx, int connectivity, int64_t min_voxels, unsigned flags,
+                         int64_t *kept, int64_t *removed);
 /* The per-voxel colour lists behind the vote -- what the reference's voxel_pass appends with
  * Model::addColor (src/ColorReconstruction.h:44-60, src/Model.h:142-149) and getColors returns:
  * for each of n voxels (flat index over the context's own planes, any order) V samples in view
@@ -495,7 +545,11 @@ int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const flo
  *     or reset;
  *   - arvx_photo_carve drops what a carve drops (the colour list, the closure's list, the mark of a
  *     closure's fills and the paint plane), even when it removes nothing; what earlier carves
- *     settled for whole coarse tiles stays valid, since it only empties voxels.
+ *     settled for whole coarse tiles stays valid, since it only empties voxels;
+ *   - arvx_components_keep drops exactly what arvx_photo_carve drops, for the same reason;
+ *   - the labelling of arvx_components lives until the next call that replaces the state: carve,
+ *     vote carve, fast carve, photo carve, arvx_handle_unseen, closure, state upload, reset or
+ *     arvx_components_keep.
  * A closure that filled voxels leaves them occupied in the state.  Once its list is gone the
  * context no longer has their colours, which the reference's Model keeps: until a carve, fast
  * carve, upload or reset replaces the state, the calls that return colours (arvx_export_model,

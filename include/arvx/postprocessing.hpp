@@ -7,6 +7,10 @@
 // neighbours.  Limitation: explicit colours must have w == 1 (every colour the
 // reference's own pipeline produces has).  Runs on the model's own device context: state and
 // the colour list of the colour pass are already there (src/main.cpp:282-299).
+//
+// dropFloaters(Model&, ...) -- an extension beyond the reference: the connected components of the
+// carved model (arvx_components_keep), for the clumps of voxels that the false foreground specks of
+// a few silhouettes leave in mid-air.
 #ifndef ARVX_POSTPROCESSING_HPP
 #define ARVX_POSTPROCESSING_HPP
 
@@ -62,6 +66,28 @@ inline int applyClosure(Model *model, int kernelSize) {
     detail::timing(kStagePostProcessing, false);
     std::cout << "LOG - PP: postprocessing completed." << std::endl;
     return 0;
+}
+
+// Extension beyond the reference: drops the floaters of a carved model, between the carve and the
+// colour pass (arvx_components_keep).  A connected component of occupied voxels (connectivity 6 or
+// 26) stays iff it has at least min_voxels voxels and -- with largest_only -- is the largest one (the
+// one with the least flat index among equals); the voxels of the others become empty and keep their
+// seen bits.  Runs on the model's own device context, as photoCarve does: the model's current state
+// goes there first if the host holds it, and the result stays on the device until somebody reads
+// the model on the host.  Returns the voxels removed.
+inline int64_t dropFloaters(Model &model, int64_t min_voxels = 1, bool largest_only = true, int connectivity = 6) {
+    std::cout << "LOG - PP: dropping floaters." << std::endl;
+    detail::timing(kStagePostProcessing, true);
+    arvx_ctx *ctx = model.device();
+    int64_t kept = 0, removed = 0;
+    detail::check(arvx_components_keep(ctx, connectivity, min_voxels, largest_only ? ARVX_COMPONENTS_LARGEST : 0u,
+                                       &kept, &removed),
+                  "arvx_components_keep");
+    model.device_changed();
+    detail::timing(kStagePostProcessing, false);
+    std::cout << "LOG - PP: floaters dropped (" << kept << " components kept, " << removed << " voxels removed)."
+              << std::endl;
+    return removed;
 }
 
 }  // namespace arvx

@@ -228,7 +228,7 @@ int main(int argc, char *argv[]) {
         {"dy", "0.0"}, {"dz", "0.0"}, {"model_debug", "false"}, {"postprocessing", "true"},
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
-        {"photoIters", "32"}, {"render", ""}, {"misses", "0"}};
+        {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -246,6 +246,9 @@ int main(int argc, char *argv[]) {
                      "    differ by a summed channel standard deviation above T; 0, the default: off),\n"
                      "  -photoViews=N (views a voxel must be visible in to be judged, default 2),\n"
                      "  -photoIters=N (sweeps at most, default 32; depth tolerance: -visibleTol),\n"
+                     "  -floaters=N (after carving: empty every connected component of fewer than N\n"
+                     "    voxels, 6-connectivity; 0, the default: off),\n"
+                     "  -largest=true (after carving: keep only the largest connected component),\n"
                      "  -render=DIR (after the mesh: the welded model drawn over every input image,\n"
                      "    DIR/renderNNNN.ppm, and its agreement with every mask)\n";
         return 0;
@@ -268,6 +271,10 @@ int main(int argc, char *argv[]) {
         }
         if (parser.i("misses") < 0 || 65535 < parser.i("misses")) {
             std::cerr << "Invalid misses argument.";
+            return 1;
+        }
+        if (parser.i("floaters") < 0) {
+            std::cerr << "Invalid floaters argument.";
             return 1;
         }
     }
@@ -401,6 +408,10 @@ int main(int argc, char *argv[]) {
         if (parser.f("photo") > 0.f)
             arvx::photoCarve(in.intr, model, in.views, parser.f("photo"), parser.i("photoViews"),
                              parser.f("visibleTol"), parser.i("photoIters"));
+        // -floaters=N, -largest=true (an extension beyond the reference): the model's connected
+        // components -- the clumps that false foreground specks leave in mid-air go before they are coloured
+        if (parser.i("floaters") > 0 || parser.b("largest"))
+            arvx::dropFloaters(model, std::max(1, parser.i("floaters")), parser.b("largest"));
         const int color = parser.i("color");
         if (color < 0 || 3 < color) {
             std::cerr << "You need to select a predefined color reconstruction mode. (--color)";
