@@ -35,6 +35,7 @@ PATH_LAZY_CODES = 8
 PATH_FUSED = 16
 PATH_BRUTE_FORCE = 32
 PATH_STREAM = 64
+PATH_RECT_BLOCKS = 128
 # bits of Context.last_fast_carve_path()["bits"] (ARVX_FLOOD_*)
 FLOOD_PREPASS = 1
 FLOOD_FRESH = 2
@@ -80,6 +81,7 @@ SYMBOLS = [
     "arvx_export_model", "arvx_get_stats", "arvx_last_carve_path", "arvx_last_fast_carve_path",
     "arvx_selftest_divide",
     "arvx_selftest_round",
+    "arvx_ctx_set_rect_cache_limit", "arvx_selftest_rect_cache",
 ]
 
 
@@ -186,6 +188,9 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.arvx_selftest_divide.argtypes = [p, C.c_int64, f32p, f32p, f32p, f32p]
     if hasattr(lib, "arvx_selftest_round") or not ab_build:
         lib.arvx_selftest_round.argtypes = [p, C.POINTER(C.c_int64)]
+    if hasattr(lib, "arvx_selftest_rect_cache") or not ab_build:
+        lib.arvx_ctx_set_rect_cache_limit.argtypes = [p, C.c_uint64]
+        lib.arvx_selftest_rect_cache.argtypes = [p, C.POINTER(C.c_int64)]
     if hasattr(lib, "arvx_mc_cells") or not ab_build:
         lib.arvx_mc_cells.argtypes = [p, C.POINTER(C.c_int64)]
         lib.arvx_mc_cells_download.argtypes = [p, C.POINTER(C.c_int32)]
@@ -895,6 +900,18 @@ class Context:
         """Mismatches between the kernels' pixel rounding and std::round (must be 0)."""
         n = C.c_int64(-1)
         self._ck(self._lib.arvx_selftest_round(self._h, C.byref(n)))
+        return int(n.value)
+
+    def set_rect_cache_limit(self, nbytes: int) -> None:
+        """Bytes the context's table of cached rectangles may take (0: none).  Releases the table;
+        it is built again, under the new limit, by the carves that follow."""
+        self._ck(self._lib.arvx_ctx_set_rect_cache_limit(self._h, nbytes))
+
+    def selftest_rect_cache(self) -> int:
+        """Entries of the table of cached rectangles that differ from a recomputation: must be 0
+        (-1: the context holds no table)."""
+        n = C.c_int64(-2)
+        self._ck(self._lib.arvx_selftest_rect_cache(self._h, C.byref(n)))
         return int(n.value)
 
     def stats(self) -> dict:

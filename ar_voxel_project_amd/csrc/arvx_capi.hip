@@ -21,6 +21,7 @@
 
 #include "arvx_ctx.h"
 #include "carve_kernels.h"
+#include "rect_cache_kernels.h"
 #ifdef ARVX_EXPERIMENTS
 #include "carve_stream_kernels.h"  // the one-launch carve: loses by 11-24 %, experiment builds only
 #endif
@@ -663,6 +664,7 @@ static int views_common(Ctx *ctx, int V, const float *M, const float *campos, in
     const bool same_M = same && ctx->h_M.size() == (size_t)V * 12 &&
                         memcmp(ctx->h_M.data(), M, (size_t)V * 12 * sizeof(float)) == 0;
     if (!same_M) {
+        ctx->rect_invalidate();  // (the cached rectangles are those of the matrices before)
         ctx->h_M.assign(M, M + (size_t)V * 12);
         ARVX_HIP(hipMemcpyAsync(ctx->M(), ctx->h_M.data(), (size_t)V * 12 * sizeof(float),
                                 hipMemcpyHostToDevice, ctx->stream));
@@ -1502,6 +1504,60 @@ static int launch_carve_stream(Ctx *ctx, arvx::CarveParams p, int ncu) {
 }
 #endif
 
+// ---- cached rectangles (rect_cache_kernels.h) ---------------------------------------------------
+
+// field widths of a table entry for the context's image size
+static arvx::RectBits rect_bits(const Ctx *ctx) {
+    arvx::RectBits rb = {1, 1, 0};
+    while ((1 << rb.xb) < ctx->W) ++rb.xb;
+    while ((1 << rb.yb) < ctx->H) ++rb.yb;
+    rb.db = (32 - rb.xb - rb.yb) / 2;
+    return rb;
+}
+static size_t rect_entries(const Ctx *ctx, const arvx::CarveParams &p) {
+    return (arvx::rec_count(p) << 4) * (size_t)ctx->V;
+}
+static void rect_params(const Ctx *ctx, arvx::CarveParams &p) {
+    const arvx::RectBits rb = rect_bits(ctx);
+    p.rcXB = rb.xb;
+    p.rcYB = rb.yb;
+    p.rcDB = rb.db;
+}
+
+// A carve of a fresh model that runs the dense classify kernel and the unshared block-mapped exact
+// kernel on the context's own records: counts it, builds the table at the second one in a row
+// under the same views, and hands p the table once it stands.  The build ends with a synchronisation -- once per set of
+// cameras --, after which the host knows whether every block rectangle fitted its entry.
+static int rect_cache_prepare(Ctx *ctx, arvx::CarveParams &p) {
+    if (!ctx->rect_limit) return ARVX_OK;
+    if (ctx->rect_streak < 2) ++ctx->rect_streak;
+    if (ctx->rect_streak < 2) return ARVX_OK;
+    rect_params(ctx, p);
+    if (ctx->rect_state == Ctx::Rect::None) {
+        ctx->rect_state = Ctx::Rect::Refused;
+        const size_t n = rect_entries(ctx, p), bytes = n * sizeof(uint32_t);
+        if (p.rcDB < 1 || bytes > ctx->rect_limit) return ARVX_OK;
+        if (ctx->pool_rect.reserve(bytes) != hipSuccess) {  // (no room on the device: no table, no error)
+            (void)hipGetLastError();
+            return ARVX_OK;
+        }
+        ctx->word(Ctx::kRectMiss) = 0;
+        hipLaunchKernelGGL(arvx::rect_cache_block_kernel<false>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)),
+                           dim3(256), 0, ctx->stream, p, (uint32_t *)ctx->pool_rect.p, n,
+                           ctx->word_dev(Ctx::kRectMiss), (unsigned long long *)nullptr);
+        ARVX_HIP(hipGetLastError());
+        ARVX_SYNC(ctx);
+        if (ctx->word(Ctx::kRectMiss)) {  // a rectangle too large for an entry: computed as before
+            ctx->word(Ctx::kRectMiss) = 0;
+            ctx->pool_rect.release();
+            return ARVX_OK;
+        }
+        ctx->rect_state = Ctx::Rect::Built;
+    }
+    if (ctx->rect_state == Ctx::Rect::Built) p.rcBlk = (const uint32_t *)ctx->pool_rect.p;
+    return ARVX_OK;
+}
+
 // `fresh`: the model is all-occupied/unseen and exists only as that flag: nothing is read,
 // every record of the grid is written.
 // `foreign_code` (records that are not the context's own, fresh): the decided coarse tiles are not
@@ -1687,6 +1743,13 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
 #else
         const bool dense = false;
 #endif
+        // the exact kernel's block rectangles from the context's table, once it stands: for the
+        // carves that run the instantiation that reads it (a fresh model, items not shared)
+        if (dense && blocks && fresh && !(p.flags & 8u) && rec == ctx->rec()) {
+            if (int rc = rect_cache_prepare(ctx, p)) return rc;
+        } else {
+            ctx->rect_streak = 0;
+        }
         if (dense)  // one workgroup per listed coarse tile and turn
             hipLaunchKernelGGL(arvx::carve_classify_dense_kernel, dim3((unsigned)ncu * (unsigned)ARVX_DENSE_WGS_PER_CU), dim3(256),
                                0, ctx->stream, p);
@@ -1699,7 +1762,10 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
 #endif
         const bool left = ctx->assoc == ARVX_ASSOC_LEFT;
         const bool may_split = p.flags & 8u;
+        // the block tests from the table: the large grids' fresh instantiations only
+        bool cached = blocks && fresh && !may_split && p.rcBlk;
 #ifdef ARVX_EXPERIMENTS
+        if (flags & ARVX_CARVE_FILTER) cached = false;
         // the fp32 filter in front of the exact projection (carve_kernels.h, filtered_view_blocks):
         // for callers whose masks leave most blocks of an item to be projected (ARVX_CARVE_FILTER)
         const bool filter = (flags & ARVX_CARVE_FILTER) != 0;
@@ -1723,7 +1789,13 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
                                ctx->stream, p);
         else
 #endif
-        if (blocks && left && may_split)
+        if (cached && left)
+            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, false, true, false, true>), dim3(pgrid), dim3(256), 0,
+                               ctx->stream, p);
+        else if (cached)
+            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<false, false, true, false, true>), dim3(pgrid), dim3(256), 0,
+                               ctx->stream, p);
+        else if (blocks && left && may_split)
             hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, true>), dim3(pgrid), dim3(256), 0,
                                ctx->stream, p);
         else if (blocks && left && fresh)
@@ -1752,7 +1824,8 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         ++ctx->carve_seq;
         // (arvx_last_carve_path: all of it once every launch is out, or nothing)
         ctx->path_bits = (dense ? ARVX_PATH_DENSE_CLASSIFY : 0u) | (may_split ? ARVX_PATH_ITEM_SHARING : 0u) |
-                         (fresh ? ARVX_PATH_FRESH : 0u) | (lazy ? ARVX_PATH_LAZY_CODES : 0u);
+                         (fresh ? ARVX_PATH_FRESH : 0u) | (lazy ? ARVX_PATH_LAZY_CODES : 0u) |
+                         (cached ? ARVX_PATH_RECT_BLOCKS : 0u);
         ctx->path_dense_grid = dense ? (unsigned)ncu * (unsigned)ARVX_DENSE_WGS_PER_CU : 0u;
         ctx->path_off_listed = (size_t)((uint8_t *)p.undecidedCount - (uint8_t *)ctx->pool_coarse.p);
         ctx->path_off_work = (size_t)((uint8_t *)p.workCount - (uint8_t *)ctx->pool_coarse.p);
@@ -1769,6 +1842,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         hipLaunchKernelGGL(arvx::carve_fused_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, p);
     ARVX_HIP(hipGetLastError());
     ctx->path_bits = (cull ? ARVX_PATH_FUSED : ARVX_PATH_BRUTE_FORCE) | (fresh ? ARVX_PATH_FRESH : 0u);
+    ctx->rect_streak = 0;
     return ARVX_OK;
 }
 
@@ -2766,6 +2840,40 @@ int arvx_selftest_round(arvx_ctx *ctx, int64_t *mismatches) {
                            0, ctx->stream, r[0], r[1], d_bad);
         ARVX_HIP(hipGetLastError());
     }
+    unsigned long long bad = 0;
+    ARVX_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    *mismatches = (int64_t)bad;
+    return ARVX_OK;
+}
+
+int arvx_ctx_set_rect_cache_limit(arvx_ctx *ctx, uint64_t bytes) {
+    ARVX_CHECK_CTX(ctx);
+    if (bytes > (uint64_t)1 << 46) return fail(ARVX_ERR_INVALID, "limit of %llu bytes", (unsigned long long)bytes);
+    if (ctx->pool_rect.p) ARVX_SYNC(ctx);  // (a kernel of the stream may still be reading the table)
+    ctx->pool_rect.release();
+    ctx->rect_state = Ctx::Rect::None;  // (decided again under the new limit)
+    ctx->rect_limit = (size_t)bytes;
+    return ARVX_OK;
+}
+
+int arvx_selftest_rect_cache(arvx_ctx *ctx, int64_t *mismatches) {
+    ARVX_CHECK_CTX(ctx);
+    if (!mismatches) return fail(ARVX_ERR_INVALID, "null mismatches");
+    *mismatches = -1;
+    if (ctx->rect_state != Ctx::Rect::Built) return ARVX_OK;
+    arvx::CarveParams p;
+    carve_geometry(ctx, p);
+    carve_views(ctx, p);
+    rect_params(ctx, p);
+    ARVX_HIP(ctx->pool_scratch.reserve(64));
+    unsigned long long *d_bad = (unsigned long long *)ctx->pool_scratch.p;
+    ARVX_HIP(hipMemsetAsync(d_bad, 0, sizeof *d_bad, ctx->stream));
+    const size_t n = rect_entries(ctx, p);
+    hipLaunchKernelGGL(arvx::rect_cache_block_kernel<true>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)),
+                       dim3(256), 0, ctx->stream, p, (uint32_t *)ctx->pool_rect.p, n, (long long *)nullptr,
+                       d_bad);
+    ARVX_HIP(hipGetLastError());
     unsigned long long bad = 0;
     ARVX_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);

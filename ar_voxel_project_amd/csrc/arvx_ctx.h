@@ -81,7 +81,8 @@ struct Ctx {
         kPacketOcc, kPacketSeen,        // arvx_state_download_packets: the two packets' words
         kCompKept, kCompRemoved,        // arvx_components_keep: components left, voxels emptied
         kRenderNeed, kRenderAgree,      // the render's large footprints; three agreement counts in a row
-        kWords = kRenderAgree + 3
+        kRectMiss = kRenderAgree + 3,   // a block's rectangle did not fit its table entry (rect_cache_kernels.h)
+        kWords
     };
     static constexpr size_t kHostBlockBytes = 192;
     static_assert(8 + 8 * (size_t)kWords <= kHostBlockBytes, "the count words fit the block");
@@ -193,6 +194,24 @@ struct Ctx {
     uint32_t *bg() const { return (uint32_t *)pool_bg.p; }
     uint16_t *sat() const { return (uint16_t *)pool_sat.p; }
     std::vector<float> h_M, h_campos;
+    // Cached rectangles (carve_kernels.h, rect_cache_kernels.h): what the carve's rectangle
+    // arithmetic answers for every (4 x 4 x 4 block, view) of this context's grid, kept while the
+    // matrices, V, W and H stand -- the masks do not enter.  Built at the second consecutive carve
+    // of a fresh model that runs the dense classify kernel and the unshared block-mapped exact
+    // kernel -- the instantiation that reads the table -- under the same views (rect_streak counts
+    // them), and only while the table fits rect_limit bytes.  Refused: not
+    // tried again for these views (it does not fit the limit or the device, or a block's rectangle
+    // does not fit an entry).  New matrices take it back to None (views_common); free_views
+    // releases the table; the events of drop() do not touch it.
+    enum class Rect { None, Built, Refused };
+    Rect rect_state = Rect::None;
+    int rect_streak = 0;
+    size_t rect_limit = (size_t)1 << 30;  // arvx_ctx_set_rect_cache_limit (0: no table)
+    DevPool pool_rect{DevPool::Exact};
+    void rect_invalidate() {
+        rect_state = Rect::None;
+        rect_streak = 0;
+    }
 
     // colour pass
     DevPool pool_images{DevPool::Exact};  // V x H x W x 3, BGR
@@ -377,6 +396,8 @@ struct Ctx {
         pool_campos.release();
         pool_bg.release();
         pool_sat.release();
+        pool_rect.release();
+        rect_invalidate();
         views_ready = false;
         cameras_ready = false;
     }

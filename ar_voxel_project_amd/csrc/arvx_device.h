@@ -107,6 +107,10 @@ struct CarveParams {
     int nA, cwA;                // coarse units: nA of cwA coarse tiles each
     int splitLog2;              // log2 sub-tile units per listed coarse tile (0: whole, 2: quarters)
     unsigned *fault;            // Ctx::d_fault
+    // cached block rectangles (carve_kernels.h, rect_cache_kernels.h), null where the carve computes
+    // them: [view of the context][record (rec_index)][16 blocks]
+    const uint32_t *rcBlk;
+    int rcXB, rcYB, rcDB;       // field widths of an entry (RectBits)
 };
 
 // global z of local plane lz

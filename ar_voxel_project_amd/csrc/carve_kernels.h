@@ -178,6 +178,46 @@ __device__ inline int classify_box(const float *__restrict__ M, const BoxW b, in
     return classify_box_m(Mr, b, W, H, sat, satW);
 }
 
+// ---- cached rectangles (rect_cache_kernels.h builds the table) ----------------------------------
+// What rect_prepare answers depends on the view's matrix, the image size, the voxel size and the
+// box -- not on the masks.  While a context's cameras stand, the answers for the boxes of
+// block_tests (4 x 4 x 4 blocks) are kept in a table, and the exact kernel loads an entry where it
+// would load the matrix and run rect_prepare; the four table reads and rect_finish follow as
+// before.  An entry holds pxlo and pylo, not `base`.  (The sub-tile rectangles of the dense classify
+// kernel were tabulated the same way and measured no gain: EXPERIMENTS.md, round 6.)
+//
+// Block entry, 32 bits, the fields' widths chosen per image size (RectBits): pxlo | pylo | dx | dy
+// from bit 0 up; dx >= 1 in every rectangle, so dx = dy = 0 marks the two answers that need no
+// look: 0 outside (kClsOut), 1 mixed.  (The kFastDiv bit is not kept: block_tests drops it.)
+struct RectBits {
+    int xb, yb, db;  // bits of pxlo, of pylo, and of dx and dy each
+};
+constexpr uint32_t kRectBlkOut = 0u, kRectBlkMixed = 1u;
+// false: the rectangle does not fit the entry (the host then does not use the block table)
+__device__ __forceinline__ bool rect_pack_block(const RectQ &q, int satW, const RectBits rb, uint32_t &e) {
+    e = kRectBlkMixed;
+    if (q.code >= 0) {
+        e = (q.code & 3) == kClsOut ? kRectBlkOut : kRectBlkMixed;
+        return true;
+    }
+    if (q.dx >= (1 << rb.db) || q.dy >= (1 << rb.db)) return false;
+    const int pylo = q.base / satW, pxlo = q.base - pylo * satW;
+    e = (uint32_t)pxlo | ((uint32_t)pylo << rb.xb) | ((uint32_t)q.dx << (rb.xb + rb.yb)) |
+        ((uint32_t)q.dy << (rb.xb + rb.yb + rb.db));
+    return true;
+}
+__device__ __forceinline__ int classify_block_entry(const uint32_t e, const RectBits rb,
+                                                    const sat_t *__restrict__ sat, int satW) {
+    if (!(e >> (rb.xb + rb.yb))) return e == kRectBlkOut ? kClsOut : kClsMixed;
+    const int pxlo = (int)__builtin_amdgcn_ubfe(e, 0u, (unsigned)rb.xb);
+    const int pylo = (int)__builtin_amdgcn_ubfe(e, (unsigned)rb.xb, (unsigned)rb.yb);
+    RectQ q;
+    q.fast = 0;
+    q.dx = (int)__builtin_amdgcn_ubfe(e, (unsigned)(rb.xb + rb.yb), (unsigned)rb.db);
+    q.dy = (int)(e >> (rb.xb + rb.yb + rb.db));
+    const sat_t *s = sat + (pylo * satW + pxlo);
+    return rect_finish(q, s[0], s[q.dx], s[q.dy * satW], s[q.dy * satW + q.dx]);
+}
 // Pre-pass over coarse tiles of 64 x 32 x 32 voxels (64 sub-tiles each; striped
 // slabs use 64 x 64 x 8 so that a coarse tile stays inside one stripe): one wave
 // per coarse tile, lane i = view i.  A view that sees the whole coarse box as
@@ -1724,6 +1764,54 @@ __device__ __forceinline__ unsigned block_tests(const CarveParams &p, const SubT
     return needLanes;
 }
 
+// The same tests from the context's table of block rectangles (p.rcBlk): the lane loads its entry --
+// the sixteen blocks of a (view, sub-tile) pair are one run of 64 bytes -- where block_tests loads
+// the matrix and runs rect_prepare.  ri: the sub-tile's record index.  Every view of `views`
+// belongs to this wave (the large grids' instantiations: items are never shared).  A block outside
+// the grid has the entry "outside".
+__device__ __forceinline__ unsigned block_tests_cached(const CarveParams &p, const size_t ri, int vbase,
+                                                       unsigned long long views, int lane,
+                                                       unsigned &carved, unsigned &seen) {
+    const int q = lane >> 4;
+    const RectBits rb = {p.rcXB, p.rcYB, p.rcDB};
+    const size_t vstride = rec_count(p) << 4;  // entries of a view
+    const uint32_t *const tab = p.rcBlk + ((ri << 4) + (lane & 15));
+    unsigned needLanes = 0;  // lane s: blocks to project in the s-th view
+    int slot = 0;
+    while (views) {
+        int vb[4];
+        int n = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {  // the next four views (scalar)
+            vb[k] = 0;
+            if (views) {
+                vb[k] = __ffsll((long long)views) - 1;
+                views &= views - 1;
+                n = k + 1;
+            }
+        }
+        const int myb = q == 0 ? vb[0] : (q == 1 ? vb[1] : (q == 2 ? vb[2] : vb[3]));
+        int cls = kClsOut;
+        if (q < n) {
+            const int view = vbase + myb;
+            cls = classify_block_entry(tab[(size_t)view * vstride], rb,
+                                       p.sat + (size_t)view * p.satStride, p.satW) & 3;
+        }
+        const unsigned long long c = __ballot(cls == kClsCarved), f = __ballot(cls == kClsFg),
+                                 x = __ballot(cls == kClsMixed);
+        carved |= (unsigned)((c | (c >> 16) | (c >> 32) | (c >> 48)) & 0xffffu);
+        seen |= (unsigned)((f | (f >> 16) | (f >> 32) | (f >> 48)) & 0xffffu);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < n) {
+                const unsigned need16 = (unsigned)((x >> (16 * k)) & 0xffffu);
+                if (lane == slot) needLanes = need16;
+                ++slot;
+            }
+    }
+    return needLanes;
+}
+
 // The same tests with the views' matrices in LDS (sM: 12 floats per view, view 0 = p.v0) and NB
 // passes per round: the arithmetic of the round's passes first, then their table reads together,
 // then the answers -- one round trip to memory per NB * 4 views instead of two per 4 (the matrix,
@@ -1812,7 +1900,10 @@ __device__ __forceinline__ unsigned block_tests_lds(const CarveParams &p, const 
 // fewer registers alive across an item).
 // FRESH: the model is fresh (flags bit2) -- known when the kernel is compiled: no record is read.
 // FILTER (experiment builds): every view goes through the fp32 filter (filtered_view_blocks).
-template <bool LEFT, bool SPLIT = true, bool FRESH = false, bool FILTER = false>
+// CACHED: the block tests take their rectangles from the context's table (block_tests_cached) --
+// instantiated for the large grids' fresh kernels only: the kernel slows down with every run-time
+// path added to it.
+template <bool LEFT, bool SPLIT = true, bool FRESH = false, bool FILTER = false, bool CACHED = false>
 __global__ __launch_bounds__(256, (SPLIT && !FRESH ? ARVX_EXACT_SPLIT_WAVES_PER_SIMD : ARVX_EXACT_WAVES_PER_SIMD))
 void carve_exact_blocks_kernel(const CarveParams p) {
 #ifdef ARVX_TIMELINE
@@ -1917,10 +2008,15 @@ void carve_exact_blocks_kernel(const CarveParams p) {
 #else
                 constexpr bool no_bt = false;
 #endif
-                const unsigned needLanes = no_bt
-                                               ? 0xffffu
-                                               : block_tests(p, t, p.v0 + 64 * c, mixed, part, pshift,
-                                                             lane, bcarved, bseen);
+                unsigned needLanes = 0xffffu;
+                if constexpr (CACHED) {
+                    static_assert(!SPLIT, "the table's variant takes every view of an item");
+                    if (!no_bt)
+                        needLanes = block_tests_cached(p, rec_index(p, tx, ty, tz, wave), p.v0 + 64 * c,
+                                                       mixed, lane, bcarved, bseen);
+                } else if (!no_bt) {
+                    needLanes = block_tests(p, t, p.v0 + 64 * c, mixed, part, pshift, lane, bcarved, bseen);
+                }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     uint32_t w = st[m];

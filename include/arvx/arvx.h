@@ -715,6 +715,7 @@ int arvx_get_stats(arvx_ctx *ctx, arvx_stats *out);
 #define ARVX_PATH_FUSED 16u         /* one kernel for rectangle tests and voxels (FUSED, > 256 views) */
 #define ARVX_PATH_BRUTE_FORCE 32u   /* no rectangle tests at all (ARVX_CARVE_NO_CULL) */
 #define ARVX_PATH_STREAM 64u        /* the one-launch streaming carve (-DARVX_EXPERIMENTS builds) */
+#define ARVX_PATH_RECT_BLOCKS 128u  /* the exact kernel's block tests came from the table of cached rectangles */
 int arvx_last_carve_path(arvx_ctx *ctx, uint32_t out[4]);
 
 /* Diagnostic: how the context's last arvx_fast_carve grew its component.  Host bookkeeping; the
@@ -760,6 +761,23 @@ int arvx_selftest_view_tables(arvx_ctx *ctx, int view, uint32_t *bg_bits, uint16
  * std::round on every float in (-0.5, 2^24], i.e. every quotient that can fall inside an
  * image; *mismatches must come back 0. */
 int arvx_selftest_round(arvx_ctx *ctx, int64_t *mismatches);
+
+/* Cached rectangles.  The rectangle arithmetic of the carve depends on the cameras, the image size
+ * and the grid, not on the masks.  At the second consecutive carve of a fresh model under the same
+ * matrices, V, W and H that runs the large grids' kernels (dense classify + block-mapped exact kernel
+ * without item sharing: above 2^26 voxels, or the ARVX_CARVE_DENSE_CLASSIFY | ARVX_CARVE_WHOLE_ITEMS
+ * path flags) the context tabulates the pixel rectangles of its 4 x 4 x 4 blocks -- 4 bytes per
+ * (block, view): V / 16 bytes per voxel, 302 MB at 512^3 x 36 views -- and the exact kernel of the carves of a fresh model that follow loads them instead of computing
+ * them (ARVX_PATH_RECT_BLOCKS; the results are the same bit for bit).  That one carve synchronises.
+ * New matrices or sizes invalidate the table, and the second carve under the new ones builds it
+ * again; a caller who carves once pays nothing.  The table is built only while it fits `bytes`
+ * (default 2^30; 0: no table) and every block's pixel rectangle fits its entry.  The call releases
+ * the table; it is decided again under the new limit. */
+int arvx_ctx_set_rect_cache_limit(arvx_ctx *ctx, uint64_t bytes);
+
+/* Self-test hook: recomputes every entry of the table of cached rectangles; *mismatches, the entries
+ * that differ, must come back 0 (-1: the context holds no table). */
+int arvx_selftest_rect_cache(arvx_ctx *ctx, int64_t *mismatches);
 
 #ifdef __cplusplus
 }
