@@ -53,6 +53,7 @@ def build_host_tests() -> str:
     _make("tools/cpp", "all")  # arvx_bench6 (the reference's -c=6 table), arvx_dropin_time
     build_weld_host_test()
     build_smooth_host_test()
+    build_decimate_host_test()
     return os.path.join(ROOT, "tests", "cpp", "test_host")
 
 
@@ -66,6 +67,12 @@ def build_smooth_host_test() -> str:
     """g++ -> tests/cpp/test_smooth_host: arvx::smoothMesh (include/arvx/marching_cubes.hpp) on a
     welded mesh from a file, built as build_weld_host_test builds its test."""
     return _build_host_test("test_smooth_host")
+
+
+def build_decimate_host_test() -> str:
+    """g++ -> tests/cpp/test_decimate_host: arvx::decimateMesh (include/arvx/marching_cubes.hpp) on
+    a welded mesh from a file, built as build_weld_host_test builds its test."""
+    return _build_host_test("test_decimate_host")
 
 
 def _build_host_test(name: str) -> str:

@@ -42,6 +42,8 @@ FLOOD_FRESH = 2
 VOTES_COUNTS = 1
 VOTES_NO_CULL = 2
 COMPONENTS_LARGEST = 1
+DECIMATE_LATTICE = 0
+DECIMATE_SMOOTHED = 1
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
 # whole test module with the streaming carve forced on every fresh model (the library itself reads
 # no environment variable)
@@ -75,6 +77,7 @@ SYMBOLS = [
     "arvx_mc_cells", "arvx_mc_cells_download", "arvx_mc_mesh", "arvx_mc_mesh_download",
     "arvx_mc_mesh_download_faces", "arvx_mc_mesh_welded", "arvx_mc_mesh_welded_download",
     "arvx_mc_mesh_smooth", "arvx_mc_mesh_smooth_download",
+    "arvx_mc_mesh_decimate", "arvx_mc_mesh_decimate_download",
     "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
@@ -210,6 +213,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "arvx_mc_mesh_smooth"):
         lib.arvx_mc_mesh_smooth.argtypes = [p, C.c_int, C.c_float, C.c_float]
         lib.arvx_mc_mesh_smooth_download.argtypes = [p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "arvx_mc_mesh_decimate"):
+        lib.arvx_mc_mesh_decimate.argtypes = [p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.arvx_mc_mesh_decimate_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]
     if hasattr(lib, "arvx_color_visible"):
         lib.arvx_color_visible.argtypes = [p, C.c_int, C.c_float]
         lib.arvx_surface_visible_download.argtypes = [p, C.POINTER(C.c_int32)]
@@ -835,6 +842,34 @@ class Context:
         self._ck(self._lib.arvx_mc_mesh_smooth_download(
             self._h, v.ctypes.data if v is not None else None, n.ctypes.data if n is not None else None))
         return v, n
+
+    def mc_mesh_decimate(self, cell: int, source: int = 0, download: bool = True):
+        """Vertex clustering of the mesh of the last mc_mesh_welded (arvx_mc_mesh_decimate) with
+        cubes of cell^3 voxels; source: DECIMATE_LATTICE or DECIMATE_SMOOTHED (the positions of
+        the last mc_mesh_smooth).  Returns mc_mesh_decimate_download()'s tuple; download=False:
+        (Vd, Td), the result stays on the device."""
+        nv, nt = C.c_int64(), C.c_int64()
+        self._ck(self._lib.arvx_mc_mesh_decimate(self._h, int(cell), int(source), C.byref(nv), C.byref(nt)))
+        self._dec_vt = (int(nv.value), int(nt.value))
+        if not download:
+            return self._dec_vt
+        return self.mc_mesh_decimate_download()
+
+    def mc_mesh_decimate_download(self, verts: bool = True, faces: bool = True, vertex_rgb: bool = True,
+                                  members: bool = True, vmap: bool = True):
+        """arvx_mc_mesh_decimate_download: (verts (Vd, 3) float32, records (Td, 6) uint32 -- i0, i1,
+        i2, r, g, b --, vertex_rgb (Vd, 3) float32, members (Vd,) int32, map (V,) int32), each None
+        when not asked for."""
+        nv, nt = getattr(self, "_dec_vt", (0, 0))
+        V = getattr(self, "_weld_v", 0)
+        out = [np.empty((nv, 3), np.float32) if verts else None,
+               np.empty((nt, 6), np.uint32) if faces else None,
+               np.empty((nv, 3), np.float32) if vertex_rgb else None,
+               np.empty(nv, np.int32) if members else None,
+               np.empty(V, np.int32) if vmap else None]
+        self._ck(self._lib.arvx_mc_mesh_decimate_download(
+            self._h, *[a.ctypes.data if a is not None else None for a in out]))
+        return tuple(out)
 
     def render(self, M, W: int, H: int, background=None, download: bool = True):
         """arvx_render: the welded mesh's vertex voxels drawn into the camera M (3 x 4, world ->

@@ -36,6 +36,7 @@
 #include "mc_mesh_kernels.h"
 #include "mc_weld_kernels.h"
 #include "mc_smooth_kernels.h"
+#include "mc_decimate_kernels.h"
 #include "visibility_kernels.h"
 #include "photo_kernels.h"
 #include "components_kernels.h"
@@ -3352,6 +3353,7 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     ctx->free_mc();
     ctx->weld_ready = false;
     ctx->smooth_ready = ctx->smooth_csr_ready = false;  // (a new mesh: new CSRs)
+    ctx->dec_ready = false;                              // (... and the old one's decimation goes)
     ctx->render_ready = false;                           // (... and the old one's render goes)
     ctx->weld_verts = ctx->weld_tris = 0;
     *vertices = *triangles = 0;
@@ -3547,6 +3549,119 @@ int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals) {
         ctx->smooth_ready = ctx->smooth_csr_ready = false;
         return rc;
     }
+    return ARVX_OK;
+}
+
+// Vertex clustering of the welded mesh (mc_decimate_kernels.h).  V and T are known on the host and
+// Vd <= min(V, clusters), Td <= T: every buffer is sized from those bounds, nothing is retried, and
+// the two counts come back in their own count words at the call's ONE synchronisation.
+int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices, int64_t *triangles) {
+    ARVX_CHECK_CTX(ctx);
+    if (!vertices || !triangles) return fail(ARVX_ERR_INVALID, "null argument");
+    if (cell < 1 || cell > 64) return fail(ARVX_ERR_INVALID, "cell %d (1..64 voxels)", cell);
+    if (source != ARVX_DECIMATE_LATTICE && source != ARVX_DECIMATE_SMOOTHED)
+        return fail(ARVX_ERR_INVALID, "source %d (ARVX_DECIMATE_LATTICE or ARVX_DECIMATE_SMOOTHED)", source);
+    if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
+    if (source == ARVX_DECIMATE_SMOOTHED && !ctx->smooth_ready)
+        return fail(ARVX_ERR_STATE, "no smoothed mesh on this welded mesh (call arvx_mc_mesh_smooth)");
+    ctx->dec_ready = false;
+    ctx->dec_verts = ctx->dec_tris = 0;
+    const long long V = ctx->weld_verts, T = ctx->weld_tris;
+    if (V == 0) {
+        ctx->dec_ready = true;
+        *vertices = *triangles = 0;
+        return ARVX_OK;
+    }
+    arvx::DecGrid d;
+    d.X = ctx->X, d.Y = ctx->Y, d.Z = ctx->Z, d.XW = (ctx->X + 63) / 64;
+    d.cell = cell;
+    d.CX = (ctx->X + cell - 1) / cell, d.CY = (ctx->Y + cell - 1) / cell, d.CZ = (ctx->Z + cell - 1) / cell;
+    d.CXW = (d.CX + 63) / 64;
+    const arvx::BitGrid cg{d.CX, d.CY, d.CZ, d.CXW};
+    const size_t nw = (size_t)d.XW * ctx->Y * ctx->Z, ncw = (size_t)d.CXW * d.CY * d.CZ;
+    const long long vcap = std::min<long long>(V, (long long)d.CX * d.CY * d.CZ);
+    // the cluster plane, then its ranks (16-byte entries first)
+    ARVX_HIP(ctx->pool_dec_planes.reserve(ncw * (sizeof(arvx::SparseWord) + sizeof(unsigned long long))));
+    ARVX_HIP(ctx->pool_dec_index.reserve((size_t)vcap * sizeof(int)));
+    ARVX_HIP(ctx->pool_dec_verts.reserve((size_t)vcap * 3 * sizeof(float)));
+    ARVX_HIP(ctx->pool_dec_rgb.reserve((size_t)vcap * 3 * sizeof(float)));
+    ARVX_HIP(ctx->pool_dec_members.reserve((size_t)vcap * sizeof(int)));
+    ARVX_HIP(ctx->pool_dec_map.reserve((size_t)V * sizeof(int)));
+    arvx::SparseWord *d_crank = (arvx::SparseWord *)ctx->pool_dec_planes.p;
+    unsigned long long *d_cbits = (unsigned long long *)(d_crank + ncw);
+    int *d_cidx = (int *)ctx->pool_dec_index.p, *d_map = (int *)ctx->pool_dec_map.p;
+    const unsigned long long *d_vtx = (const unsigned long long *)ctx->pool_weld_planes.p + nw;
+    const arvx::SparseList vtx{(const arvx::SparseWord *)ctx->pool_weld_rank.p};
+    const float *q = (source == ARVX_DECIMATE_LATTICE || ctx->smooth_q == 0)
+                         ? (const float *)ctx->pool_weld_verts.p
+                         : (const float *)ctx->pool_smooth_verts.p + (ctx->smooth_q - 1) * 3 * V;
+    // (the control block holds both totals: it must not move between the compaction and the scan)
+    if (int rc = compact_control(ctx, (size_t)((T + arvx::kScanChunk - 1) / arvx::kScanChunk), nullptr)) return rc;
+    int *d_counts = nullptr;
+    if (int rc = chunk_counts(ctx, ncw, &d_counts)) return rc;
+    hipLaunchKernelGGL(arvx::mc_decimate_plane_kernel, dim3((unsigned)((ncw + 255) / 256)), dim3(256), 0,
+                       ctx->stream, d_vtx, d, d_cbits, d_counts);
+    ARVX_HIP(hipGetLastError());
+    const long long *d_nverts = nullptr;
+    if (int rc = bit_compact(ctx, d_cbits, ncw, cg, vcap, d_cidx, d_crank, Ctx::kDecVerts, &d_nverts)) return rc;
+    hipLaunchKernelGGL(arvx::mc_decimate_vertex_kernel, dim3((unsigned)((vcap + 255) / 256)), dim3(256), 0,
+                       ctx->stream, (const int *)d_cidx, vcap, d_nverts, d, vtx, V, q,
+                       (const float *)ctx->pool_weld_rgb.p, (float *)ctx->pool_dec_verts.p,
+                       (float *)ctx->pool_dec_rgb.p, (int *)ctx->pool_dec_members.p);
+    ARVX_HIP(hipGetLastError());
+    hipLaunchKernelGGL(arvx::mc_decimate_map_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const int *)ctx->pool_weld_index.p, V, d, arvx::SparseList{d_crank}, d_map);
+    ARVX_HIP(hipGetLastError());
+    if (T > 0) {
+        ARVX_HIP(ctx->pool_dec_faces.reserve((size_t)T * 6 * sizeof(unsigned)));
+        ARVX_HIP(ctx->pool_dec_flags.reserve((size_t)T * 2 * sizeof(int)));
+        ARVX_HIP(ctx->pool_dec_slots.reserve((size_t)vcap * arvx::kDecSlots * sizeof(unsigned)));
+        const unsigned *faces = (const unsigned *)ctx->pool_weld_faces.p;
+        unsigned *d_slots = (unsigned *)ctx->pool_dec_slots.p;
+        int *d_flags = (int *)ctx->pool_dec_flags.p, *d_off = d_flags + T;
+        const unsigned blocks_t = (unsigned)((T + 255) / 256);
+        ARVX_HIP(hipMemsetAsync(d_slots, 0xff, (size_t)vcap * arvx::kDecSlots * sizeof(unsigned), ctx->stream));
+        hipLaunchKernelGGL(arvx::mc_decimate_claim_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T, V,
+                           (const int *)d_map, (const int *)d_cidx, vcap, d_nverts, d, d_slots);
+        ARVX_HIP(hipGetLastError());
+        hipLaunchKernelGGL(arvx::mc_decimate_flag_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T, V,
+                           (const int *)d_map, (const int *)d_cidx, vcap, d_nverts, d, (const unsigned *)d_slots,
+                           d_flags);
+        ARVX_HIP(hipGetLastError());
+        if (int rc = scan_counts(ctx, d_flags, nullptr, T, nullptr, d_off, Ctx::kDecTris, nullptr)) return rc;
+        hipLaunchKernelGGL(arvx::mc_decimate_write_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T, V,
+                           (const int *)d_map, (const int *)d_flags, (const int *)d_off, T,
+                           (unsigned *)ctx->pool_dec_faces.p);
+        ARVX_HIP(hipGetLastError());
+    }
+    ARVX_SYNC(ctx);
+    const long long nverts = host_total(ctx, Ctx::kDecVerts), ntris = T > 0 ? host_total(ctx, Ctx::kDecTris) : 0;
+    if (nverts < 0 || ntris < 0) return fail(ARVX_ERR_HIP, "the decimation's kernels left no count");
+    if (nverts > vcap || ntris > T) return fail(ARVX_ERR_HIP, "the decimated mesh outgrew the welded one");
+    ctx->dec_verts = nverts;
+    ctx->dec_tris = ntris;
+    ctx->dec_ready = true;
+    *vertices = nverts;
+    *triangles = ntris;
+    return ARVX_OK;
+}
+
+int arvx_mc_mesh_decimate_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb,
+                                   int32_t *members, int32_t *map) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->dec_ready) return fail(ARVX_ERR_STATE, "no decimated mesh (call arvx_mc_mesh_decimate)");
+    const size_t Vd = (size_t)ctx->dec_verts, Td = (size_t)ctx->dec_tris, V = (size_t)ctx->weld_verts;
+    if (Vd > 0 && verts)
+        ARVX_HIP(hipMemcpyAsync(verts, ctx->pool_dec_verts.p, Vd * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if (Td > 0 && faces)
+        ARVX_HIP(hipMemcpyAsync(faces, ctx->pool_dec_faces.p, Td * 24, hipMemcpyDeviceToHost, ctx->stream));
+    if (Vd > 0 && vertex_rgb)
+        ARVX_HIP(hipMemcpyAsync(vertex_rgb, ctx->pool_dec_rgb.p, Vd * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if (Vd > 0 && members)
+        ARVX_HIP(hipMemcpyAsync(members, ctx->pool_dec_members.p, Vd * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (V > 0 && map)
+        ARVX_HIP(hipMemcpyAsync(map, ctx->pool_dec_map.p, V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
     return ARVX_OK;
 }
 

@@ -75,6 +75,7 @@ struct Ctx {
         kSurface, kClosure, kCells, kTris, kVerts,  // list lengths, in the device copies' order
         kSmoothScan,                    // arvx_mc_mesh_smooth's offset scans: a total nobody reads
         kComponents,                    // the component table's length (arvx_components[_keep])
+        kDecVerts, kDecTris,            // arvx_mc_mesh_decimate: decimated vertices, surviving faces
         kDeviceTotals,
         kPhotoRemoved = kDeviceTotals,  // voxels an iteration of arvx_photo_carve removed
         kVisNeed,                       // large footprints the visible pass wanted to list
@@ -276,7 +277,7 @@ struct Ctx {
     // calls drop() once, after its refusals and before its work, so that a refused call leaves the
     // context as it was.  (The closure calls it where its fills go into the state: the colour pass's
     // planes it starts from are those of the state before.)  The mesh products (mc_ready,
-    // weld_ready, smooth_*) are not here: each lives until the next call of its own stage.  The
+    // weld_ready, smooth_*, dec_ready) are not here: each lives until the next call of its own stage.  The
     // render of the welded mesh (arvx_render) is: it shows the state the mesh was built from, so
     // whatever replaces that state drops it (and so does the next arvx_mc_mesh_welded).
     enum class Event {
@@ -363,6 +364,13 @@ struct Ctx {
         pool_smooth_normals;
     bool smooth_csr_ready = false, smooth_ready = false;
     int smooth_q = 0;  // where the smoothed positions are: 0 the welded mesh's, 1 / 2 a buffer
+    // arvx_mc_mesh_decimate: the cluster plane and its ranks, the cluster list, the decimated mesh
+    // (positions, colours, member counts, face records), the welded vertices' map, the faces' flags
+    // and offsets, and the slot table (mc_decimate_kernels.h), sized at first use and kept
+    DevPool pool_dec_planes, pool_dec_index, pool_dec_verts, pool_dec_rgb, pool_dec_members, pool_dec_map,
+        pool_dec_faces, pool_dec_flags, pool_dec_slots;
+    int64_t dec_verts = 0, dec_tris = 0;
+    bool dec_ready = false;
 
     // arvx_render: the W x H keys, the images (id | depth | bgr), the large-footprint list behind
     // its header (render_kernels.h), all sized at first use and kept.  Count words: kRenderNeed, then

@@ -643,6 +643,51 @@ int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, f
 int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu);
 int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals);
 
+/* The welded mesh reduced by vertex clustering (Rossignac-Borrel; an extension beyond the
+ * reference).  Definition, on the welded mesh of the last arvx_mc_mesh_welded -- V vertices with
+ * lattice positions l_i (integers stored as fp32), vertex colours col_i, T face records {i0, i1,
+ * i2, r, g, b} --, an integer cell, 1 <= cell <= 64, and a source: ARVX_DECIMATE_LATTICE with
+ * q_i = l_i, or ARVX_DECIMATE_SMOOTHED with q_i the positions of the last arvx_mc_mesh_smooth on
+ * this welded mesh:
+ *   - the cluster of vertex i is (l_i.x / cell, l_i.y / cell, l_i.z / cell), integer division; its
+ *     flat index is taken over a cluster grid of ceil(X / cell) x ceil(Y / cell) x ceil(Z / cell),
+ *     x fastest;
+ *   - decimated vertices: the non-empty clusters in ascending flat index, Vd of them; map[i] is the
+ *     decimated index of welded vertex i;
+ *   - the members of a cluster are its welded vertices in ascending i (ascending (z, y, x) inside
+ *     the cluster's box); members[d] is their count n;
+ *   - position and colour of a decimated vertex, per component, every fp32 operation rounded on its
+ *     own (no fma): s = +0; s = s + q_i over the members ascending; the result is s / (float)n, an
+ *     IEEE quotient.  The colour is the same sum over col_i;
+ *   - clustering always uses the lattice positions: the clusters, map, members, the colours and
+ *     the faces do not depend on the source;
+ *   - faces: face t maps to (map[i0], map[i1], map[i2]).  A face with two equal mapped corners is
+ *     dropped.  Among the faces with the same set of three mapped corners (unordered, whatever the
+ *     winding) only the one with the least t stays.  The survivors keep ascending t order, their
+ *     corner order (the winding) and their own r, g, b.  Td of them.
+ * So cell = 1 gives Vd = V, the positions unchanged, and the welded mesh without its degenerate and
+ * repeated faces; a cell no smaller than the grid gives Vd <= 1 and Td = 0; an empty welded mesh
+ * gives 0 and 0.
+ * arvx_mc_mesh_decimate acts on the context's welded mesh with ONE host synchronisation and returns
+ * Vd and Td.  Its buffers are sized from the bounds the host knows -- Vd <= min(V, clusters),
+ * Td <= T --, so nothing is retried; beside the outputs (24 Vd + 4 Vd + 4 V + 24 T bytes) it keeps
+ * 8 T bytes of flags and offsets, the cluster plane and, for the duplicate test, a table of 78
+ * 4-byte slots -- 312 bytes -- per possible decimated vertex, all sized at first use and kept.
+ * arvx_mc_mesh_decimate_download copies 3 Vd floats of positions, 6 Td uints of face records,
+ * 3 Vd floats of colours, Vd member counts and V map entries; any pointer may be null.
+ * Refusals.  ARVX_ERR_STATE: no welded mesh (slab and striped contexts never have one);
+ * ARVX_DECIMATE_SMOOTHED without a smoothed mesh on this welded mesh; a download before a
+ * decimation.  ARVX_ERR_INVALID: cell outside [1, 64]; an unknown source; null count pointers.  A
+ * refused call leaves the previous decimated mesh as it was.
+ * The decimated mesh lives until the next arvx_mc_mesh_decimate or the next arvx_mc_mesh_welded.
+ * It changes nothing else: the welded and smoothed meshes, a render and arvx_mc_mesh stay as they
+ * were. */
+#define ARVX_DECIMATE_LATTICE 0
+#define ARVX_DECIMATE_SMOOTHED 1
+int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices, int64_t *triangles);
+int arvx_mc_mesh_decimate_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb,
+                                   int32_t *members, int32_t *map);
+
 /* ---- render (extension beyond the reference) -------------------------------------------------
  * Draws the welded mesh's vertex voxels into a camera view: the model over a photograph, the voxel
  * under a pixel, a carve checked against its own silhouettes.  Definition, on a whole-grid context

@@ -23,11 +23,14 @@
 #define ARVX_MARCHING_CUBES_HPP
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <fstream>
+#include <map>
 #include <numeric>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -544,6 +547,103 @@ inline bool marchingCubesSmoothed(Model *model, float scale = 1.0f, Vec3f transl
     return detail::marching_cubes_write(model, scale, translation, threshold, outFileName,
                                         [=](Model *m, float t) {
                                             return marchingCubesMeshSmoothed(m, t, iterations, lambda, mu);
+                                        });
+}
+
+// ---- decimated mesh (an extension beyond the reference) -----------------------------------------
+//
+// The definition of arvx_mc_mesh_decimate (include/arvx/arvx.h) on the host, for a welded mesh
+// whose vertices lie on the lattice (for any other mesh the cluster of a vertex is floor(p) / cell,
+// floored, and the clusters are taken in ascending (z, y, x)): vertices that fall into the same
+// cube of cell^3 voxels become one, at the mean of `smoothed`'s positions when it is given (same
+// vertex count; the clusters always come from `welded`) or of their own; faces that lose a corner
+// go, of the faces with the same corner set the first stays.  members (may be null): welded
+// vertices per decimated vertex; map (may be null): the decimated index of every welded vertex.
+// (Compiled with -ffp-contract=off, as the tools and tests are, this is bit for bit what the device
+// computes.)
+inline SimpleMesh decimateMesh(const SimpleMesh &welded, int cell, const SimpleMesh *smoothed = nullptr,
+                               std::vector<int32_t> *members = nullptr, std::vector<int32_t> *map = nullptr) {
+    if (cell < 1) throw std::invalid_argument("decimateMesh: cell must be >= 1");
+    const HostVector<Vec3f> &lattice = welded.GetVertices();
+    const HostVector<Vec3f> &q = smoothed ? smoothed->GetVertices() : lattice;
+    const size_t V = lattice.size();
+    if (q.size() != V) throw std::invalid_argument("decimateMesh: the smoothed mesh has other vertices");
+    auto cluster_of = [cell](float p) {
+        const long long l = (long long)std::floor(p);
+        return l >= 0 ? l / cell : -((-l + cell - 1) / cell);
+    };
+    // clusters in ascending (z, y, x); their members arrive in ascending vertex index
+    std::map<std::array<long long, 3>, std::vector<unsigned int>> clusters;
+    for (size_t i = 0; i < V; ++i)
+        clusters[{cluster_of(lattice[i].z()), cluster_of(lattice[i].y()), cluster_of(lattice[i].x())}].push_back(
+            (unsigned int)i);
+    SimpleMesh out;
+    std::vector<unsigned int> index(V);
+    if (members) members->clear();
+    for (const auto &c : clusters) {
+        const float n = (float)c.second.size();
+        Vec3f s(0, 0, 0);
+        for (unsigned int i : c.second)
+            for (int k = 0; k < 3; ++k) s[k] = s[k] + q[i][k];
+        const unsigned int at = out.AddVertex(Vec3f(s.x() / n, s.y() / n, s.z() / n));
+        for (unsigned int i : c.second) index[i] = at;
+        if (members) members->push_back((int32_t)c.second.size());
+    }
+    if (map) map->assign(index.begin(), index.end());
+    std::map<std::array<unsigned int, 3>, bool> seen;
+    for (const Triangle &t : welded.GetTriangles()) {
+        const unsigned int a = index[t.idx0], b = index[t.idx1], c = index[t.idx2];
+        if (a == b || b == c || a == c) continue;
+        std::array<unsigned int, 3> key{a, b, c};
+        std::sort(key.begin(), key.end());
+        if (!seen.emplace(key, true).second) continue;
+        out.AddFace(a, b, c, t.r, t.g, t.b);
+    }
+    return out;
+}
+
+// marchingCubesMeshWelded, decimated: decimateMesh of the welded mesh (iterations = 0) or of the
+// welded mesh with smoothMesh's positions (iterations > 0).  When every w is 0 or 1 the device
+// does all of it (arvx_mc_mesh_welded, arvx_mc_mesh_smooth, arvx_mc_mesh_decimate) and only the
+// decimated mesh crosses PCIe; a model with fractional w is decimated on the host.
+inline SimpleMesh marchingCubesMeshDecimated(Model *model, float threshold = 0.5f, int cell = 2,
+                                             int iterations = 0, float lambda = 0.5f, float mu = -0.53f) {
+    if (!(threshold > 0.f)) return SimpleMesh();
+    bool on_device = false;
+    (void)model->inside_state(threshold, on_device);
+    if (!on_device) {
+        const SimpleMesh welded = marchingCubesMeshWelded(model, threshold);
+        if (iterations <= 0) return decimateMesh(welded, cell);
+        const SimpleMesh smoothed = smoothMesh(welded, iterations, lambda, mu);
+        return decimateMesh(welded, cell, &smoothed);
+    }
+    int apply_unseen = 0;
+    arvx_ctx *ctx = detail::mesh_context(model, apply_unseen);
+    int64_t nv = 0, nt = 0, dv = 0, dt = 0;
+    detail::check(arvx_mc_mesh_welded(ctx, apply_unseen, &nv, &nt), "arvx_mc_mesh_welded");
+    if (iterations > 0) detail::check(arvx_mc_mesh_smooth(ctx, iterations, lambda, mu), "arvx_mc_mesh_smooth");
+    detail::check(arvx_mc_mesh_decimate(ctx, cell, iterations > 0 ? ARVX_DECIMATE_SMOOTHED : ARVX_DECIMATE_LATTICE,
+                                        &dv, &dt),
+                  "arvx_mc_mesh_decimate");
+    SimpleMesh mesh;
+    HostVector<Vec3f> &mv = mesh.GetVertices();
+    HostVector<Triangle> &mt = mesh.GetTriangles();
+    mv.resize((size_t)dv);  // (recycled memory, not zeroed: host_pool.hpp)
+    mt.resize((size_t)dt);
+    detail::check(arvx_mc_mesh_decimate_download(ctx, dv ? mv[0].data() : nullptr, dt ? &mt[0].idx0 : nullptr,
+                                                 nullptr, nullptr, nullptr),
+                  "arvx_mc_mesh_decimate_download");
+    return mesh;
+}
+
+// marchingCubes writing the decimated welded mesh: marchingCubes' arguments, log lines and
+// Benchmark stage, then the cell and the smoothing's arguments.
+inline bool marchingCubesDecimated(Model *model, float scale = 1.0f, Vec3f translation = Vec3f(0, 0, 0),
+                                   float threshold = 0.5f, std::string outFileName = "out/mesh.off",
+                                   int cell = 2, int iterations = 0, float lambda = 0.5f, float mu = -0.53f) {
+    return detail::marching_cubes_write(model, scale, translation, threshold, outFileName,
+                                        [=](Model *m, float t) {
+                                            return marchingCubesMeshDecimated(m, t, cell, iterations, lambda, mu);
                                         });
 }
 

@@ -227,7 +227,7 @@ int main(int argc, char *argv[]) {
         {"z", "100"}, {"size", "0.0028"}, {"color", "0"}, {"scale", "1.0"}, {"dx", "0.0"},
         {"dy", "0.0"}, {"dz", "0.0"}, {"model_debug", "false"}, {"postprocessing", "true"},
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
-        {"smooth", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
+        {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
         {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
@@ -237,6 +237,8 @@ int main(int argc, char *argv[]) {
                      "  -postprocessing, -intermediateMesh, -outFile (flags of the reference's "
                      "src/main.cpp:16-39), -weld (shared mesh vertices),\n"
                      "  -smooth=N (the welded mesh after N Taubin iterations, lambda 0.5, mu -0.53),\n"
+                     "  -decimate=C (the welded mesh -- after -smooth=N, if given -- with the vertices of\n"
+                     "    every cube of C^3 voxels merged into one, 1 <= C <= 64; 0, the default: off),\n"
                      "  -visible=true (-color=1|2 over the views in which each voxel is visible),\n"
                      "  -visibleTol=T (its depth tolerance in voxel edges, default 3),\n"
                      "  -misses=K (-carve=1: empty a voxel only when more than K views see it as\n"
@@ -444,8 +446,12 @@ int main(int argc, char *argv[]) {
                       << std::endl;
         if (parser.b("postprocessing")) arvx::applyClosure(&model, 3);
         // -weld (an extension beyond the reference): the same mesh with shared vertices;
-        // -smooth=N (N > 0): that mesh after N Taubin iterations
-        if (parser.i("smooth") > 0)
+        // -smooth=N (N > 0): that mesh after N Taubin iterations; -decimate=C (C > 0): the welded
+        // (and smoothed) mesh reduced by vertex clustering
+        if (parser.i("decimate") > 0)
+            arvx::marchingCubesDecimated(&model, parser.f("scale"), modelTranslation, 0.5f, parser.str("outFile"),
+                                         parser.i("decimate"), std::max(parser.i("smooth"), 0));
+        else if (parser.i("smooth") > 0)
             arvx::marchingCubesSmoothed(&model, parser.f("scale"), modelTranslation, 0.5f,
                                         parser.str("outFile"), parser.i("smooth"));
         else if (parser.b("weld"))
