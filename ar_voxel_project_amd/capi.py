@@ -85,6 +85,8 @@ SYMBOLS = [
     "arvx_selftest_divide",
     "arvx_selftest_round",
     "arvx_ctx_set_rect_cache_limit", "arvx_selftest_rect_cache",
+    "arvx_ctx_set_view_window", "arvx_view_window", "arvx_view_window_host",
+    "arvx_selftest_fill_view_tables", "arvx_selftest_view_table_raw",
 ]
 
 
@@ -194,6 +196,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "arvx_selftest_rect_cache") or not ab_build:
         lib.arvx_ctx_set_rect_cache_limit.argtypes = [p, C.c_uint64]
         lib.arvx_selftest_rect_cache.argtypes = [p, C.POINTER(C.c_int64)]
+    if hasattr(lib, "arvx_view_window") or not ab_build:
+        lib.arvx_ctx_set_view_window.argtypes = [p, C.c_int]
+        lib.arvx_view_window.argtypes = [p, C.c_int, C.POINTER(C.c_int)]
+        lib.arvx_view_window_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, f32p, C.c_int, C.c_int,
+                                              C.POINTER(C.c_int)]
+        lib.arvx_selftest_fill_view_tables.argtypes = [p, C.c_int]
+        lib.arvx_selftest_view_table_raw.argtypes = [p, C.c_int, C.c_void_p]
     if hasattr(lib, "arvx_mc_cells") or not ab_build:
         lib.arvx_mc_cells.argtypes = [p, C.POINTER(C.c_int64)]
         lib.arvx_mc_cells_download.argtypes = [p, C.POINTER(C.c_int32)]
@@ -276,6 +285,16 @@ def compose_projection(K, Rt) -> np.ndarray:
     M = np.empty(12, np.float32)
     _check(load_library().arvx_compose_projection(_fp(K), _fp(Rt), _fp(M)))
     return M.reshape(3, 4)
+
+
+def view_window_host(X: int, Y: int, Z: int, voxel_size: float, M, W: int, H: int) -> Tuple[int, int, int, int]:
+    """(first row, last row, first column, last column), inclusive, of the part of a view's
+    summed-area table that the one-launch view derivation writes for a grid of X x Y x Z voxels
+    under the camera M (3 x 4): arvx_view_window_host, host arithmetic only."""
+    M = _f32(M).reshape(12)
+    rect = (C.c_int * 4)()
+    _check(load_library().arvx_view_window_host(X, Y, Z, C.c_float(voxel_size), _fp(M), W, H, rect))
+    return tuple(int(r) for r in rect)
 
 
 def stripe_planes(Z: int, world: int, rank: int) -> np.ndarray:
@@ -941,6 +960,33 @@ class Context:
         """Bytes the context's table of cached rectangles may take (0: none).  Releases the table;
         it is built again, under the new limit, by the carves that follow."""
         self._ck(self._lib.arvx_ctx_set_rect_cache_limit(self._h, nbytes))
+
+    def set_view_window(self, on: bool) -> None:
+        """Whether set_views writes only the part of each summed-area table that this context's
+        grid projects into (default) or whole tables; from the next set_views on."""
+        self._ck(self._lib.arvx_ctx_set_view_window(self._h, int(bool(on))))
+
+    def view_window(self, view: int) -> Tuple[int, int, int, int]:
+        """(first row, last row, first column, last column), inclusive, of view `view`'s table that
+        the last set_views wrote."""
+        rect = (C.c_int * 4)()
+        self._ck(self._lib.arvx_view_window(self._h, view, rect))
+        return tuple(int(r) for r in rect)
+
+    def selftest_fill_view_tables(self, value: int) -> None:
+        """Every byte of the table buffer <- value; the views count as not derived."""
+        self._ck(self._lib.arvx_selftest_fill_view_tables(self._h, int(value)))
+
+    def selftest_view_table_raw(self, view: int, H: int) -> np.ndarray:
+        """View `view`'s table as it stands, (H + 1, ld) uint16, padding columns included; the
+        entries outside the window are NOT written first (selftest_view_tables does that)."""
+        ld = C.c_int()
+        self._lib.arvx_selftest_view_tables.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                        C.POINTER(C.c_int)]
+        self._ck(self._lib.arvx_selftest_view_tables(self._h, view, None, None, C.byref(ld)))
+        table = np.zeros((H + 1, ld.value), np.uint16)
+        self._ck(self._lib.arvx_selftest_view_table_raw(self._h, view, table.ctypes.data))
+        return table
 
     def selftest_rect_cache(self) -> int:
         """Entries of the table of cached rectangles that differ from a recomputation: must be 0

@@ -618,6 +618,160 @@ int arvx_ctx_voxels(const arvx_ctx *ctx, int64_t *count) {
 
 // ---- views -------------------------------------------------------------------
 
+// The WINDOW of a view: the part of its summed-area table that a rectangle test of a box of voxels
+// of the grid X x Y x Z (voxel indices 0 .. X-1, 0 .. Y-1, global z 0 .. Z-1: every slab, halo
+// plane and stripe, and the coarse boxes of striped slabs that span foreign planes) can read.
+// Host arithmetic in double; it depends on the matrix, the image size, the voxel size and the grid,
+// not on the masks.
+//
+// rect_prepare (carve_kernels.h) clamps nothing: for a box it returns the pixel rectangle
+//   [ceil(umin - mu - 1/2), floor(umax + mu + 1/2)] x [ceil(vmin - mv - 1/2), floor(vmax + mv + 1/2)]
+// with umin .. vmax taken over the fp32 quotients at the box's eight corners, and reads the table
+// (code < 0) only when that rectangle lies inside the image; it then reads the entries
+// (pylo .. pyhi + 1, pxlo .. pxhi + 1).
+//  (1) A sub-box's corners w = fl32(i * s) lie inside the grid's box (rounding is monotone).  The
+//      rows a_r are affine in w and u = a_0 / a_2 is linear-fractional, so where a_2 keeps its sign
+//      over the grid's box the REAL u at every corner of every sub-box lies between the smallest
+//      and the largest real u at the grid's eight corners, [Umin, Umax].
+//  (2) A sub-box's COMPUTED corner quotient differs from the real one by at most
+//        errU = (eps_0 + Ua eps_2) / (cabs - 2 eps_2) + 2^-20 Ua + 2^-12
+//      (the error budget written at classify_box) with eps_r = 2^-19 E_r, E_r = sum_k |M[r][k]| max
+//      |w_k| over the GRID (a sub-box's is not larger), Ua = max |U| over the grid's corners and
+//      cabs = min |a_2| over the grid's corners: a sub-box's computed |a_2| is at least cabs - eps_2
+//      and the budget divides by that less eps_2.
+//  (3) A sub-box's margin mu is the same expression in its own fp32 quantities, times 1.0001:
+//      bounded by mu = 1.001 (eps_0 + Ua' eps_2) / (cabs - 2 eps_2) + 2^-20 Ua' + 2^-12 with
+//      Ua' = Ua + errU.  (eps_r carries a factor 1.001 here for the fp32 roundings of E_r.)
+//  (4) So every rectangle lies in [Umin - errU - mu - 1/2, Umax + errU + mu + 1/2]; one whole pixel
+//      is added on each side for what fp32 does to these sums and roundings (|u| < 10^6: an fp32
+//      sum is off by less than 1/8), and +1 on the high side for the table's border.
+//  (5) The result is clipped to the table and rounded outwards to the tiles of views_strip_kernel:
+//      strip I = (table row - 1) / 64 (row 0 is written by strip 0), tile column J = column / 64.
+// The view takes the whole table when a_2 changes sign over the grid or comes within 16 eps_2 of
+// zero (cameras inside or at the grid: the argument of (1) and the divisor of (2) need more), or
+// when |u| or |v| reaches 10^6 at a corner.
+// win: {I0, I1, J0, J1}, inclusive.  Returns whether the window is the whole table.
+static bool view_window(int X, int Y, int Z, float s, const float *M, int W, int H, int win[4]) {
+    const int TI = (H + 63) / 64, JL = W / 64;  // last tile column: that of table column W
+    win[0] = 0;
+    win[1] = TI - 1;
+    win[2] = 0;
+    win[3] = JL;
+    // the grid's box as make_box forms it
+    const double wy[2] = {0.0, (double)((float)(Y - 1) * s)};
+    const double wx[2] = {0.0, (double)((float)(X - 1) * s)};
+    const double wz[2] = {0.0, (double)((float)(-(Z - 1)) * s)};
+    double E[3], lo[3], hi[3];
+    double a[3][8];
+    for (int r = 0; r < 3; ++r) {
+        const double m0 = M[4 * r], m1 = M[4 * r + 1], m2 = M[4 * r + 2], m3 = M[4 * r + 3];
+        E[r] = std::fabs(m0) * std::fabs(wy[1]) + std::fabs(m1) * std::fabs(wx[1]) +
+               std::fabs(m2) * std::fabs(wz[1]) + std::fabs(m3);
+        for (int c = 0; c < 8; ++c) a[r][c] = m0 * wy[c & 1] + m1 * wx[(c >> 1) & 1] + m2 * wz[c >> 2] + m3;
+    }
+    double cmin = INFINITY, cmax = -INFINITY;
+    for (int c = 0; c < 8; ++c) {
+        cmin = std::fmin(cmin, a[2][c]);
+        cmax = std::fmax(cmax, a[2][c]);
+    }
+    const double k19 = 1.001 / 524288.0, k20 = 1.0 / 1048576.0, k12 = 1.0 / 4096.0;
+    const double eps0 = E[0] * k19, eps1 = E[1] * k19, eps2 = E[2] * k19;
+    if (!(cmin > 0.0 || cmax < 0.0)) return true;  // a_2 changes sign (also NaN)
+    const double cabs = cmin > 0.0 ? cmin : -cmax;
+    if (!(cabs > 16.0 * eps2 + 1e-30)) return true;
+    const double D = cabs - 2.0 * eps2;
+    for (int r = 0; r < 2; ++r) {
+        lo[r] = INFINITY;
+        hi[r] = -INFINITY;
+        for (int c = 0; c < 8; ++c) {
+            const double u = a[r][c] / a[2][c];
+            lo[r] = std::fmin(lo[r], u);
+            hi[r] = std::fmax(hi[r], u);
+        }
+    }
+    int t0[2], t1[2];  // table columns / rows, inclusive
+    for (int r = 0; r < 2; ++r) {
+        const double Ua = std::fmax(std::fabs(lo[r]), std::fabs(hi[r]));
+        if (!(Ua < 1.0e6)) return true;  // also NaN
+        const double epsr = r == 0 ? eps0 : eps1;
+        const double err = (epsr + Ua * eps2) / D + Ua * k20 + k12;
+        const double Ub = Ua + err;
+        const double mu = 1.001 * (epsr + Ub * eps2) / D + Ub * k20 + k12;
+        const double n = r == 0 ? (double)W : (double)H;
+        double l = std::floor(lo[r] - err - mu - 0.5) - 1.0;
+        double h = std::ceil(hi[r] + err + mu + 0.5) + 1.0 + 1.0;  // slack, then the border
+        if (!(l == l && h == h)) return true;
+        l = std::fmin(std::fmax(l, 0.0), n);  // (entries 0 .. n of the table)
+        h = std::fmin(std::fmax(h, l), n);
+        t0[r] = (int)l;
+        t1[r] = (int)h;
+    }
+    win[2] = t0[0] / 64;
+    win[3] = t1[0] / 64;
+    win[0] = t0[1] <= 1 ? 0 : (t0[1] - 1) / 64;
+    win[1] = t1[1] <= 1 ? 0 : (t1[1] - 1) / 64;
+    return win[0] == 0 && win[1] == TI - 1 && win[2] == 0 && win[3] == JL;
+}
+static uint32_t window_word(const int win[4]) {
+    return (uint32_t)win[0] | ((uint32_t)win[1] << 8) | ((uint32_t)win[2] << 16) | ((uint32_t)win[3] << 24);
+}
+// the table rows and columns (inclusive) that the tiles of a window word cover
+static void window_rect(uint32_t w, int H, int satW, int rect[4]) {
+    const int I0 = (int)(w & 0xffu), I1 = (int)((w >> 8) & 0xffu), J0 = (int)((w >> 16) & 0xffu), J1 = (int)(w >> 24);
+    rect[0] = I0 == 0 ? 0 : 64 * I0 + 1;
+    rect[1] = std::min(H, 64 * (I1 + 1));
+    rect[2] = 64 * J0;
+    rect[3] = std::min(satW - 1, 64 * J1 + 63);
+}
+
+int arvx_view_window_host(int X, int Y, int Z, float voxel_size, const float M[12], int W, int H,
+                          int rect[4]) {
+    if (!M || !rect) return fail(ARVX_ERR_INVALID, "null argument");
+    if (X < 1 || Y < 1 || Z < 1 || !(voxel_size > 0.f)) return fail(ARVX_ERR_INVALID, "bad grid");
+    if (W < 1 || H < 1 || W > arvx::kMaxImageDim || H > arvx::kMaxImageDim)
+        return fail(ARVX_ERR_INVALID, "image size %dx%d out of range", W, H);
+    int win[4];
+    view_window(X, Y, Z, voxel_size, M, W, H, win);
+    window_rect(window_word(win), H, (W + 1 + 63) / 64 * 64, rect);
+    return ARVX_OK;
+}
+
+// The window words of the next derivation, on the device: those of the cameras where the strip
+// kernel runs with windows (strip), the whole table everywhere else.  Sent only when one differs
+// from what the device holds.
+static int views_windows(Ctx *ctx, bool strip) {
+    const int V = ctx->V;
+    if (!ctx->win_valid) {
+        ctx->h_win_geo.resize(V);
+        for (int v = 0; v < V; ++v) {
+            int win[4];
+            view_window(ctx->X, ctx->Y, ctx->Z, ctx->s, ctx->h_M.data() + 12 * (size_t)v, ctx->W, ctx->H, win);
+            ctx->h_win_geo[v] = window_word(win);
+        }
+        ctx->win_valid = true;
+    }
+    const int whole[4] = {0, (ctx->H + 63) / 64 - 1, 0, ctx->W / 64};
+    const uint32_t all = window_word(whole);
+    const bool geo = strip && ctx->win_on;
+    bool same = ctx->h_win.size() == (size_t)V && ctx->pool_win.cap >= (size_t)V * sizeof(uint32_t);
+    ctx->sat_partial = false;
+    for (int v = 0; v < V; ++v) {
+        const uint32_t w = geo ? ctx->h_win_geo[v] : all;
+        if (w != all) ctx->sat_partial = true;
+        same = same && ctx->h_win[v] == w;
+    }
+    if (!same) {
+        ARVX_HIP(ctx->pool_win.reserve((size_t)V * sizeof(uint32_t)));
+        if (geo)
+            ctx->h_win = ctx->h_win_geo;
+        else
+            ctx->h_win.assign(V, all);
+        ARVX_HIP(hipMemcpyAsync(ctx->pool_win.p, ctx->h_win.data(), (size_t)V * sizeof(uint32_t),
+                                hipMemcpyHostToDevice, ctx->stream));
+    }
+    return ARVX_OK;
+}
+
 static int views_common(Ctx *ctx, int V, const float *M, const float *campos, int W, int H,
                         int C) {
     if (V < 1 || V > 4096) return fail(ARVX_ERR_INVALID, "V=%d out of range [1,4096]", V);
@@ -686,6 +840,7 @@ static int views_common(Ctx *ctx, int V, const float *M, const float *campos, in
     return ARVX_OK;
 }
 
+static int views_tables_from_bits(Ctx *ctx);
 static int views_preprocess(Ctx *ctx, const uint8_t *d_masks, int C) {
     const int npix = ctx->W * ctx->H;
     ARVX_HIP(hipGetLastError());  // anything stale would be blamed on the launches below
@@ -708,19 +863,24 @@ static int views_preprocess(Ctx *ctx, const uint8_t *d_masks, int C) {
         }
         unsigned long long *ctr = (unsigned long long *)ctx->pool_vstrip.p;
         unsigned long long *gran = (unsigned long long *)((uint8_t *)ctx->pool_vstrip.p + off_gran);
+        // the table's tiles outside a view's window stay unwritten (view_window, above)
+        if (int rc = views_windows(ctx, true)) return rc;
+        const uint32_t *win = (const uint32_t *)ctx->pool_win.p;
         if (C == 1)
             hipLaunchKernelGGL(arvx::views_strip_kernel<1>, dim3(TIs, ctx->V), dim3(64 * (ctx->W / 64 + 1)),
                                0, ctx->stream, d_masks, ctx->W, ctx->H, TIs, ctx->bg(), ctx->bgWords,
-                               ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault);
+                               ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault, win);
         else
             hipLaunchKernelGGL(arvx::views_strip_kernel<3>, dim3(TIs, ctx->V), dim3(64 * (ctx->W / 64 + 1)),
                                0, ctx->stream, d_masks, ctx->W, ctx->H, TIs, ctx->bg(), ctx->bgWords,
-                               ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault);
+                               ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault, win);
         ARVX_HIP(hipGetLastError());
         ctx->views_ready = true;
         ctx->cameras_ready = true;
         return ARVX_OK;
     }
+    // (the three launches write whole tables: the windows on record are "everything")
+    if (int rc = views_windows(ctx, false)) return rc;
     if (C == 1 && npix % 32 == 0 && ((uintptr_t)d_masks & 15u) == 0) {
         hipLaunchKernelGGL(arvx::views_bits16_kernel, dim3((npix / 16 + 255) / 256, ctx->V),
                            dim3(256), 0, ctx->stream, d_masks, npix, ctx->bg(), ctx->bgWords);
@@ -738,6 +898,14 @@ static int views_preprocess(Ctx *ctx, const uint8_t *d_masks, int C) {
                            C, npix, ctx->bg(), ctx->bgWords);
     }
     ARVX_HIP(hipGetLastError());
+    if (int rc = views_tables_from_bits(ctx)) return rc;
+    ctx->views_ready = true;
+    ctx->cameras_ready = true;
+    return ARVX_OK;
+}
+
+// every view's whole summed-area table from its bit plane: two launches (views_kernels.h)
+static int views_tables_from_bits(Ctx *ctx) {
     const int W = ctx->W, H = ctx->H, V = ctx->V;
     // tiles of 64 table columns x 64 image rows (views_kernels.h)
     const int TJ = (W + 1 + 63) / 64, TI = (H + arvx::kTileRows - 1) / arvx::kTileRows;
@@ -751,8 +919,48 @@ static int views_preprocess(Ctx *ctx, const uint8_t *d_masks, int C) {
                        ctx->bg(), ctx->bgWords, W, H, TJ, TI, V, d_rs, d_T, d_ts, ctx->sat(),
                        ctx->satStride, ctx->satW);
     ARVX_HIP(hipGetLastError());
-    ctx->views_ready = true;
-    ctx->cameras_ready = true;
+    return ARVX_OK;
+}
+
+// Who reads the table, and why a partial one (Ctx::sat_partial) serves them: the carve kernels in
+// every variant (coarse, classify, dense classify, fused, the exact kernels' block tests -- computed
+// or from the cached rectangles, whose entries are rect_prepare's answers for the same boxes --,
+// the streaming carve) and the vote kernel read it only through rect_prepare + rect_finish /
+// classify_box / classify_block_entry, for boxes of voxels of this context's grid: inside the
+// window by view_window's argument.  The brute-force carve, the colour, photo, render and mesh
+// stages read the bit plane or no view data at all; the plane is always complete.  Whoever wants
+// the table entry by entry (arvx_selftest_view_tables) calls this first: the two launches of the
+// other mask formats write every entry from the complete bit plane -- the same absolute values --
+// and the mark goes.
+static int complete_tables(Ctx *ctx) {
+    if (!ctx->sat_partial) return ARVX_OK;
+    if (int rc = views_tables_from_bits(ctx)) return rc;
+    ctx->sat_partial = false;
+    return ARVX_OK;
+}
+
+int arvx_ctx_set_view_window(arvx_ctx *ctx, int on) {
+    ARVX_CHECK_CTX(ctx);
+    ctx->win_on = on != 0;  // (takes effect at the next arvx_set_views[_device])
+    return ARVX_OK;
+}
+
+int arvx_view_window(arvx_ctx *ctx, int view, int rect[4]) {
+    ARVX_CHECK_CTX(ctx);
+    if (!rect) return fail(ARVX_ERR_INVALID, "null rect");
+    if (!ctx->views_ready || ctx->h_win.size() != (size_t)ctx->V)
+        return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
+    if (view < 0 || view >= ctx->V) return fail(ARVX_ERR_INVALID, "view %d outside [0,%d)", view, ctx->V);
+    window_rect(ctx->h_win[view], ctx->H, ctx->satW, rect);
+    return ARVX_OK;
+}
+
+int arvx_selftest_fill_view_tables(arvx_ctx *ctx, int value) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->views_ready) return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
+    ARVX_HIP(hipMemsetAsync(ctx->sat(), value & 0xff, (size_t)ctx->V * ctx->satStride * sizeof(uint16_t),
+                            ctx->stream));
+    ctx->views_ready = false;  // (the tables are gone: the next arvx_set_views derives them)
     return ARVX_OK;
 }
 
@@ -2814,6 +3022,9 @@ int arvx_selftest_view_tables(arvx_ctx *ctx, int view, uint32_t *bg_bits, uint16
     if (view < 0 || view >= ctx->V) return fail(ARVX_ERR_INVALID, "view %d outside [0,%d)", view, ctx->V);
     if (!ld) return fail(ARVX_ERR_INVALID, "null ld");
     *ld = ctx->satW;
+    // (every entry is asked for: those outside the views' windows are written now)
+    if (table)
+        if (int rc = complete_tables(ctx)) return rc;
     const size_t words = ((size_t)ctx->W * ctx->H + 31) / 32;
     if (bg_bits)
         ARVX_HIP(hipMemcpyAsync(bg_bits, ctx->bg() + (size_t)view * ctx->bgWords, words * sizeof(uint32_t),
@@ -2822,6 +3033,17 @@ int arvx_selftest_view_tables(arvx_ctx *ctx, int view, uint32_t *bg_bits, uint16
         ARVX_HIP(hipMemcpyAsync(table, ctx->sat() + (size_t)view * ctx->satStride,
                                 (size_t)ctx->satStride * sizeof(uint16_t), hipMemcpyDeviceToHost,
                                 ctx->stream));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+int arvx_selftest_view_table_raw(arvx_ctx *ctx, int view, uint16_t *table) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->views_ready) return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
+    if (view < 0 || view >= ctx->V) return fail(ARVX_ERR_INVALID, "view %d outside [0,%d)", view, ctx->V);
+    if (!table) return fail(ARVX_ERR_INVALID, "null table");
+    ARVX_HIP(hipMemcpyAsync(table, ctx->sat() + (size_t)view * ctx->satStride,
+                            (size_t)ctx->satStride * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);
     return ARVX_OK;
 }

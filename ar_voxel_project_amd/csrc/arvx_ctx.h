@@ -212,7 +212,22 @@ struct Ctx {
     void rect_invalidate() {
         rect_state = Rect::None;
         rect_streak = 0;
+        win_valid = false;  // (the windows follow the same inputs as the cached rectangles)
     }
+    // View windows (arvx_capi.hip, view_window): per view the tiles of the summed-area table that
+    // a rectangle test of this context's grid can read, as one word I0 | I1 << 8 | J0 << 16 |
+    // J1 << 24 (strips I0..I1, tile columns J0..J1 of views_strip_kernel, inclusive).  They follow
+    // the matrices, V, W, H, the voxel size and the grid, not the masks: derived again where the
+    // cached rectangles are invalidated, sent to the device only when a word differs.
+    // sat_partial: the last derivation left entries outside some window unwritten (stale or never
+    // written); only rectangle tests of boxes of this grid may read the table while it stands
+    // (complete_tables, arvx_capi.hip, clears it).
+    bool win_on = true;      // arvx_ctx_set_view_window
+    bool win_valid = false;  // h_win is that of the current matrices and sizes
+    bool sat_partial = false;
+    std::vector<uint32_t> h_win_geo;  // the cameras' windows (while win_valid)
+    std::vector<uint32_t> h_win;      // what the device holds in pool_win: the last derivation's
+    DevPool pool_win{DevPool::Exact};
 
     // colour pass
     DevPool pool_images{DevPool::Exact};  // V x H x W x 3, BGR

@@ -335,11 +335,21 @@ __device__ __forceinline__ uint32_t nonzero16x3(const uint4 a, const uint4 b, co
 // ctr: one 64-bit ticket counter per view (zero when allocated, never reset); gran: the published
 // column counts, [view][strip][W / 2] granules; err: set when a wait gives up (never seen; the
 // host checks it at its next synchronisation).  C: channel bytes per pixel, 1 or 3.
+//
+// Round 7, the view's WINDOW.  win[v] = I0 | I1 << 8 | J0 << 16 | J1 << 24: the strips and tile
+// columns (inclusive) whose table entries a rectangle test of the context's grid can read
+// (arvx_capi.hip, view_window: it follows the cameras and the grid, not the masks).  A wave whose
+// tile lies outside writes no table entry -- it skips the staging of its rows, the row loop and
+// the zero row, and nothing else: the mask loads, the bit plane, the counts it publishes, the
+// waits, the scans and both barriers are those of every wave, so the hand-off is unchanged and the
+// entries that are written keep their absolute values.  The word is read once per workgroup, as a
+// scalar.
 template <int C>
 __global__ __launch_bounds__(64 * kStripMaxWaves) void views_strip_kernel(
     const uint8_t *__restrict__ masks, int W, int H, int TI, uint32_t *__restrict__ bg, int bgWords,
     uint16_t *__restrict__ sat, int satStride, int ld, unsigned long long *__restrict__ ctr,
-    unsigned long long *__restrict__ gran, unsigned *__restrict__ err) {
+    unsigned long long *__restrict__ gran, unsigned *__restrict__ err,
+    const uint32_t *__restrict__ win) {
     __shared__ unsigned long long s_bits[64 * (kStripMaxWaves - 1)];  // [row][pixel tile column]
     __shared__ int s_rowcnt[kStripMaxWaves][64];
     __shared__ uint16_t s_col[kStripMaxWaves][64];
@@ -477,7 +487,14 @@ __global__ __launch_bounds__(64 * kStripMaxWaves) void views_strip_kernel(
     if (lane == 63) s_tot[J] = sc;
     __syncthreads();
 
-    // ---- the table, as in views_table_kernel
+    // ---- the table, as in views_table_kernel: only the tiles inside the view's window
+    {
+        const uint32_t w = win[v];  // (blockIdx.y: a scalar load)
+        const int Ju = __builtin_amdgcn_readfirstlane(J);
+        const bool inside = I >= (int)(w & 0xffu) && I <= (int)((w >> 8) & 0xffu) &&
+                            Ju >= (int)((w >> 16) & 0xffu) && Ju <= (int)(w >> 24);
+        if (!inside) return;  // (no barrier follows)
+    }
     int left = 0, lt = 0;
     for (int k = 0; k < J; ++k) {
         left += s_rowcnt[k][lane];

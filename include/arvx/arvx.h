@@ -824,6 +824,36 @@ int arvx_ctx_set_rect_cache_limit(arvx_ctx *ctx, uint64_t bytes);
  * that differ, must come back 0 (-1: the context holds no table). */
 int arvx_selftest_rect_cache(arvx_ctx *ctx, int64_t *mismatches);
 
+/* View windows.  A rectangle test of the carve reads a view's summed-area table only inside the
+ * pixel rectangle that the whole grid projects into (plus a margin and the table's border row and
+ * column).  That rectangle follows the cameras, the image size, the voxel size and the grid -- not
+ * the masks -- so arvx_set_views[_device] writes only the part of each table inside it, rounded
+ * outwards to tiles of 64 x 64 entries, where it derives the views in one launch (one- or
+ * three-channel masks, W a multiple of 64; every other format writes whole tables).  The window is
+ * derived again when the matrices or sizes change; a view whose camera is inside or next to the grid
+ * takes its whole table.  The results of every stage are what they were; the bit planes are always
+ * complete.
+ *   arvx_ctx_set_view_window: on = 0 makes every view take its whole table from the next
+ *     arvx_set_views[_device] on (default: on).
+ *   arvx_view_window: rect = {first row, last row, first column, last column} of view `view`'s table
+ *     (rows 0 .. H, columns 0 .. W and the row's padding), inclusive, that the last derivation
+ *     wrote.
+ *   arvx_view_window_host: the same for one camera and a grid of X x Y x Z voxels, as the one-launch
+ *     derivation would choose it; host arithmetic, no device and no context. */
+int arvx_ctx_set_view_window(arvx_ctx *ctx, int on);
+int arvx_view_window(arvx_ctx *ctx, int view, int rect[4]);
+int arvx_view_window_host(int X, int Y, int Z, float voxel_size, const float M[12], int W, int H,
+                          int rect[4]);
+
+/* Self-test hooks of the view windows.  arvx_selftest_fill_view_tables sets every byte of the
+ * context's table buffer to `value` and marks the views as not derived: the next
+ * arvx_set_views[_device] must leave nothing of it where a carve looks.
+ * arvx_selftest_view_table_raw copies view `view`'s table as it stands ((H + 1) rows of the ld that
+ * arvx_selftest_view_tables reports), without writing the entries outside the window first --
+ * arvx_selftest_view_tables does write them, and returns complete tables as before. */
+int arvx_selftest_fill_view_tables(arvx_ctx *ctx, int value);
+int arvx_selftest_view_table_raw(arvx_ctx *ctx, int view, uint16_t *table);
+
 #ifdef __cplusplus
 }
 #endif
