@@ -54,6 +54,7 @@ def build_host_tests() -> str:
     build_weld_host_test()
     build_smooth_host_test()
     build_decimate_host_test()
+    build_morph_host_test()
     return os.path.join(ROOT, "tests", "cpp", "test_host")
 
 
@@ -73,6 +74,13 @@ def build_decimate_host_test() -> str:
     """g++ -> tests/cpp/test_decimate_host: arvx::decimateMesh (include/arvx/marching_cubes.hpp) on
     a welded mesh from a file, built as build_weld_host_test builds its test."""
     return _build_host_test("test_decimate_host")
+
+
+def build_morph_host_test() -> str:
+    """g++ -> tests/cpp/test_morph_host: arvx::signedDistance and arvx::morph
+    (include/arvx/postprocessing.hpp) on a Model from a file, built as build_weld_host_test builds its
+    test."""
+    return _build_host_test("test_morph_host")
 
 
 def _build_host_test(name: str) -> str:

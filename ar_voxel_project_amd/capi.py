@@ -42,6 +42,12 @@ FLOOD_FRESH = 2
 VOTES_COUNTS = 1
 VOTES_NO_CULL = 2
 COMPONENTS_LARGEST = 1
+DISTANCE_BORDER_OCCUPIED = 1
+DISTANCE_INF = 2147483647
+MORPH_ERODE = 0
+MORPH_DILATE = 1
+MORPH_OPEN = 2
+MORPH_CLOSE = 3
 DECIMATE_LATTICE = 0
 DECIMATE_SMOOTHED = 1
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
@@ -72,6 +78,7 @@ SYMBOLS = [
     "arvx_photo_carve", "arvx_carve_votes", "arvx_votes_download",
     "arvx_components", "arvx_components_download", "arvx_components_labels_download",
     "arvx_components_keep",
+    "arvx_distance", "arvx_distance_download", "arvx_morph",
     "arvx_colors_upload", "arvx_closure", "arvx_closure_count", "arvx_closure_download",
     "arvx_closure_download32",
     "arvx_mc_cells", "arvx_mc_cells_download", "arvx_mc_mesh", "arvx_mc_mesh_download",
@@ -242,6 +249,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.arvx_components_labels_download.argtypes = [p, C.c_void_p]
         lib.arvx_components_keep.argtypes = [p, C.c_int, C.c_int64, C.c_uint, C.POINTER(C.c_int64),
                                              C.POINTER(C.c_int64)]
+    if hasattr(lib, "arvx_distance"):
+        lib.arvx_distance.argtypes = [p, C.c_uint]
+        lib.arvx_distance_download.argtypes = [p, C.c_void_p]
+        lib.arvx_morph.argtypes = [p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(lib, "arvx_render"):
         lib.arvx_render.argtypes = [p, f32p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
         lib.arvx_render_view.argtypes = [p, C.c_int]
@@ -711,6 +722,25 @@ class Context:
                                                 COMPONENTS_LARGEST if largest else 0,
                                                 C.byref(kept), C.byref(removed)))
         return kept.value, removed.value
+
+    def distance(self, border_occupied: bool = False) -> np.ndarray:
+        """arvx_distance + arvx_distance_download: the signed squared Euclidean distance of every voxel
+        to the nearest voxel of the other kind, int32 in flat index order: positive on occupied voxels
+        (to the nearest empty site; the lattice points outside the grid count as empty unless
+        border_occupied), negative on empty ones, +-DISTANCE_INF where there is no such site.  The
+        state is unchanged."""
+        self._ck(self._lib.arvx_distance(self._h, DISTANCE_BORDER_OCCUPIED if border_occupied else 0))
+        out = np.empty(self.nvox, np.int32)
+        self._ck(self._lib.arvx_distance_download(self._h, out.ctypes.data))
+        return out
+
+    def morph(self, op: int, radius_sq: int) -> Tuple[int, int]:
+        """arvx_morph: erosion, dilation, opening or closing (MORPH_*) of the occupancy by the ball of
+        the offsets o with |o|^2 <= radius_sq -> (voxels removed, voxels added)."""
+        removed = C.c_int64()
+        added = C.c_int64()
+        self._ck(self._lib.arvx_morph(self._h, int(op), int(radius_sq), C.byref(removed), C.byref(added)))
+        return removed.value, added.value
 
     def surface_visible(self) -> np.ndarray:
         """arvx_surface_visible_download: views each coloured voxel is visible in (surface()'s

@@ -40,6 +40,7 @@
 #include "visibility_kernels.h"
 #include "photo_kernels.h"
 #include "components_kernels.h"
+#include "distance_kernels.h"
 #include "vote_kernels.h"
 #include "render_kernels.h"
 #include "exchange_kernels.h"
@@ -2739,6 +2740,150 @@ int arvx_components_keep(arvx_ctx *ctx, int connectivity, int64_t min_voxels, un
     if (int rc = components_run(ctx, connectivity, &rule, nullptr, &k, &r)) return rc;
     if (kept) *kept = (int64_t)k;
     if (removed) *removed = (int64_t)r;
+    return ARVX_OK;
+}
+
+// ---- signed distance field and ball morphology (distance_kernels.h) -----------------------------
+
+static int distance_refusals(const Ctx *ctx) {
+    if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
+        return fail(ARVX_ERR_STATE, "the distance field needs a whole-grid context (the nearest site may "
+                                    "lie in any plane)");
+    const long long x = ctx->X + 1ll, y = ctx->Y + 1ll, z = ctx->Z + 1ll;
+    if (x * x + y * y + z * z > (long long)ARVX_DISTANCE_INF - 1)
+        return fail(ARVX_ERR_STATE, "the squared distances of a %d x %d x %d grid do not fit 32 bits", ctx->X,
+                    ctx->Y, ctx->Z);
+    return ARVX_OK;
+}
+
+// the buffers of arvx_distance and arvx_morph; planes[k]: the k-th of the three bit planes
+static int distance_reserve(Ctx *ctx, const arvx::BitGrid &g, unsigned long long *planes[3], unsigned *grid_y,
+                            unsigned *grid_z) {
+    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
+    if (ctx->ncu <= 0) {
+        ctx->ncu = 256;
+        (void)hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
+        if (ctx->ncu <= 0) ctx->ncu = 256;
+    }
+    // a column pass: a lane per column and sign, a workgroup per 256 lanes, at most 4 per compute unit
+    // (8 are 9 % faster at 512^3 and take twice the stack memory: DESIGN.md 4.12)
+    // -- the others' lanes are taken in turn --, each with a stack region of (len + 2) * 256 entries
+    const size_t most = (size_t)std::max(ctx->ncu, 1) * 4;
+    *grid_y = (unsigned)std::min((2 * (size_t)g.X * g.Z + 255) / 256, most);
+    *grid_z = (unsigned)std::min((2 * (size_t)g.X * g.Y + 255) / 256, most);
+    const size_t stack = std::max((size_t)*grid_y * (g.Y + 2), (size_t)*grid_z * (g.Z + 2)) * 256 * sizeof(int2);
+    ARVX_HIP(ctx->pool_dist_field.reserve(ctx->nvox * sizeof(int)));
+    ARVX_HIP(ctx->pool_dist_planes.reserve(3 * nwords * sizeof(unsigned long long)));
+    ARVX_HIP(ctx->pool_dist_stack.reserve(stack));
+    ARVX_HIP(ctx->pool_dist_ctl.reserve(64));
+    for (int k = 0; k < 3; ++k) planes[k] = (unsigned long long *)ctx->pool_dist_planes.p + k * nwords;
+    return ARVX_OK;
+}
+
+// the three passes: the field of bit plane `occ` into pool_dist_field
+static int distance_run(Ctx *ctx, const arvx::BitGrid &g, const unsigned long long *occ, int border_empty,
+                        unsigned grid_y, unsigned grid_z) {
+    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
+    int *S = (int *)ctx->pool_dist_field.p;
+    int2 *stack = (int2 *)ctx->pool_dist_stack.p;
+    const size_t per_wg = 4 * (size_t)arvx::kDistWordsPerWave;
+    hipLaunchKernelGGL(arvx::dist_row_kernel, dim3((unsigned)((nwords + per_wg - 1) / per_wg)), dim3(256), 0,
+                       ctx->stream, occ, g, border_empty, S);
+    ARVX_HIP(hipGetLastError());
+    // along y: column (x, z) starts at z * X * Y + x, its values X apart
+    hipLaunchKernelGGL(arvx::dist_column_kernel, dim3(grid_y), dim3(256), 0, ctx->stream, S,
+                       (long long)g.X * g.Z, g.Y, (long long)g.X, g.X, (long long)g.X * g.Y, border_empty, stack);
+    ARVX_HIP(hipGetLastError());
+    // along z: column (x, y) starts at y * X + x, its values X * Y apart
+    hipLaunchKernelGGL(arvx::dist_column_kernel, dim3(grid_z), dim3(256), 0, ctx->stream, S,
+                       (long long)g.X * g.Y, g.Z, (long long)g.X * g.Y, g.X, (long long)g.X, border_empty, stack);
+    ARVX_HIP(hipGetLastError());
+    return ARVX_OK;
+}
+
+int arvx_distance(arvx_ctx *ctx, unsigned flags) {
+    ARVX_CHECK_CTX(ctx);
+    if (flags & ~ARVX_DISTANCE_BORDER_OCCUPIED) return fail(ARVX_ERR_INVALID, "unknown flag bits 0x%x", flags);
+    if (int rc = distance_refusals(ctx)) return rc;
+    ctx->dist_ready = false;  // (the field of an earlier call is written over)
+    const arvx::BitGrid g{ctx->X, ctx->Y, ctx->Z, (ctx->X + 63) / 64};
+    unsigned long long *planes[3];
+    unsigned gy = 0, gz = 0;
+    if (int rc = distance_reserve(ctx, g, planes, &gy, &gz)) return rc;
+    if (int rc = launch_bit_pack(ctx, g, 0, 0, planes[0], nullptr)) return rc;
+    if (int rc = distance_run(ctx, g, planes[0], !(flags & ARVX_DISTANCE_BORDER_OCCUPIED), gy, gz)) return rc;
+    ctx->dist_ready = true;
+    return ARVX_OK;
+}
+
+int arvx_distance_download(arvx_ctx *ctx, int32_t *signed_sq) {
+    ARVX_CHECK_CTX(ctx);
+    if (!signed_sq) return fail(ARVX_ERR_INVALID, "null signed_sq");
+    if (!ctx->dist_ready) return fail(ARVX_ERR_STATE, "no distance field: arvx_distance has not run on this state");
+    ARVX_HIP(hipMemcpyAsync(signed_sq, ctx->pool_dist_field.p, ctx->nvox * sizeof(int32_t), hipMemcpyDeviceToHost,
+                            ctx->stream));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+int arvx_morph(arvx_ctx *ctx, int op, int64_t radius_sq, int64_t *removed, int64_t *added) {
+    ARVX_CHECK_CTX(ctx);
+    if (op < ARVX_MORPH_ERODE || op > ARVX_MORPH_CLOSE) return fail(ARVX_ERR_INVALID, "op %d: must be 0..3", op);
+    if (radius_sq < 0 || radius_sq >= (int64_t)ARVX_DISTANCE_INF)
+        return fail(ARVX_ERR_INVALID, "radius_sq %lld: must be in [0, %d)", (long long)radius_sq, ARVX_DISTANCE_INF);
+    if (int rc = distance_refusals(ctx)) return rc;
+    if (int frc = fills_without_colours(ctx)) return frc;
+    const bool grows = op == ARVX_MORPH_DILATE || op == ARVX_MORPH_CLOSE;
+    // every record exists before a bit is cleared or set (rec_andnot_bitgrid_kernel and
+    // rec_or_bitgrid_kernel write records only): a lazy state ends here, as in arvx_components_keep
+    if (int mrc = need_rec(ctx)) return mrc;
+    const arvx::BitGrid g{ctx->X, ctx->Y, ctx->Z, (ctx->X + 63) / 64};
+    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
+    unsigned long long *planes[3];
+    unsigned gy = 0, gz = 0;
+    if (int rc = distance_reserve(ctx, g, planes, &gy, &gz)) return rc;
+    ctx->drop(grows ? Event::MorphGrow : Event::MorphShrink);
+    unsigned long long *occ = planes[0], *mid = planes[1], *change = planes[2];
+    unsigned long long *d_count = (unsigned long long *)ctx->pool_dist_ctl.p;
+    const int *S = (const int *)ctx->pool_dist_field.p;
+    const int R = (int)radius_sq;
+    const size_t per_wg = 4 * (size_t)arvx::kDistWordsPerWave;  // (words of a dist_threshold_kernel workgroup)
+    const unsigned gt = (unsigned)((nwords + per_wg - 1) / per_wg), gw = (unsigned)((nwords + 255) / 256);
+    ARVX_HIP(hipMemsetAsync(d_count, 0, sizeof *d_count, ctx->stream));
+    if (int rc = launch_bit_pack(ctx, g, 0, 0, occ, nullptr)) return rc;
+    // the field of the state; for OPEN and CLOSE the first half's set as a plane, and the field of that
+    if (int rc = distance_run(ctx, g, occ, 1, gy, gz)) return rc;
+    if (op == ARVX_MORPH_OPEN || op == ARVX_MORPH_CLOSE) {
+        hipLaunchKernelGGL(arvx::dist_threshold_kernel, dim3(gt), dim3(256), 0, ctx->stream, S, g, R, grows ? 1 : 0,
+                           0, (const unsigned long long *)occ, mid, d_count);
+        ARVX_HIP(hipGetLastError());
+        // (CLOSE: the erosion of the dilated set leaves the grid's edge alone)
+        if (int rc = distance_run(ctx, g, mid, grows ? 0 : 1, gy, gz)) return rc;
+    }
+    // what leaves (ERODE; OPEN: after the dilation of the eroded set) or joins (DILATE; CLOSE: after
+    // the erosion of the dilated set) the model, against the occupancy the call started from
+    const int second_grows = op == ARVX_MORPH_DILATE || op == ARVX_MORPH_OPEN;
+    hipLaunchKernelGGL(arvx::dist_threshold_kernel, dim3(gt), dim3(256), 0, ctx->stream, S, g, R, second_grows,
+                       grows ? 2 : 1, (const unsigned long long *)occ, change, d_count);
+    ARVX_HIP(hipGetLastError());
+    arvx::CarveParams rp;
+    carve_geometry(ctx, rp);
+    rp.rec = ctx->rec();
+    if (grows)
+        hipLaunchKernelGGL(arvx::rec_or_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, g.Z,
+                           (const unsigned long long *)change);
+    else
+        hipLaunchKernelGGL(arvx::rec_andnot_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, g.Z,
+                           (const unsigned long long *)change);
+    ARVX_HIP(hipGetLastError());
+    ctx->word(Ctx::kMorphChanged) = -1;
+    ARVX_HIP(hipMemcpyAsync(&ctx->word(Ctx::kMorphChanged), d_count, sizeof(long long), hipMemcpyDeviceToHost,
+                            ctx->stream));
+    ARVX_SYNC(ctx);
+    const long long n = ctx->word(Ctx::kMorphChanged);
+    if (n < 0) return fail(ARVX_ERR_HIP, "the morphology's kernels left no count");
+    if (removed) *removed = grows ? 0 : (int64_t)n;
+    if (added) *added = grows ? (int64_t)n : 0;
     return ARVX_OK;
 }
 

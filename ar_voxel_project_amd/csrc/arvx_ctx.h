@@ -83,6 +83,7 @@ struct Ctx {
         kCompKept, kCompRemoved,        // arvx_components_keep: components left, voxels emptied
         kRenderNeed, kRenderAgree,      // the render's large footprints; three agreement counts in a row
         kRectMiss = kRenderAgree + 3,   // a block's rectangle did not fit its table entry (rect_cache_kernels.h)
+        kMorphChanged,                  // arvx_morph: voxels that left or joined the model
         kWords
     };
     static constexpr size_t kHostBlockBytes = 192;
@@ -273,6 +274,13 @@ struct Ctx {
     int comp_conn = 0;
     long long comp_count = 0, comp_cap = 0;
 
+    // arvx_distance / arvx_morph (distance_kernels.h): the field (int32 per voxel, flat index order; read
+    // only while dist_ready is set), three bit planes (the occupancy, arvx_morph's intermediate set, the
+    // voxels it removes or adds), the column passes' envelope stacks and the change counter
+    DevPool pool_dist_field{DevPool::Exact}, pool_dist_planes{DevPool::Exact}, pool_dist_stack{DevPool::Exact},
+        pool_dist_ctl;
+    bool dist_ready = false;
+
     // closure (dilation) result: filled voxels, ascending index
     int *d_clo_index = nullptr;
     void *d_clo_rgba = nullptr;  // float4 per filled voxel
@@ -288,7 +296,8 @@ struct Ctx {
 
     // ---- what each call drops --------------------------------------------------------------
     // The rules of arvx.h ("What the context's results belong to") as one table: a row per event,
-    // named after the method of CtxModel (tests/stage_model.py) that restates it.  Every entry point
+    // named after the method of CtxModel (tests/stage_model.py) that restates it (the two Morph rows
+    // have none there: tests/test_distance_gpu.py checks what they drop).  Every entry point
     // calls drop() once, after its refusals and before its work, so that a refused call leaves the
     // context as it was.  (The closure calls it where its fills go into the state: the colour pass's
     // planes it starts from are those of the state before.)  The mesh products (mc_ready,
@@ -297,13 +306,15 @@ struct Ctx {
     // whatever replaces that state drops it (and so does the next arvx_mc_mesh_welded).
     enum class Event {
         SetViews, SetImages, Color, UploadColors, ProjectionAssoc, HandleUnseen, Closure,
-        Carve, FastCarve, UploadState, UploadPlanes, UploadHalo, Reset, PhotoCarve, ComponentsKeep
+        Carve, FastCarve, UploadState, UploadPlanes, UploadHalo, Reset, PhotoCarve, ComponentsKeep,
+        MorphShrink, MorphGrow
     };
     void drop(Event e) {
         struct Row { uint8_t colours, closure, fills, paint, cstate, state, render, votes, comps; };
         static constexpr Row kRows[] = {
             //                    colour closure closure paint cstate state   render votes  component
-            //                    list   list    fills         tiles  changes                labels
+            //                    list   list    fills         tiles  changes                labels,
+            //                                                                                   distance field
             /* SetViews        */ {1,    1,      0,      0,    0,     0,      0,      1,     0},
             /* SetImages       */ {1,    1,      0,      0,    0,     0,      0,      0,     0},
             /* Color           */ {1,    1,      0,      0,    0,     0,      0,      0,     0},
@@ -319,6 +330,8 @@ struct Ctx {
             /* Reset           */ {1,    1,      1,      1,    1,     1,      1,      1,     1},
             /* PhotoCarve      */ {1,    1,      1,      1,    0,     1,      1,      1,     1},
             /* ComponentsKeep  */ {1,    1,      1,      1,    0,     1,      1,      1,     1},
+            /* MorphShrink     */ {1,    1,      1,      1,    0,     1,      1,      1,     1},  // (ERODE, OPEN)
+            /* MorphGrow       */ {1,    1,      1,      1,    1,     1,      1,      1,     1},  // (DILATE, CLOSE)
         };
         // paint 2: the owned planes' paint is replaced; the plane stays where halo planes keep
         // theirs.  state 2: only never-seen voxels become occupied (next_state).  cstate: a call
@@ -331,7 +344,11 @@ struct Ctx {
         // component labels: the labelling of arvx_components describes the occupancy it read; every
         // call that changes the state drops it.  arvx_components_keep drops what photo carving drops,
         // for the same reasons: it only empties voxels and keeps every seen bit.
-        static_assert(sizeof kRows / sizeof kRows[0] == (size_t)Event::ComponentsKeep + 1, "a row per event");
+        // distance field: the field of arvx_distance describes the same occupancy and lives exactly as
+        // long as the labelling.  arvx_morph: an erosion or an opening only empties voxels and keeps
+        // every seen bit, so it drops what arvx_components_keep drops; a dilation or a closing occupies
+        // voxels a later carve has to look at, so it drops the settled coarse tiles as an upload does.
+        static_assert(sizeof kRows / sizeof kRows[0] == (size_t)Event::MorphGrow + 1, "a row per event");
         const Row &r = kRows[(int)e];
         if (r.colours) color_ready = color_visible = false;
         if (r.closure) closure_ready = false;
@@ -345,7 +362,7 @@ struct Ctx {
         }
         if (r.render) render_ready = false;
         if (r.votes) votes_ready = false;
-        if (r.comps) comp_ready = false;
+        if (r.comps) comp_ready = dist_ready = false;
     }
     // The state changes: whatever carries the old count as its stamp is stale -- but for
     // handleUnseen (unseen_only) the colour pass's planes of the state before stay usable: its

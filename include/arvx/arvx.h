@@ -497,6 +497,73 @@ int arvx_components_download(arvx_ctx *ctx, int32_t *label, int32_t *size);
 int arvx_components_labels_download(arvx_ctx *ctx, int32_t *voxel_label);
 int arvx_components_keep(arvx_ctx *ctx, int connectivity, int64_t min_voxels, unsigned flags,
                          int64_t *kept, int64_t *removed);
+/* ---- signed distance field and ball morphology (extension beyond the reference) ----------------
+ * The stages above decide a voxel by its views or by its connectivity; none decides it by shape.  A
+ * fin, a spur or a one-voxel bridge that is still attached survives arvx_components_keep, and the
+ * only morphology of the reference is arvx_closure, one box dilation.  The exact Euclidean distance
+ * transform answers both: once every voxel knows its squared distance to the nearest voxel of the
+ * other kind, erosion, dilation, opening and closing by a ball of any radius are one threshold each.
+ * Definition, on a whole-grid context, its current state:
+ *  - OCCUPIED is what arvx_components calls occupied (bit0 of the byte arvx_state_download would
+ *    return, a closure's fills included); lattice points are integer triples, the grid is
+ *    [0,X) x [0,Y) x [0,Z), and |i - j|^2 is the integer dx^2 + dy^2 + dz^2;
+ *  - the SIGNED SQUARED DISTANCE d(i), an int32 per voxel in flat index order x + X*(y + Y*z):
+ *      i occupied: d(i) = +min |i - j|^2 over the EMPTY sites j: the empty voxels of the grid and,
+ *        unless ARVX_DISTANCE_BORDER_OCCUPIED is set, every lattice point outside the grid (the
+ *        nearest of those is axis-aligned, so the border alone contributes
+ *        min(x+1, X-x, y+1, Y-y, z+1, Z-z)^2); d(i) >= 1;
+ *      i empty: d(i) = -min |i - j|^2 over the occupied voxels j of the grid (nothing outside the
+ *        grid is ever occupied for this purpose); d(i) <= -1;
+ *      where the minimum runs over nothing (a full grid under BORDER_OCCUPIED, an empty grid):
+ *        d(i) = +ARVX_DISTANCE_INF resp. -ARVX_DISTANCE_INF;
+ *  - the BALL of squared radius R (an integer, 0 <= R < INT32_MAX) is the offsets o with |o|^2 <= R;
+ *    with A the occupied set:
+ *      ARVX_MORPH_ERODE   A' = { i in A : d(i) > R }, the border empty;
+ *      ARVX_MORPH_DILATE  A' = A + { i not in A : -d(i) <= R }, clipped by the grid;
+ *      ARVX_MORPH_OPEN    A' = DILATE(ERODE(A)); it never adds a voxel;
+ *      ARVX_MORPH_CLOSE   B = DILATE(A), A' = { i in B : d_B(i) > R } with d_B taken under
+ *                         BORDER_OCCUPIED, so that the grid's edge does not eat the model; it never
+ *                         removes a voxel;
+ *    R = 0 leaves the occupancy as it is under every op.
+ * Everything is an integer and a minimum depends on no thread order: compared bit for bit.
+ *   arvx_distance           builds the field of the current state.  The state is unchanged, nothing
+ *                           is dropped, and the host is not synchronised.
+ *   arvx_distance_download  the X*Y*Z values; synchronises.
+ *   arvx_morph              applies the op.  A voxel that leaves A loses its occupied bit and keeps
+ *                           its seen bit; a voxel that joins A gets the occupied bit, keeps its seen
+ *                           bit as it was and carries no colour (MODEL_COLOR until a colour pass or a
+ *                           closure gives it one).  *removed / *added (either may be null) compare the
+ *                           final state with the initial one; one of them is 0 for every op.
+ * The field of arvx_distance lives exactly as long as the labelling of arvx_components: until any
+ * call that replaces the state, arvx_morph included; before a field and after such a call
+ * arvx_distance_download answers ARVX_ERR_STATE.  arvx_morph computes the fields it needs itself and
+ * leaves none behind.  It replaces the state: ERODE and OPEN only empty voxels and behave as
+ * arvx_components_keep does -- they drop what photo carving drops (paint plane included) even when
+ * nothing changes, and leave what earlier carves settled for whole coarse tiles valid --; DILATE and
+ * CLOSE occupy voxels and drop the settled coarse tiles on top of that, as a state upload does, so
+ * that a later carve looks at the new voxels.  All four end a lazy state first, refuse a state
+ * holding a closure's fills whose list is gone, and drop a components labelling, a distance field
+ * and the vote counts.
+ * Refusals (a refused call changes nothing): a slab or a striped context, or a grid with
+ * (X+1)^2 + (Y+1)^2 + (Z+1)^2 > INT32_MAX - 1, whose distances do not fit: ARVX_ERR_STATE; unknown
+ * flag bits, an op outside 0..3, radius_sq outside [0, INT32_MAX), a null signed_sq:
+ * ARVX_ERR_INVALID.
+ * arvx_morph makes one host synchronisation, for the counts.
+ * Device memory, allocated at first use and kept: 4 bytes per voxel (the field, transformed in
+ * place), three bit planes (occupancy, intermediate set, change: 3/8 byte per voxel), and the column
+ * passes' envelope stacks: 8 bytes per entry, (max(Y, Z) + 2) * 256 entries per workgroup, at most 4
+ * workgroups per compute unit and never more than two lanes per column need (1.0 GiB at 512^3 on 256
+ * compute units: the stage's largest buffer).
+ * Out of scope: slabs and multi-GPU, structuring elements other than the ball, anisotropic voxels. */
+#define ARVX_DISTANCE_BORDER_OCCUPIED 1u /* lattice points outside the grid are no empty sites */
+#define ARVX_DISTANCE_INF 2147483647
+#define ARVX_MORPH_ERODE 0
+#define ARVX_MORPH_DILATE 1
+#define ARVX_MORPH_OPEN 2
+#define ARVX_MORPH_CLOSE 3
+int arvx_distance(arvx_ctx *ctx, unsigned flags);
+int arvx_distance_download(arvx_ctx *ctx, int32_t *signed_sq);
+int arvx_morph(arvx_ctx *ctx, int op, int64_t radius_sq, int64_t *removed, int64_t *added);
 /* The per-voxel colour lists behind the vote -- what the reference's voxel_pass appends with
  * Model::addColor (src/ColorReconstruction.h:44-60, src/Model.h:142-149) and getColors returns:
  * for each of n voxels (flat index over the context's own planes, any order) V samples in view
@@ -548,8 +615,11 @@ int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const flo
  *     settled for whole coarse tiles stays valid, since it only empties voxels;
  *   - arvx_components_keep drops exactly what arvx_photo_carve drops, for the same reason;
  *   - the labelling of arvx_components lives until the next call that replaces the state: carve,
- *     vote carve, fast carve, photo carve, arvx_handle_unseen, closure, state upload, reset or
- *     arvx_components_keep.
+ *     vote carve, fast carve, photo carve, arvx_handle_unseen, closure, state upload, reset,
+ *     arvx_components_keep or arvx_morph; the field of arvx_distance lives exactly as long;
+ *   - arvx_morph with ERODE or OPEN drops exactly what arvx_components_keep drops; with DILATE or
+ *     CLOSE it also drops what earlier carves settled for whole coarse tiles, as a state upload
+ *     does, because it occupies voxels.
  * A closure that filled voxels leaves them occupied in the state.  Once its list is gone the
  * context no longer has their colours, which the reference's Model keeps: until a carve, fast
  * carve, upload or reset replaces the state, the calls that return colours (arvx_export_model,

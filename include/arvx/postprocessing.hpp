@@ -14,6 +14,10 @@
 #ifndef ARVX_POSTPROCESSING_HPP
 #define ARVX_POSTPROCESSING_HPP
 
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
 #include "arvx/voxel_carving.hpp"
 
 namespace arvx {
@@ -88,6 +92,46 @@ inline int64_t dropFloaters(Model &model, int64_t min_voxels = 1, bool largest_o
     std::cout << "LOG - PP: floaters dropped (" << kept << " components kept, " << removed << " voxels removed)."
               << std::endl;
     return removed;
+}
+
+// Extension beyond the reference: erosion, dilation, opening or closing (ARVX_MORPH_*) of the model
+// by a ball of radius_voxels voxels (arvx_morph with radius_sq = floor(radius_voxels^2)), next to
+// dropFloaters: an opening removes what is thinner than the ball -- fins, spurs, one-voxel bridges --
+// and what it cuts loose, dropFloaters drops.  Voxels that leave the model keep their seen bits;
+// voxels that join it carry no colour until a colour pass gives them one.  Runs on the model's own
+// device context with the same hand-over as dropFloaters.  Returns the voxels removed plus added.
+inline int64_t morph(Model &model, int op, float radius_voxels) {
+    static const char *const kNames[] = {"erosion", "dilation", "opening", "closing"};
+    if (op < ARVX_MORPH_ERODE || op > ARVX_MORPH_CLOSE) throw Error(ARVX_ERR_INVALID, "morph: op must be 0..3");
+    if (!(radius_voxels >= 0.f)) throw Error(ARVX_ERR_INVALID, "morph: radius_voxels must be >= 0");
+    const double r2 = std::floor((double)radius_voxels * (double)radius_voxels);
+    if (r2 >= (double)ARVX_DISTANCE_INF) throw Error(ARVX_ERR_INVALID, "morph: radius_voxels too large");
+    const int64_t radius_sq = (int64_t)r2;
+    std::cout << "LOG - PP: starting " << kNames[op] << " (squared radius " << radius_sq << ")." << std::endl;
+    detail::timing(kStagePostProcessing, true);
+    arvx_ctx *ctx = model.device();
+    int64_t removed = 0, added = 0;
+    detail::check(arvx_morph(ctx, op, radius_sq, &removed, &added), "arvx_morph");
+    model.device_changed();
+    detail::timing(kStagePostProcessing, false);
+    std::cout << "LOG - PP: " << kNames[op] << " completed (" << removed << " voxels removed, " << added
+              << " voxels added)." << std::endl;
+    return removed + added;
+}
+
+// Extension beyond the reference: the signed squared Euclidean distance of every voxel of the model
+// to the nearest voxel of the other kind (arvx_distance; definition in arvx/arvx.h), flat index order
+// x + X*(y + Y*z): positive on occupied voxels, negative on empty ones, +-ARVX_DISTANCE_INF where
+// there is no such voxel.  border_occupied: the lattice points outside the grid are no empty sites.
+// The model is unchanged.
+inline std::vector<int32_t> signedDistance(Model &model, bool border_occupied = false) {
+    arvx_ctx *ctx = model.device();
+    int64_t n = 0;
+    detail::check(arvx_ctx_voxels(ctx, &n), "arvx_ctx_voxels");
+    std::vector<int32_t> out((size_t)n);
+    detail::check(arvx_distance(ctx, border_occupied ? ARVX_DISTANCE_BORDER_OCCUPIED : 0u), "arvx_distance");
+    detail::check(arvx_distance_download(ctx, out.data()), "arvx_distance_download");
+    return out;
 }
 
 }  // namespace arvx

@@ -228,7 +228,8 @@ int main(int argc, char *argv[]) {
         {"dy", "0.0"}, {"dz", "0.0"}, {"model_debug", "false"}, {"postprocessing", "true"},
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
-        {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"}};
+        {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"},
+        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -251,6 +252,10 @@ int main(int argc, char *argv[]) {
                      "  -floaters=N (after carving: empty every connected component of fewer than N\n"
                      "    voxels, 6-connectivity; 0, the default: off),\n"
                      "  -largest=true (after carving: keep only the largest connected component),\n"
+                     "  -erode=R | -dilate=R | -open=R | -close=R (after carving and -photo, before\n"
+                     "    -floaters / -largest: erosion, dilation, opening or closing of the model by a\n"
+                     "    ball of radius R voxels, R >= 0 a float; at most one of them; an opening removes\n"
+                     "    what is thinner than the ball, and -largest=true then drops what it cut loose),\n"
                      "  -render=DIR (after the mesh: the welded model drawn over every input image,\n"
                      "    DIR/renderNNNN.ppm, and its agreement with every mask)\n";
         return 0;
@@ -277,6 +282,20 @@ int main(int argc, char *argv[]) {
         }
         if (parser.i("floaters") < 0) {
             std::cerr << "Invalid floaters argument.";
+            return 1;
+        }
+        int morphs = 0;
+        for (const char *name : {"erode", "dilate", "open", "close"}) {
+            if (parser.str(name).empty()) continue;
+            ++morphs;
+            const float r = parser.f(name);
+            if (!(r >= 0.f) || !(r < 46341.f)) {
+                std::cerr << "Invalid " << name << " argument.";
+                return 1;
+            }
+        }
+        if (morphs > 1) {
+            std::cerr << "At most one of -erode, -dilate, -open and -close may be given.";
             return 1;
         }
     }
@@ -410,6 +429,13 @@ int main(int argc, char *argv[]) {
         if (parser.f("photo") > 0.f)
             arvx::photoCarve(in.intr, model, in.views, parser.f("photo"), parser.i("photoViews"),
                              parser.f("visibleTol"), parser.i("photoIters"));
+        // -erode=R, -dilate=R, -open=R, -close=R (an extension beyond the reference): ball morphology of
+        // the carved model, before the components so that what an opening cuts loose can be dropped
+        {
+            const char *const names[] = {"erode", "dilate", "open", "close"};  // (ARVX_MORPH_* order)
+            for (int op = 0; op < 4; ++op)
+                if (!parser.str(names[op]).empty()) arvx::morph(model, op, parser.f(names[op]));
+        }
         // -floaters=N, -largest=true (an extension beyond the reference): the model's connected
         // components -- the clumps that false foreground specks leave in mid-air go before they are coloured
         if (parser.i("floaters") > 0 || parser.b("largest"))
