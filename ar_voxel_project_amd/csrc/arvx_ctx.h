@@ -296,14 +296,19 @@ struct Ctx {
 
     // ---- what each call drops --------------------------------------------------------------
     // The rules of arvx.h ("What the context's results belong to") as one table: a row per event,
-    // named after the method of CtxModel (tests/stage_model.py) that restates it (the two Morph rows
-    // have none there: tests/test_distance_gpu.py checks what they drop).  Every entry point
-    // calls drop() once, after its refusals and before its work, so that a refused call leaves the
-    // context as it was.  (The closure calls it where its fills go into the state: the colour pass's
-    // planes it starts from are those of the state before.)  The mesh products (mc_ready,
-    // weld_ready, smooth_*, dec_ready) are not here: each lives until the next call of its own stage.  The
-    // render of the welded mesh (arvx_render) is: it shows the state the mesh was built from, so
-    // whatever replaces that state drops it (and so does the next arvx_mc_mesh_welded).
+    // restated by a method of CtxModel (tests/stage_model.py), from arvx.h and not from this table:
+    // SetViews set_views, SetImages set_images, Color color, UploadColors upload_colors, HandleUnseen
+    // handle_unseen, Closure closure, Carve carve and carve_votes, FastCarve fast_carve, UploadState
+    // upload_state, UploadPlanes upload_planes, Reset reset, PhotoCarve photo_carve, ComponentsKeep
+    // keep_components, MorphShrink and MorphGrow morph (by its op).  ProjectionAssoc, UploadHalo and the
+    // render column have no restatement there.  tests/test_stage_sequences_gpu.py replays orders of
+    // those calls against it.  Every entry point calls drop() once, after its refusals and before its
+    // work, so that a refused call leaves the context as it was.  (The closure calls it where its fills
+    // go into the state: the colour pass's planes it starts from are those of the state before.)  The
+    // mesh products (mc_ready, weld_ready, smooth_*, dec_ready) are not here: each lives until the next
+    // call of its own stage.  The render of the welded mesh (arvx_render) is: it shows the state the
+    // mesh was built from, so whatever replaces that state drops it (and so does the next
+    // arvx_mc_mesh_welded).
     enum class Event {
         SetViews, SetImages, Color, UploadColors, ProjectionAssoc, HandleUnseen, Closure,
         Carve, FastCarve, UploadState, UploadPlanes, UploadHalo, Reset, PhotoCarve, ComponentsKeep,

@@ -37,8 +37,8 @@ def statistic(Ms, s, xs, ys, zs, images, tol, assoc_left=True):
 
 def inconsistent(n, D, max_std, min_views):
     """Step 4, in fp64."""
-    lim = (F64(F32(max_std)) * F64(F32(max_std))) * (n.astype(F64) * n.astype(F64))
-    with np.errstate(invalid="ignore"):
+    with np.errstate(invalid="ignore"):  # (inf * 0 where max_std is +inf and no view sees the voxel)
+        lim = (F64(F32(max_std)) * F64(F32(max_std))) * (n.astype(F64) * n.astype(F64))
         return (n >= min_views) & (D.astype(F64) > lim)
 
 

@@ -8,10 +8,19 @@ own Model (src/Model.{h,cpp}): RGBA per voxel plus the seen bits, on which carve
 passes, handleUnseen and applyClosure act as in src/VoxelCarving.cpp, src/ColorReconstruction.h
 and src/Postprocessing3d.cpp.  replay() runs a recorded list of operations on a CtxModel and on
 something with the same methods (the device context's driver in tests/test_stage_sequences_gpu.py),
-so that any failing sequence can be pinned as a plain list."""
+so that any failing sequence can be pinned as a plain list.
+
+The stages beyond the reference's pipeline are restated too, each from its section of arvx.h and
+"What the context's results belong to" there, on top of the numpy restatements the stages' own tests
+use: the vote carve (tests/vote_carve.py) and its counts, photo-consistency carving
+(tests/photo_carve.py), the components' labelling and arvx_components_keep (tests/components.py), the
+distance field and arvx_morph (tests/distance.py).  The vote counts, the labelling and the field are
+results of the context like the colour and closure lists: CtxModel holds them for as long as arvx.h
+says they live, and their downloads are refused before and after.  Not restated: arvx_render*, the
+smoothed and decimated meshes, arvx_color_visible and arvx_ctx_set_projection_assoc."""
 import numpy as np
 
-from tests import mesh_weld, occ_codec
+from tests import components, distance, mesh_weld, occ_codec, photo_carve, vote_carve
 
 OCC, SEEN, PAINT = 1, 2, 4
 MODEL_COLOR = np.array([50, 168, 141, 1], np.float32)
@@ -146,6 +155,9 @@ class CtxModel:
         self.colors = None     # (index, rgb) of the voxels the colour list colours
         self.clo = None        # (index, rgba, apply_unseen) of the closure's list
         self.fills = False     # the state holds an earlier closure's fills
+        self.counts = None     # (background, inside) of a vote carve that kept its counts
+        self.comp = None       # per-voxel labels of the last components()
+        self.field = None      # [occupancy bytes, border_occupied, the field once somebody asked] of distance()
 
     def resolve(self, name, args):
         """Concrete arguments of an operation recorded with a seed: ("upload_state", seed),
@@ -165,18 +177,32 @@ class CtxModel:
         return args
 
     # ---- calls ----------------------------------------------------------------------------
+    def _state_results_gone(self):
+        """The vote counts, the labelling and the field describe the state they were taken from:
+        every call that replaces it ends them (arvx.h: arvx_carve_votes, arvx_components,
+        arvx_distance)."""
+        self.counts = None
+        self.comp = None
+        self.field = None
+
     def _state_changes(self, keep_paint=False):
         self.colors = None
         self.clo = None
         self.fills = False
         if not keep_paint:
             self.paint = None
+        self._state_results_gone()
+
+    def _fills_ok(self):
+        if self.fills and self.clo is None:
+            raise Refused("the closure's fills have lost their colours")
 
     def set_views(self, lo, hi):
         self.views = (lo, hi)
         self.images = False
         self.colors = None
         self.clo = None
+        self.counts = None  # (they are sums over the views)
 
     def set_images(self):
         if self.views is None:
@@ -206,6 +232,62 @@ class CtxModel:
         self._state_changes()
         self.st = st.reshape(-1)
 
+    def carve_votes(self, max_misses, counts):
+        """arvx_carve_votes(max_misses, ARVX_VOTES_COUNTS iff counts): a carve as far as the other
+        results go."""
+        if self.views is None:
+            raise Refused("carve_votes before set_views")
+        sc, v = self.sc, self._v()
+        st, votes = vote_carve.carve_votes(sc.oracle, sc.X, sc.Y, sc.Z, sc.s, sc.M[v], sc.masks[v],
+                                           max_misses, state=self.st & 3)
+        self._state_changes()
+        self.st = st.reshape(-1)
+        if counts:
+            self.counts = (votes.background, votes.inside)
+
+    def photo_carve(self, max_std, min_views, tol_voxels, max_iterations):
+        """arvx_photo_carve with a tolerance of tol_voxels voxel edges (0 and inf are allowed)
+        -> (iterations, removed)."""
+        if self.views is None or not self.images:
+            raise Refused("photo_carve without views / images")
+        self._fills_ok()
+        sc, v = self.sc, self._v()
+        ph = photo_carve.photo_carve(sc.X, sc.Y, sc.Z, sc.s, sc.M[v], sc.images[v], self.st & 3, max_std,
+                                     min_views, np.float32(tol_voxels) * sc.s, max_iterations)
+        self._state_changes()  # (even when nothing was removed)
+        self.st = ph.state
+        return ph.iterations, ph.removed
+
+    def components(self, connectivity):
+        """arvx_components -> the number of components; the labelling stays for the two downloads."""
+        sc = self.sc
+        self.comp = components.labels(self.st, (sc.X, sc.Y, sc.Z), connectivity)
+        return len(components.table(self.comp)[0])
+
+    def keep_components(self, connectivity, min_voxels, largest):
+        """arvx_components_keep -> (components kept, voxels removed)."""
+        self._fills_ok()
+        sc = self.sc
+        st, kept, removed = components.keep(self.st & 3, (sc.X, sc.Y, sc.Z), connectivity, min_voxels,
+                                            bool(largest))
+        self._state_changes()  # (the labelling of an earlier components() with it: none is left)
+        self.st = st
+        return kept, removed
+
+    def distance(self, border_occupied):
+        """arvx_distance.  (The field itself is worked out when distance_field asks for it: until
+        then no call can have changed the occupancy without dropping it.)"""
+        self.field = [(self.st & OCC).copy(), bool(border_occupied), None]
+
+    def morph(self, op, radius_sq):
+        """arvx_morph -> (removed, added)."""
+        self._fills_ok()
+        sc = self.sc
+        st, removed, added = distance.morph(self.st & 3, (sc.X, sc.Y, sc.Z), op, radius_sq)
+        self._state_changes()  # (even for a radius of 0; no field is left)
+        self.st = st
+        return removed, added
+
     def color(self, mode):
         if self.views is None or not self.images:
             raise Refused("color without views / images")
@@ -226,6 +308,7 @@ class CtxModel:
     def handle_unseen(self):
         self.st = self.st | ((self.st & SEEN) == 0).astype(np.uint8)
         self.clo = None
+        self._state_results_gone()
 
     def painted(self, apply_unseen):
         p = np.zeros(self.N, bool) if self.paint is None else self.paint.copy()
@@ -258,6 +341,8 @@ class CtxModel:
         self.st[idx] |= OCC
         self.clo = (idx, after[idx].copy(), bool(apply_unseen))
         self.fills = len(idx) > 0
+        # arvx.h names the closure among the calls that end the three results, whatever it fills
+        self._state_results_gone()
 
     def upload_state(self, state):
         state = np.asarray(state, np.uint8).reshape(-1)
@@ -289,8 +374,7 @@ class CtxModel:
         return flat_words64(self.st & OCC), flat_words64(self.st & SEEN)
 
     def _flag_ok(self, apply_unseen):
-        if self.fills and self.clo is None:
-            raise Refused("the closure's fills have lost their colours")
+        self._fills_ok()
         if self.clo is not None and bool(apply_unseen) != self.clo[2]:
             raise Refused("closure computed with the other apply_unseen")
 
@@ -307,6 +391,30 @@ class CtxModel:
         if self.clo is None:
             raise Refused("no closure result")
         return self.clo[0], self.clo[1]
+
+    def votes(self):
+        if self.counts is None:
+            raise Refused("no vote counts")
+        return self.counts
+
+    def component_table(self):
+        if self.comp is None:
+            raise Refused("no labelling")
+        return components.table(self.comp)
+
+    def component_labels(self):
+        if self.comp is None:
+            raise Refused("no labelling")
+        return self.comp
+
+    def distance_field(self):
+        """arvx_distance_download alone: the field of the last distance()."""
+        if self.field is None:
+            raise Refused("no distance field")
+        sc = self.sc
+        if self.field[2] is None:
+            self.field[2] = distance.signed_sq(self.field[0], (sc.X, sc.Y, sc.Z), self.field[1])
+        return self.field[2]
 
     def mc_cells(self):
         sc = self.sc
@@ -387,8 +495,10 @@ class HostModel:
 def replay(model, target, ops, check):
     """Run `ops` -- tuples (name, *args) -- on `model` (a CtxModel) and `target` (the same
     methods on the device).  A call the model refuses must be refused by the target (it raises
-    Refused too) and the other way round; observations ("obs", name, *args) are compared by
-    check(name, want, got, step).  Returns the number of steps run."""
+    Refused too) and the other way round; where the model's call returns something (the counts of
+    photo_carve, components, keep_components and morph) the target's call returns the same;
+    observations ("obs", name, *args) are compared by check(name, want, got, step).  Returns the
+    number of steps run."""
     for step, op in enumerate(ops):
         name, args = op[0], op[1:]
         if name == "obs":
@@ -407,15 +517,18 @@ def replay(model, target, ops, check):
                 check(oname, want[1], got[1], step)
             continue
         args = model.resolve(name, args)
+        want_ret = got_ret = None
         try:
-            getattr(model, name)(*args)
+            want_ret = getattr(model, name)(*args)
             want = "ok"
         except Refused:
             want = "refused"
         try:
-            getattr(target, name)(*args)
+            got_ret = getattr(target, name)(*args)
             got = "ok"
         except Refused:
             got = "refused"
         assert want == got, (step, name, f"model: {want}", f"device: {got}")
+        if want == "ok" and want_ret is not None:
+            assert got_ret == want_ret, (step, name, f"model returns {want_ret}", f"device returns {got_ret}")
     return len(ops)

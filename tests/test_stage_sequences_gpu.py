@@ -5,7 +5,17 @@ The device keeps caches between calls -- the lazy coarse-tile codes, the colour 
 the state packets, the colour / closure lists, the paint plane, the carve's tile summaries -- and a
 fixed carve -> colour -> handleUnseen -> closure chain on a fresh context never asks whether they
 are still valid for the next call.  Random sequences do, and the pinned ones keep the cases that
-once went wrong (or were found by reading the code) from coming back."""
+once went wrong (or were found by reading the code) from coming back.
+
+A second generator and a second set of pinned sequences (random_stage_ops, STAGE_PINNED) mix the
+stages beyond the reference's pipeline into those orders: the vote carve, photo-consistency carving,
+arvx_components_keep and the four ops of arvx_morph replace the state by hand-written need_rec / drop
+code of their own, and the vote counts, the components' labelling and the distance field are three
+more results whose lifetime the context has to get right.  The counts the state-changing calls
+return are compared as well.  tests/test_stage_model_cpu.py checks, without a GPU, that the generator
+gives every new stage something to do and that the old generator's sequences are what they were."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -27,6 +37,7 @@ class Device:
         self.arvx, self.sc = arvx, sc
         self.ctx = arvx.Context(sc.X, sc.Y, sc.Z, sc.s, lib_path=lib_path)
         self.views = None
+        self.ncomp = 0  # components of the last components()
 
     def close(self):
         self.ctx.close()
@@ -45,7 +56,13 @@ class Device:
         self.views = (lo, hi)
 
     def set_images(self):
-        lo, hi = self.views if self.views else (0, NV)
+        if self.views is None:
+            # (capi's set_images checks the images against the views' sizes, which it does not have
+            # yet: the library is asked itself, and answers before it looks at an image)
+            ctx, im = self.ctx, self.sc.images
+            ptrs = (ctypes.c_void_p * len(im))(*[im[i].ctypes.data for i in range(len(im))])
+            return self._call(lambda: ctx._ck(ctx._lib.arvx_set_images(ctx._h, ptrs, im.shape[2] * 3)))
+        lo, hi = self.views
         self._call(self.ctx.set_images, self.sc.images[lo:hi])
 
     def carve(self, first=0, count=None):
@@ -106,6 +123,51 @@ class Device:
     def mc_mesh_welded(self, apply_unseen):
         return self._call(self.ctx.mc_mesh_welded, bool(apply_unseen))
 
+    # ---- the stages beyond the reference's pipeline ----
+    def carve_votes(self, max_misses, counts):
+        self._call(self.ctx.carve_votes, max_misses, bool(counts))
+
+    def photo_carve(self, max_std, min_views, tol_voxels, max_iterations):
+        tol = float(np.float32(tol_voxels) * self.sc.s)
+        return self._call(self.ctx.photo_carve, max_std, min_views, tol, max_iterations)
+
+    def components(self, connectivity):
+        labels, _ = self._call(self.ctx.components, connectivity)
+        self.ncomp = len(labels)
+        return self.ncomp
+
+    def keep_components(self, connectivity, min_voxels, largest):
+        return self._call(self.ctx.keep_components, min_voxels, bool(largest), connectivity)
+
+    def distance(self, border_occupied):
+        """arvx_distance alone: distance_field downloads."""
+        flags = self.arvx.DISTANCE_BORDER_OCCUPIED if border_occupied else 0
+        self._call(lambda: self.ctx._ck(self.ctx._lib.arvx_distance(self.ctx._h, flags)))
+
+    def morph(self, op, radius_sq):
+        return self._call(self.ctx.morph, op, radius_sq)
+
+    def votes(self):
+        return self._call(self.ctx.votes)
+
+    def component_table(self):
+        """arvx_components_download alone, no relabelling: the table of the last components() (a
+        table has at most a label per voxel: room for that, whatever the library hands out)."""
+        ctx = self.ctx
+        lab, size = np.full(ctx.nvox, -1, np.int32), np.full(ctx.nvox, -1, np.int32)
+        self._call(lambda: ctx._ck(ctx._lib.arvx_components_download(ctx._h, lab.ctypes.data, size.ctypes.data)))
+        return lab[:self.ncomp], size[:self.ncomp]
+
+    def component_labels(self):
+        return self._call(self.ctx.component_labels)
+
+    def distance_field(self):
+        """arvx_distance_download alone, no rebuild."""
+        ctx = self.ctx
+        out = np.empty(ctx.nvox, np.int32)
+        self._call(lambda: ctx._ck(ctx._lib.arvx_distance_download(ctx._h, out.ctypes.data)))
+        return out
+
 
 def packet_grid(X, Y):
     return X % 32 == 0 and (X * Y) % 64 == 0
@@ -150,6 +212,132 @@ def random_ops(seed, X, Y):
             ops.append((k,))
     ops.append(("obs", "export_model", int(rng.integers(0, 2))))
     ops.append(("obs", "download_state"))
+    return ops
+
+
+# ---- sequences over the stages beyond the reference's pipeline ---------------------------------
+
+STAGE_OBS = ["votes", "component_table", "component_labels", "distance_field"]
+STAGE_GRIDS = GRIDS
+ERODE, DILATE, OPEN, CLOSE = 0, 1, 2, 3
+INF = float("inf")
+
+
+def random_stage_ops(seed, X, Y):
+    """The kinds of random_ops at reduced weight, plus the vote carve, photo carving, the components,
+    the distance field and the morphology, their arguments from the edges of their ranges.  A sequence
+    opens with something that leaves the later stages material (two of the grids carve down to
+    next to nothing under all views).  A stage that leaves a result is often asked for it, at once or
+    after one of the calls that must keep it (keeper), so that a result is also seen to survive them.
+    On the 128 x 64 x 64 grid a sequence gets two photo sweeps in all: a photo carve drawn there is cut
+    to what is left of them, and once none is left it TURNS INTO A KEEP (so max_iterations 4 does not
+    occur on that grid in the random set; the pinned sequences ask for it there)."""
+    rng = np.random.default_rng(7000 + seed)
+    pick = lambda values: values[int(rng.integers(len(values)))]
+
+    def votes():
+        return ("carve_votes", pick([0, 1, 2, NV, 65535]), int(rng.random() < 0.6))
+
+    # The restatement of a photo sweep over the surface of an uploaded noise state is the one slow step
+    # on the host, 0.15 s on the 128 x 64 x 64 grid: the budget keeps a case within three times the
+    # slowest of test_random_sequence.
+    sweeps_left = 2 if X * Y >= 8192 else 1 << 30
+
+    def photo():
+        nonlocal sweeps_left
+        max_iterations = min(pick([1, 2, 4]), sweeps_left)
+        if max_iterations == 0:
+            return keep()
+        sweeps_left -= max_iterations
+        return ("photo_carve", pick([0.0, 20.0, 60.0, INF]), int(rng.integers(1, 4)), pick([0.0, 1.0, 2.0, INF]),
+                max_iterations)
+
+    def keep():
+        return ("keep_components", pick([6, 26]), pick([1, 2, 10, 100]), int(rng.random() < 0.4))
+
+    def morph():
+        return ("morph", pick([ERODE, DILATE, OPEN, CLOSE]), pick([0, 1, 2, 3, 9]))
+
+    def keeper(result):
+        """A call that keeps `result` ("votes", "labelling" or "field"), per arvx.h."""
+        calls = [("set_images",), ("color", int(rng.integers(0, 2))), ("upload_colors", int(rng.integers(0, 1 << 30)))]
+        if result != "votes":
+            calls.append(("set_views", 1, NV))
+        if result != "labelling":
+            calls.append(("components", pick([6, 26])))
+        if result != "field":
+            calls.append(("distance", int(rng.integers(0, 2))))
+        return pick(calls)
+
+    def ask(result, names, p):
+        """With probability p an observation of `result`, half of the time behind a keeper."""
+        if rng.random() < p:
+            if rng.random() < 0.5:
+                ops.append(keeper(result))
+            ops.append(("obs", pick(names)))
+
+    ops = []
+    if rng.random() < 0.95:
+        ops.append(("set_views", 0, NV))
+        if rng.random() < 0.9:
+            ops.append(("set_images",))
+    opening = rng.random()
+    if opening < 0.3:
+        ops.append(("carve",))
+    elif opening < 0.65:
+        ops.append(("upload_state", int(rng.integers(0, 1 << 30))))
+    elif opening < 0.85:
+        ops.append(("carve_votes", pick([1, 2]), int(rng.random() < 0.6)))
+    kinds = ["carve", "carve_views", "fast_carve", "set_views", "set_images", "color", "upload_colors",
+             "handle_unseen", "closure", "upload_state", "upload_planes", "reset", "obs",
+             "carve_votes", "photo_carve", "components", "keep_components", "distance", "morph", "stage_obs"]
+    p = np.array([5, 2, 1, 3, 3, 5, 2, 6, 7, 5, 2, 1, 5,
+                  8, 7, 6, 8, 5, 12, 10], float)
+    obs = [o for o in OBS if o != "download_packets" or packet_grid(X, Y)]
+    for _ in range(int(rng.integers(7, 13))):
+        k = kinds[rng.choice(len(kinds), p=p / p.sum())]
+        if k == "carve_views":
+            f = int(rng.integers(0, 3))
+            ops.append(("carve", f, int(rng.integers(1, 4 - f))))
+        elif k == "set_views":
+            lo = int(rng.integers(0, 3))
+            ops.append(("set_views", lo, int(rng.integers(lo + 3, NV + 1))))
+        elif k == "color":
+            ops.append(("color", int(rng.integers(0, 2))))
+        elif k == "closure":
+            ops.append(("closure", pick([1, 3, 3, 5]), int(rng.integers(0, 2))))
+            if rng.random() < 0.3:  # (the fills lose their list: photo carve, keep and morph are refused)
+                ops.append(pick([("handle_unseen",), ("set_images",), ("color", 0)]))
+        elif k == "upload_state":
+            ops.append((k, int(rng.integers(0, 1 << 30)), int(rng.random() < 0.3)))
+        elif k in ("upload_planes", "upload_colors"):
+            ops.append((k, int(rng.integers(0, 1 << 30))))
+        elif k == "obs":
+            o = pick(obs)
+            ops.append(("obs", o, int(rng.integers(0, 2))) if o in ("export_model", "mc_mesh", "mc_mesh_welded")
+                       else ("obs", o))
+        elif k == "carve_votes":
+            ops.append(votes())
+            if ops[-1][2]:
+                ask("votes", ["votes"], 0.6)
+        elif k == "photo_carve":
+            ops.append(photo())
+        elif k == "components":
+            ops.append(("components", pick([6, 26])))
+            ask("labelling", ["component_table", "component_labels"], 0.5)
+        elif k == "keep_components":
+            ops.append(keep())
+        elif k == "distance":
+            ops.append(("distance", int(rng.integers(0, 2))))
+            ask("field", ["distance_field"], 0.5)
+        elif k == "morph":
+            ops.append(morph())
+        elif k == "stage_obs":
+            ops.append(("obs", pick(STAGE_OBS)))
+        else:
+            ops.append((k,))
+    ops.append(("obs", "download_state"))
+    ops.append(("obs", "export_model", int(rng.integers(0, 2))))
     return ops
 
 
@@ -199,6 +387,15 @@ def test_random_sequence(arvx, scenes_by_grid, grid, seed):
     run(arvx, sc, random_ops(seed, grid[0], grid[1]), f"seed {seed} grid {grid}")
 
 
+STAGE_SEEDS = [(STAGE_GRIDS[i % len(STAGE_GRIDS)], i) for i in range(48)]
+
+
+@pytest.mark.parametrize("grid,seed", STAGE_SEEDS, ids=[f"{g[0]}x{g[1]}x{g[2]}-s{s}" for g, s in STAGE_SEEDS])
+def test_random_stage_sequence(arvx, scenes_by_grid, grid, seed):
+    sc = scenes_by_grid[grid]
+    run(arvx, sc, random_stage_ops(seed, grid[0], grid[1]), f"stage seed {seed} grid {grid}")
+
+
 # ---- pinned sequences ----------------------------------------------------------------------
 
 PINNED = {
@@ -245,3 +442,124 @@ PINNED = {
 @pytest.mark.parametrize("grid", [GRIDS[0], GRIDS[1]], ids=["lazy", "packets"])
 def test_pinned_sequence(arvx, scenes_by_grid, name, grid):
     run(arvx, scenes_by_grid[grid], PINNED[name], f"pinned {name} grid {grid}")
+
+
+# ---- pinned sequences over the stages beyond the reference's pipeline -------------------------
+
+VIEWS = [("set_views", 0, NV), ("set_images",)]
+STATE3 = [("obs", "component_table"), ("obs", "component_labels"), ("obs", "distance_field")]
+
+
+def _on_lazy_state(stage):
+    """A carve of a fresh model leaves most coarse tiles as their code only; the stage has to end that
+    lazy state (every form the state downloads in shows it), and the carve under other views that
+    follows must neither trust a tile the stage changed nor miss the voxels it added."""
+    return [("set_views", 0, 4), ("set_images",), ("carve",), stage, ("obs", "download_state"),
+            ("obs", "download_planes"), ("obs", "download_packets"), ("obs", "mc_cells"),
+            ("set_views", 2, NV), ("carve",), ("obs", "download_state")]
+
+
+# Every view but 2 and 3 sees the whole grid, so after most carves handleUnseen has nothing to
+# occupy.  View 2 alone leaves a quarter of the grid never seen (and carves nothing there); an erosion
+# then empties part of it, and that part is what handleUnseen brings back.
+UNSEEN_EMPTY = VIEWS + [("carve", 2, 1), ("morph", ERODE, 9)]
+
+
+def _photo_after_unseen(max_std, max_iterations):
+    """The colour pass's planes, handed on by handleUnseen (planes_unseen), meet the photo loop's own
+    plane rebuild; the closure then starts from whatever planes are left."""
+    return UNSEEN_EMPTY + [("color", 1), ("handle_unseen",), ("photo_carve", max_std, 3, 1.0, max_iterations),
+                           ("obs", "download_state"), ("closure", 3, 0), ("obs", "closure_list"),
+                           ("obs", "export_model", 0), ("obs", "mc_cells")]
+
+
+STAGE_PINNED = {
+    # (a vote carve under the views of the carve before it can empty nothing: it runs under six others,
+    # two of them new, and the last carve runs under all eight)
+    "lazy_votes": [("set_views", 0, 4), ("set_images",), ("carve",), ("set_views", 2, NV), ("carve_votes", 1, 1),
+                   ("obs", "votes"), ("obs", "download_state"), ("obs", "download_planes"),
+                   ("obs", "download_packets"), ("obs", "mc_cells"), ("set_views", 0, NV), ("carve",),
+                   ("obs", "download_state")],
+    "lazy_photo": _on_lazy_state(("photo_carve", 20.0, 2, 1.0, 2)),
+    "lazy_keep": _on_lazy_state(("keep_components", 6, 10, 0)),
+    "lazy_erode": _on_lazy_state(("morph", ERODE, 2)),
+    "lazy_dilate": _on_lazy_state(("morph", DILATE, 3)),  # (the second carve looks at the new voxels)
+    "lazy_open": _on_lazy_state(("morph", OPEN, 1)),
+    "lazy_close": _on_lazy_state(("morph", CLOSE, 9)),    # (as for DILATE)
+    # a closure's fills whose list handleUnseen dropped: the three stages that would have to know the
+    # fills' colours are refused and change nothing; after a carve each is accepted
+    "fills_without_list": VIEWS + [("carve", 0, 3), ("closure", 3, 0), ("handle_unseen",),
+                                   ("photo_carve", 20.0, 1, 1.0, 1), ("keep_components", 6, 2, 0),
+                                   ("morph", DILATE, 1), ("morph", ERODE, 1), ("obs", "download_state"),
+                                   ("carve", 0, 3), ("photo_carve", 20.0, 1, 1.0, 1), ("keep_components", 6, 2, 0),
+                                   ("morph", DILATE, 1), ("obs", "download_state"), ("obs", "export_model", 0)],
+    # ... while the list is there a keep is accepted; it drops the list and the mark of the fills, which
+    # are plain occupancy from then on: a second closure is defined again
+    "fills_with_list_keep": VIEWS + [("carve", 0, 3), ("color", 0), ("closure", 3, 0), ("keep_components", 26, 2, 0),
+                                     ("obs", "closure_list"), ("obs", "surface"), ("closure", 3, 0),
+                                     ("obs", "closure_list"), ("obs", "export_model", 0)],
+    # ... also where the closure ran on the lazy state and wrote out only the coarse tiles it filled into:
+    # the keep / the dilation then writes out the rest, and must leave the filled tiles as they are
+    "lazy_closure_keep_closure": VIEWS + [("carve",), ("closure", 3, 0), ("keep_components", 6, 100, 0),
+                                          ("obs", "download_state"), ("closure", 3, 0), ("obs", "closure_list"),
+                                          ("obs", "export_model", 0), ("obs", "mc_cells")],
+    "lazy_closure_dilate": VIEWS + [("carve",), ("closure", 3, 1), ("morph", DILATE, 1), ("obs", "download_state"),
+                                    ("obs", "download_planes"), ("obs", "export_model", 1)],
+    # the labelling and the field read a lazy state as it is (they change nothing, so they do not end it),
+    # before and after handleUnseen on it
+    "lazy_components_distance": VIEWS + [("carve",), ("components", 6)] + STATE3[:2] + [
+        ("distance", 0), ("obs", "distance_field"), ("handle_unseen",), ("components", 26), ("distance", 1)]
+        + STATE3 + [("obs", "download_state")],
+    # the paint plane (bit2, on empty voxels too) goes with a vote carve, a keep and a morph that change no
+    # voxel: no bit2 in the bytes, no UNSEEN_COLOR in the model
+    "paint_dropped_without_a_change": [("set_views", 0, NV), ("upload_state", 11, 1), ("carve_votes", 65535, 0),
+                                       ("obs", "download_state"), ("obs", "export_model", 0),
+                                       ("upload_state", 12, 1), ("keep_components", 6, 1, 0),
+                                       ("obs", "download_state"), ("obs", "export_model", 0),
+                                       ("upload_state", 13, 1), ("morph", ERODE, 0),
+                                       ("obs", "download_state"), ("obs", "export_model", 0),
+                                       ("upload_state", 14, 1), ("morph", CLOSE, 0),
+                                       ("obs", "download_state"), ("obs", "export_model", 0)],
+    # the vote counts: kept by what replaces neither the state nor the views ...
+    "votes_lifetime": VIEWS + [("carve_votes", 1, 1), ("obs", "votes"), ("set_images",), ("color", 1),
+                               ("upload_colors", 5), ("components", 6), ("distance", 0), ("obs", "votes"),
+                               # ... dropped by new views, handleUnseen, the closure, a vote carve without counts
+                               ("set_views", 0, NV), ("obs", "votes"),
+                               ("carve_votes", 1, 1), ("handle_unseen",), ("obs", "votes"),
+                               ("carve_votes", 2, 1), ("obs", "votes"), ("closure", 3, 0), ("obs", "votes"),
+                               ("carve_votes", 2, 1), ("obs", "votes"), ("carve_votes", 2, 0), ("obs", "votes")],
+    # the labelling and the field: kept by the colour calls, new images, new views and each other's
+    # build ...
+    # build (the field a labelling built after it, the labelling a field built after it): all three
+    # downloads after every one of those calls, before anything is built again ...
+    "labelling_field_lifetime": VIEWS + [("carve", 0, 3), ("distance", 1), ("components", 26)] + STATE3 + [
+        ("color", 0)] + STATE3 + [("upload_colors", 6)] + STATE3 + [("set_images",)] + STATE3 + [
+        ("set_views", 1, NV)] + STATE3 + [("distance", 0)] + STATE3 + [("components", 6)] + STATE3 + [
+        # ... dropped by handleUnseen and by the closure.  arvx.h: "the labelling of arvx_components
+        # lives until the next call that replaces the state: carve, vote carve, fast carve, photo carve,
+        # arvx_handle_unseen, closure, state upload, reset, ..." -- the list names the call, not what
+        # it fills: a closure of kernel size 1, which fills nothing, drops both as well
+        ("handle_unseen",)] + STATE3 + [
+        ("components", 6), ("distance", 0), ("closure", 1, 0), ("obs", "closure_list")] + STATE3 + [
+        ("carve", 0, 2), ("components", 6), ("distance", 0), ("closure", 3, 0)] + STATE3 + [
+        # a keep leaves no labelling (not even its own), a morph no field
+        ("components", 26), ("keep_components", 26, 1, 0), ("obs", "component_table"),
+        ("obs", "component_labels"), ("distance", 0), ("morph", OPEN, 0), ("obs", "distance_field")],
+    # what handleUnseen occupies and what a closure fills is occupied for the components, the field
+    # and the keep
+    "unseen_components_distance_keep": UNSEEN_EMPTY + [("handle_unseen",), ("components", 6)] + STATE3[:2] + [
+        ("distance", 0), ("obs", "distance_field"), ("keep_components", 6, 10, 1), ("obs", "download_state"),
+        ("obs", "mc_cells")],
+    "closure_components_distance": VIEWS + [("carve",), ("color", 1), ("closure", 3, 1), ("components", 26)]
+                                   + STATE3[:2] + [("distance", 0), ("obs", "distance_field"),
+                                                   ("obs", "export_model", 1)],
+    # max_iterations 1 stops while voxels are still being removed, 4 stops on an empty sweep
+    "color_unseen_photo_closure_1": _photo_after_unseen(60.0, 1),
+    "color_unseen_photo_closure_4": _photo_after_unseen(140.0, 4),
+}
+
+
+@pytest.mark.parametrize("name", sorted(STAGE_PINNED))
+@pytest.mark.parametrize("grid", [GRIDS[0], GRIDS[1]], ids=["lazy", "packets"])
+def test_pinned_stage_sequence(arvx, scenes_by_grid, name, grid):
+    run(arvx, scenes_by_grid[grid], STAGE_PINNED[name], f"pinned {name} grid {grid}")
