@@ -81,6 +81,40 @@ using Form = Ctx::Form;
         ARVX_HIP(hipSetDevice((ctx)->device));                       \
     } while (0)
 
+#define ARVX_TRY(expr)                                    \
+    do {                                                  \
+        if (int arvx_rc_ = (expr)) return arvx_rc_;       \
+    } while (0)
+
+// ---- launches ---------------------------------------------------------------------------
+// Every kernel of this file goes out through launch(): on the context's stream as it stands at the
+// call (ExchangeStreamScope swaps that member), checked straight after the launch, a failure
+// reported with the line of the stage that launched.  The arguments convert to the kernel's own
+// parameter types, so a call casts only what does not convert by itself (a void pointer).
+struct LaunchSite {  // the context and, through the default argument, the line of the call
+    const Ctx *ctx;
+    int line;
+    LaunchSite(const Ctx *c, int l = __builtin_LINE()) : ctx(c), line(l) {}
+};
+struct Lds {  // bytes of dynamic LDS of a launch
+    size_t bytes;
+};
+template <class... P>
+[[nodiscard]] static int launch(LaunchSite at, void (*kernel)(P...), dim3 grid, dim3 block, Lds lds,
+                                std::common_type_t<P>... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds.bytes, at.ctx->stream, args...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? ARVX_OK : arvx::fail_hip(e, "kernel launch", __FILE__, at.line);
+}
+template <class... P>
+[[nodiscard]] static int launch(LaunchSite at, void (*kernel)(P...), dim3 grid, dim3 block,
+                                std::common_type_t<P>... args) {
+    return launch(at, kernel, grid, block, Lds{0}, args...);
+}
+
+// workgroups of `per` for n entries
+static unsigned blocks_for(size_t n, size_t per = 256) { return (unsigned)((n + per - 1) / per); }
+
 // The entry points of the occupancy hand-off (pack / compress / expand) launch on the
 // context's exchange stream when the caller has set one: everything they launch inside goes
 // there, and the caller orders the two streams with events.
@@ -168,11 +202,32 @@ static int check_fault(Ctx *ctx) {
     } while (0)
 
 static int need_rec(Ctx *ctx, bool lazy_ok = false);
-static void carve_geometry(const Ctx *ctx, arvx::CarveParams &p);
+static arvx::CarveParams record_params(const Ctx *ctx);
 
 // the paint plane where it takes part (null: nobody is painted)
 static const unsigned long long *paint_plane(const Ctx *ctx) {
     return ctx->paint_valid ? (const unsigned long long *)ctx->pool_paint.p : nullptr;
+}
+
+// one context holds every plane of the grid: what the stages with global connectivity ask for
+static bool whole_grid(const Ctx *ctx) { return ctx->stripe_world <= 1 && ctx->z0 == 0 && ctx->z1 == ctx->Z; }
+
+// the bit planes (bitplane_kernels.h) of `planes` planes of the grid (default: the owned ones), and
+// their words
+static arvx::BitGrid bit_grid(const Ctx *ctx, int planes) {
+    return arvx::BitGrid{ctx->X, ctx->Y, planes, (ctx->X + 63) / 64};
+}
+static arvx::BitGrid bit_grid(const Ctx *ctx) { return bit_grid(ctx, ctx->z1 - ctx->z0); }
+static size_t bit_words(const arvx::BitGrid &g) { return (size_t)g.XW * g.Y * g.Z; }
+
+// compute units of the context's device (cached)
+static int compute_units(Ctx *ctx) {
+    if (ctx->ncu <= 0) {
+        ctx->ncu = 256;
+        (void)hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
+        if (ctx->ncu <= 0) ctx->ncu = 256;
+    }
+    return ctx->ncu;
 }
 
 // The context's planes ze0 .. ze0 + g.Z - 1 as bit planes (bitplane_kernels.h) from the
@@ -181,27 +236,16 @@ static const unsigned long long *paint_plane(const Ctx *ctx) {
 static int launch_bit_pack(Ctx *ctx, const arvx::BitGrid &g, int closure_occupied, int apply_unseen,
                            unsigned long long *occ, unsigned long long *unseen) {
     if (int rc = need_rec(ctx, true)) return rc;  // (bitgrid_from_rec_kernel reads lazy tiles)
-    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
-    arvx::CarveParams p;
-    carve_geometry(ctx, p);
-    p.rec = ctx->rec();
-    hipLaunchKernelGGL(arvx::bitgrid_from_rec_kernel, dim3((unsigned)((nwords + 255) / 256)),
-                       dim3(256), 0, ctx->stream, p, 0, g.Z, closure_occupied, apply_unseen,
-                       closure_occupied ? paint_plane(ctx) : nullptr, occ, unseen);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::bitgrid_from_rec_kernel, blocks_for(bit_words(g)), 256, record_params(ctx), 0, g.Z,
+                  closure_occupied, apply_unseen, closure_occupied ? paint_plane(ctx) : nullptr, occ, unseen);
 }
 
 // counts the set bits per block and scans the counts; *total = number of set bits
 static int bit_compact_count(Ctx *ctx, const unsigned long long *bits, size_t nwords, int *d_cnt,
                              long long *d_off, long long *total) {
     const int nblk = (int)((nwords + arvx::kBitBlock - 1) / arvx::kBitBlock);
-    hipLaunchKernelGGL(arvx::bit_count_kernel, dim3(nblk), dim3(256), 0, ctx->stream, bits, nwords,
-                       d_cnt);
-    ARVX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(arvx::surface_scan_kernel, dim3(1), dim3(256), 0, ctx->stream, d_cnt, nblk,
-                       d_off);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::bit_count_kernel, nblk, 256, bits, nwords, d_cnt));
+    ARVX_TRY(launch(ctx, arvx::surface_scan_kernel, 1, 256, d_cnt, nblk, d_off));
     ARVX_HIP(hipMemcpyAsync(total, d_off + nblk, sizeof *total, hipMemcpyDeviceToHost,
                             ctx->stream));
     ARVX_SYNC(ctx);
@@ -253,17 +297,14 @@ static int scan_counts(Ctx *ctx, const int *counts, const int4 *cells, long long
         const int8_t *table = nullptr;  // (the triangle counts of Bourke's table, on the device)
         ARVX_HIP(hipGetSymbolAddress((void **)&table, HIP_SYMBOL(arvx::kMcTri)));
         table += offsetof(arvx::McTriTable, n);
-        hipLaunchKernelGGL(arvx::scan_lookback_kernel<true>, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream,
-                           (const int *)cells, table, n, n_dev, d_offsets, tickets,
-                           (unsigned)ctx->compact_tickets, status, ctx->compact_epoch, d_total,
-                           ctx->word_dev(w), ctx->d_fault);
+        ARVX_TRY(launch(ctx, arvx::scan_lookback_kernel<true>, (unsigned)nchunks, 256, (const int *)cells, table,
+                        n, n_dev, d_offsets, tickets, (unsigned)ctx->compact_tickets, status,
+                        ctx->compact_epoch, d_total, ctx->word_dev(w), ctx->d_fault));
     } else {
-        hipLaunchKernelGGL(arvx::scan_lookback_kernel<false>, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream,
-                           counts, (const int8_t *)nullptr, n, (const long long *)nullptr, d_offsets,
-                           tickets, (unsigned)ctx->compact_tickets, status, ctx->compact_epoch,
-                           d_total, ctx->word_dev(w), ctx->d_fault);
+        ARVX_TRY(launch(ctx, arvx::scan_lookback_kernel<false>, (unsigned)nchunks, 256, counts, nullptr, n,
+                        nullptr, d_offsets, tickets, (unsigned)ctx->compact_tickets, status,
+                        ctx->compact_epoch, d_total, ctx->word_dev(w), ctx->d_fault));
     }
-    ARVX_HIP(hipGetLastError());
     ctx->compact_tickets += nchunks;
     if (d_total_out) *d_total_out = d_total;
     return ARVX_OK;
@@ -284,10 +325,8 @@ static int bit_compact(Ctx *ctx, const unsigned long long *bits, size_t nwords, 
     // the next producer on the way
     int *cur = (int *)ctx->pool_chunk_counts.p + (size_t)ctx->counts_cur * ctx->counts_stride;
     int *other = (int *)ctx->pool_chunk_counts.p + (size_t)(ctx->counts_cur ^ 1) * ctx->counts_stride;
-    hipLaunchKernelGGL(arvx::bit_compact_counted_kernel, dim3((unsigned)nchunks), dim3(256), 0, ctx->stream,
-                       bits, nwords, g, (const int *)cur, other, cap, d_index, d_words, d_total,
-                       ctx->word_dev(w));
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::bit_compact_counted_kernel, (unsigned)nchunks, 256, bits, nwords, g, cur,
+                    other, cap, d_index, d_words, d_total, ctx->word_dev(w)));
     ctx->counts_clean[ctx->counts_cur ^ 1] = true;
     if (d_total_out) *d_total_out = d_total;
     return ARVX_OK;
@@ -355,14 +394,14 @@ struct NoSettle {
     int operator()() const { return ARVX_OK; }
 };
 
-// The protocol: launch() reserves and enqueues everything at the lists' capacities; ONE
+// The protocol: enqueue() reserves and launches everything at the lists' capacities; ONE
 // synchronisation; every list's length is read; settle() reads what else the kernels left; lists
 // that outgrew their room get an eighth more than they need and the call's launches run once more.
 // Never a third time: the second attempt had room for all.
-template <size_t N, class Launch, class Settle = NoSettle>
-static int run_lists(Ctx *ctx, ListRoom (&lists)[N], Launch launch, Settle settle = {}) {
+template <size_t N, class Enqueue, class Settle = NoSettle>
+static int run_lists(Ctx *ctx, ListRoom (&lists)[N], Enqueue enqueue, Settle settle = {}) {
     for (int attempt = 0;; ++attempt) {
-        if (int rc = launch()) return rc;
+        if (int rc = enqueue()) return rc;
         ARVX_SYNC(ctx);
         bool fits = true, counted = true;
         for (ListRoom &l : lists) {
@@ -386,35 +425,30 @@ static int room_for_missing_cells(const ListRoom &cells, ListRoom &tris) {
 }
 
 // f(std::true_type) or f(std::false_type) by the context's grouping: the kernels take it as a
-// template argument, `kernel<decltype(left)::value>`
+// template argument, `kernel<decltype(left)::value>`; f's return value (that of its launch) comes back
 template <class F>
-static void by_assoc(const Ctx *ctx, F f) {
-    if (ctx->assoc == ARVX_ASSOC_LEFT) f(std::true_type{});
-    else f(std::false_type{});
+[[nodiscard]] static int by_assoc(const Ctx *ctx, F f) {
+    return ctx->assoc == ARVX_ASSOC_LEFT ? f(std::true_type{}) : f(std::false_type{});
 }
 
 static int bit_compact_write(Ctx *ctx, const unsigned long long *bits, size_t nwords,
                              const arvx::BitGrid &g, const long long *d_off, int *d_index,
                              arvx::SparseWord *d_words) {
     const int nblk = (int)((nwords + arvx::kBitBlock - 1) / arvx::kBitBlock);
-    hipLaunchKernelGGL(arvx::bit_write_kernel, dim3(nblk), dim3(256), 0, ctx->stream, bits, nwords,
-                       g, d_off, d_index, d_words);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::bit_write_kernel, nblk, 256, bits, nwords, g, d_off, d_index, d_words);
 }
 
 // xyz -> device, kernel, results back: the two projection self-tests share this frame
-template <class Launch>
+template <class Enqueue>
 static int selftest_xyz(Ctx *ctx, int64_t n, const int32_t *xyz, size_t out_floats, float *out,
-                        Launch launch) {
+                        Enqueue enqueue) {
     if (n < 1 || !xyz || !out) return fail(ARVX_ERR_INVALID, "bad argument");
     const size_t in_bytes = (size_t)n * 3 * sizeof(int32_t);
     ARVX_HIP(ctx->pool_scratch.reserve(in_bytes + out_floats * sizeof(float) + 64));
     int *d_xyz = (int *)ctx->pool_scratch.p;
     float *d_out = (float *)((uint8_t *)ctx->pool_scratch.p + ((in_bytes + 15) & ~(size_t)15));
     ARVX_HIP(hipMemcpyAsync(d_xyz, xyz, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    launch(d_xyz, d_out);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(enqueue(d_xyz, d_out));
     ARVX_HIP(hipMemcpyAsync(out, d_out, out_floats * sizeof(float), hipMemcpyDeviceToHost,
                             ctx->stream));
     ARVX_SYNC(ctx);
@@ -867,15 +901,9 @@ static int views_preprocess(Ctx *ctx, const uint8_t *d_masks, int C) {
         // the table's tiles outside a view's window stay unwritten (view_window, above)
         if (int rc = views_windows(ctx, true)) return rc;
         const uint32_t *win = (const uint32_t *)ctx->pool_win.p;
-        if (C == 1)
-            hipLaunchKernelGGL(arvx::views_strip_kernel<1>, dim3(TIs, ctx->V), dim3(64 * (ctx->W / 64 + 1)),
-                               0, ctx->stream, d_masks, ctx->W, ctx->H, TIs, ctx->bg(), ctx->bgWords,
-                               ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault, win);
-        else
-            hipLaunchKernelGGL(arvx::views_strip_kernel<3>, dim3(TIs, ctx->V), dim3(64 * (ctx->W / 64 + 1)),
-                               0, ctx->stream, d_masks, ctx->W, ctx->H, TIs, ctx->bg(), ctx->bgWords,
-                               ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault, win);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, C == 1 ? arvx::views_strip_kernel<1> : arvx::views_strip_kernel<3>,
+                        dim3(TIs, ctx->V), 64 * (ctx->W / 64 + 1), d_masks, ctx->W, ctx->H, TIs, ctx->bg(),
+                        ctx->bgWords, ctx->sat(), ctx->satStride, ctx->satW, ctr, gran, ctx->d_fault, win));
         ctx->views_ready = true;
         ctx->cameras_ready = true;
         return ARVX_OK;
@@ -883,22 +911,17 @@ static int views_preprocess(Ctx *ctx, const uint8_t *d_masks, int C) {
     // (the three launches write whole tables: the windows on record are "everything")
     if (int rc = views_windows(ctx, false)) return rc;
     if (C == 1 && npix % 32 == 0 && ((uintptr_t)d_masks & 15u) == 0) {
-        hipLaunchKernelGGL(arvx::views_bits16_kernel, dim3((npix / 16 + 255) / 256, ctx->V),
-                           dim3(256), 0, ctx->stream, d_masks, npix, ctx->bg(), ctx->bgWords);
+        ARVX_TRY(launch(ctx, arvx::views_bits16_kernel, dim3((npix / 16 + 255) / 256, ctx->V), 256, d_masks,
+                        npix, ctx->bg(), ctx->bgWords));
     } else if (C == 1 || C == 3) {
         const dim3 g1(((npix + 3) / 4 + 255) / 256, ctx->V);
-        if (C == 1)
-            hipLaunchKernelGGL(arvx::views_bits_kernel<1>, g1, dim3(256), 0, ctx->stream, d_masks,
-                               npix, ctx->bg(), ctx->bgWords);
-        else
-            hipLaunchKernelGGL(arvx::views_bits_kernel<3>, g1, dim3(256), 0, ctx->stream, d_masks,
-                               npix, ctx->bg(), ctx->bgWords);
+        ARVX_TRY(launch(ctx, C == 1 ? arvx::views_bits_kernel<1> : arvx::views_bits_kernel<3>, g1, 256, d_masks,
+                        npix, ctx->bg(), ctx->bgWords));
     } else {
         const dim3 g1((npix + 255) / 256, ctx->V);
-        hipLaunchKernelGGL(arvx::views_bits_generic_kernel, g1, dim3(256), 0, ctx->stream, d_masks,
-                           C, npix, ctx->bg(), ctx->bgWords);
+        ARVX_TRY(launch(ctx, arvx::views_bits_generic_kernel, g1, 256, d_masks, C, npix, ctx->bg(),
+                        ctx->bgWords));
     }
-    ARVX_HIP(hipGetLastError());
     if (int rc = views_tables_from_bits(ctx)) return rc;
     ctx->views_ready = true;
     ctx->cameras_ready = true;
@@ -914,13 +937,10 @@ static int views_tables_from_bits(Ctx *ctx) {
     ARVX_HIP(ctx->pool_scratch.reserve((n_rs + n_T + n_ts) * sizeof(int) + 64));
     int *d_rs = (int *)ctx->pool_scratch.p, *d_T = d_rs + n_rs, *d_ts = d_T + n_T;
     const unsigned tgrid = (unsigned)(((size_t)TJ * TI * V + 3) / 4);
-    hipLaunchKernelGGL(arvx::views_tile_sums_kernel, dim3(tgrid), dim3(256), 0, ctx->stream,
-                       ctx->bg(), ctx->bgWords, W, H, TJ, TI, V, d_rs, d_T, d_ts);
-    hipLaunchKernelGGL(arvx::views_table_kernel, dim3(tgrid), dim3(256), 0, ctx->stream,
-                       ctx->bg(), ctx->bgWords, W, H, TJ, TI, V, d_rs, d_T, d_ts, ctx->sat(),
-                       ctx->satStride, ctx->satW);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    ARVX_TRY(launch(ctx, arvx::views_tile_sums_kernel, tgrid, 256, ctx->bg(), ctx->bgWords, W, H, TJ, TI, V,
+                    d_rs, d_T, d_ts));
+    return launch(ctx, arvx::views_table_kernel, tgrid, 256, ctx->bg(), ctx->bgWords, W, H, TJ, TI, V, d_rs,
+                  d_T, d_ts, ctx->sat(), ctx->satStride, ctx->satW);
 }
 
 // Who reads the table, and why a partial one (Ctx::sat_partial) serves them: the carve kernels in
@@ -1045,10 +1065,8 @@ int arvx_undistort_device(arvx_ctx *ctx, int V, const void *dev_src, int W, int 
         return fail(ARVX_ERR_INVALID, "bad argument (src and dst must differ)");
     arvx::UndistortParams p;
     if (int rc = undistort_params(K, dist, ndist, W, H, C, p)) return rc;
-    hipLaunchKernelGGL(arvx::undistort_kernel, dim3((W + 63) / 64, (H + 3) / 4, V), dim3(256), 0,
-                       ctx->stream, (const uint8_t *)dev_src, (uint8_t *)dev_dst, p);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::undistort_kernel, dim3((W + 63) / 64, (H + 3) / 4, V), 256,
+                  (const uint8_t *)dev_src, (uint8_t *)dev_dst, p);
 }
 
 int arvx_undistort(arvx_ctx *ctx, int V, const uint8_t *const *src, int W, int H, int C,
@@ -1067,9 +1085,7 @@ int arvx_undistort(arvx_ctx *ctx, int V, const uint8_t *const *src, int W, int H
     for (int i = 0; i < V; ++i)
         ARVX_HIP(hipMemcpy2DAsync(d_src + img * i, rowb, src[i], stride, rowb, H,
                                   hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(arvx::undistort_kernel, dim3((W + 63) / 64, (H + 3) / 4, V), dim3(256), 0,
-                       ctx->stream, d_src, d_dst, p);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::undistort_kernel, dim3((W + 63) / 64, (H + 3) / 4, V), 256, d_src, d_dst, p));
     for (int i = 0; i < V; ++i)
         ARVX_HIP(hipMemcpy2DAsync(dst[i], stride, d_dst + img * i, rowb, rowb, H,
                                   hipMemcpyDeviceToHost, ctx->stream));
@@ -1100,6 +1116,13 @@ static void carve_geometry(const Ctx *ctx, arvx::CarveParams &p) {
     p.coarseZ = (p.Z + (8 << p.czShift) - 1) / (8 << p.czShift);
     p.ccode = ctx->form == Form::Lazy ? (const uint8_t *)ctx->pool_ccode.p : nullptr;
 }
+// that geometry over the context's own records: what the stages' kernels take
+static arvx::CarveParams record_params(const Ctx *ctx) {
+    arvx::CarveParams p;
+    carve_geometry(ctx, p);
+    p.rec = ctx->rec();
+    return p;
+}
 // the views' matrices and tables (arvx_set_views) as the carve kernels see them
 static void carve_views(const Ctx *ctx, arvx::CarveParams &p) {
     p.M = ctx->M();
@@ -1112,6 +1135,13 @@ static void carve_views(const Ctx *ctx, arvx::CarveParams &p) {
     p.satW = ctx->satW;
 }
 
+// A bit plane over the context's first nz planes (bitplane_kernels.h) put onto the records (grow) or
+// taken off them.  Both kernels write records only: the caller has ended a lazy state first.
+static int records_apply(Ctx *ctx, const unsigned long long *plane, int nz, bool grow) {
+    return launch(ctx, grow ? arvx::rec_or_bitgrid_kernel : arvx::rec_andnot_bitgrid_kernel,
+                  blocks_for(bit_words(bit_grid(ctx, nz))), 256, record_params(ctx), 0, nz, plane);
+}
+
 // a record buffer for this context's grid, every record "finished" when it is new
 static int ensure_records(Ctx *ctx, arvx::DevPool &buf) {
     arvx::CarveParams g;
@@ -1119,10 +1149,7 @@ static int ensure_records(Ctx *ctx, arvx::DevPool &buf) {
     const size_t need = arvx::rec_count(g) * arvx::kRecU16 * sizeof(uint16_t);
     if (buf.cap >= need) return ARVX_OK;
     ARVX_HIP(buf.reserve(need));
-    hipLaunchKernelGGL(arvx::rec_init_kernel, dim3(2048), dim3(256), 0, ctx->stream,
-                       (uint32_t *)buf.p, need / 4);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::rec_init_kernel, 2048, 256, (uint32_t *)buf.p, need / 4);
 }
 
 // The state as records: what every stage works on.  lazy_ok: the caller's kernels read the
@@ -1131,9 +1158,7 @@ static int ensure_records(Ctx *ctx, arvx::DevPool &buf) {
 static int need_rec(Ctx *ctx, bool lazy_ok) {
     if (int rc = ensure_records(ctx, ctx->pool_rec)) return rc;
     if (ctx->form == Form::Records || (ctx->form == Form::Lazy && lazy_ok)) return ARVX_OK;
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
+    arvx::CarveParams g = record_params(ctx);
     if (ctx->form == Form::Lazy) {
         g.ccode = nullptr;
         g.coarseCarved = (uint8_t *)ctx->pool_ccode.p;
@@ -1141,10 +1166,8 @@ static int need_rec(Ctx *ctx, bool lazy_ok) {
     } else {
         g.flags = 4u | 16u;  // a fresh model: all occupied, none seen
     }
-    hipLaunchKernelGGL(arvx::carve_fill_kernel,
-                       dim3((unsigned)((size_t)g.coarseX * g.coarseY * g.coarseZ)), dim3(256), 0,
-                       ctx->stream, g);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::carve_fill_kernel, (unsigned)((size_t)g.coarseX * g.coarseY * g.coarseZ), 256,
+                    g));
     ctx->form = Form::Records;
     return ARVX_OK;
 }
@@ -1163,20 +1186,16 @@ static int fills_without_colours(Ctx *ctx) {
 // (+ bit2 into the paint plane).  Ends with a host synchronisation.
 static int bytes_into_records(Ctx *ctx, int zl0, int nz) {
     if (int rc = need_rec(ctx)) return rc;
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
+    arvx::CarveParams g = record_params(ctx);
     const size_t pw = (size_t)((ctx->X + 63) / 64) * ctx->Y * (size_t)(ctx->ze1 - ctx->ze0);
     const bool had = ctx->pool_paint.cap >= pw * 8 && ctx->paint_valid;
     ARVX_HIP(ctx->pool_paint.reserve(pw * 8));
     if (!had) ARVX_HIP(hipMemsetAsync(ctx->pool_paint.p, 0, pw * 8, ctx->stream));
     int *d_any = (int *)(ctx->stats() + 8);
     ARVX_HIP(hipMemsetAsync(d_any, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(arvx::rec_from_bytes_kernel,
-                       dim3((unsigned)((size_t)g.tilesX * g.tilesY * g.tilesZ)), dim3(256), 0,
-                       ctx->stream, g, (const uint8_t *)ctx->pool_state_bytes.p, zl0, nz,
-                       (unsigned long long *)ctx->pool_paint.p, d_any);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::rec_from_bytes_kernel, (unsigned)((size_t)g.tilesX * g.tilesY * g.tilesZ), 256,
+                    g, (const uint8_t *)ctx->pool_state_bytes.p, zl0, nz,
+                    (unsigned long long *)ctx->pool_paint.p, d_any));
     int any = 0;
     ARVX_HIP(hipMemcpyAsync(&any, d_any, sizeof any, hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);  // (also: the host bytes may go away)
@@ -1188,14 +1207,9 @@ static int bytes_into_records(Ctx *ctx, int zl0, int nz) {
 static int records_into_bytes(Ctx *ctx, int zl0, int nz) {
     if (int rc = need_rec(ctx, true)) return rc;  // (rec_to_bytes_kernel reads lazy tiles)
     ARVX_HIP(ctx->pool_state_bytes.reserve(ctx->nvox_ext));
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
-    hipLaunchKernelGGL(arvx::rec_to_bytes_kernel,
-                       dim3((unsigned)((size_t)g.tilesX * g.tilesY * g.tilesZ)), dim3(256), 0,
-                       ctx->stream, g, (uint8_t *)ctx->pool_state_bytes.p, zl0, nz, paint_plane(ctx));
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    arvx::CarveParams g = record_params(ctx);
+    return launch(ctx, arvx::rec_to_bytes_kernel, (unsigned)((size_t)g.tilesX * g.tilesY * g.tilesZ), 256,
+                  g, (uint8_t *)ctx->pool_state_bytes.p, zl0, nz, paint_plane(ctx));
 }
 
 int arvx_state_reset(arvx_ctx *ctx) {
@@ -1253,12 +1267,9 @@ int arvx_state_upload_planes(arvx_ctx *ctx, const uint32_t *occ, const uint32_t 
     uint32_t *d_occ = (uint32_t *)ctx->pool_scratch.p, *d_seen = d_occ + nwords;
     ARVX_HIP(hipMemcpyAsync(d_occ, occ, nwords * 4, hipMemcpyHostToDevice, ctx->stream));
     ARVX_HIP(hipMemcpyAsync(d_seen, seen, nwords * 4, hipMemcpyHostToDevice, ctx->stream));
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
-    hipLaunchKernelGGL(arvx::rec_from_planes_kernel, dim3((unsigned)((nwords + 255) / 256)),
-                       dim3(256), 0, ctx->stream, g, ctx->z0 - ctx->ze0, nz, d_occ, d_seen);
-    ARVX_HIP(hipGetLastError());
+    arvx::CarveParams g = record_params(ctx);
+    ARVX_TRY(launch(ctx, arvx::rec_from_planes_kernel, blocks_for(nwords), 256, g, ctx->z0 - ctx->ze0, nz, d_occ,
+                    d_seen));
     ARVX_SYNC(ctx);  // the host planes may go away
     return ARVX_OK;
 }
@@ -1271,12 +1282,9 @@ int arvx_state_download_planes(arvx_ctx *ctx, uint32_t *occ, uint32_t *seen) {
     const size_t nwords = (size_t)((ctx->X + 31) / 32) * ctx->Y * nz;
     ARVX_HIP(ctx->pool_scratch.reserve(2 * nwords * sizeof(uint32_t) + 64));
     uint32_t *d_occ = (uint32_t *)ctx->pool_scratch.p, *d_seen = d_occ + nwords;
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
-    hipLaunchKernelGGL(arvx::planes_from_rec_kernel, dim3((unsigned)((nwords + 255) / 256)),
-                       dim3(256), 0, ctx->stream, g, ctx->z0 - ctx->ze0, nz, d_occ, d_seen);
-    ARVX_HIP(hipGetLastError());
+    arvx::CarveParams g = record_params(ctx);
+    ARVX_TRY(launch(ctx, arvx::planes_from_rec_kernel, blocks_for(nwords), 256, g, ctx->z0 - ctx->ze0, nz, d_occ,
+                    d_seen));
     ARVX_HIP(hipMemcpyAsync(occ, d_occ, nwords * 4, hipMemcpyDeviceToHost, ctx->stream));
     ARVX_HIP(hipMemcpyAsync(seen, d_seen, nwords * 4, hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);
@@ -1310,9 +1318,7 @@ int arvx_state_download_packets(arvx_ctx *ctx, uint64_t *occ_packet, int64_t occ
     if (!(ctx->packets_seq == ctx->state_seq && ctx->pool_state_packets.cap >= 2 * S * 8)) {
         if (int mrc = need_rec(ctx, true)) return mrc;
         ARVX_HIP(ctx->pool_state_packets.reserve(2 * S * 8));
-        arvx::CarveParams g;
-        carve_geometry(ctx, g);
-        g.rec = ctx->rec();
+        arvx::CarveParams g = record_params(ctx);
         const int zl0 = ctx->z0 - ctx->ze0;
         const int nwg = (int)((nb + arvx::kOccGroupsPerWg - 1) / arvx::kOccGroupsPerWg);
         arvx::OccGeom og;
@@ -1322,15 +1328,14 @@ int arvx_state_download_packets(arvx_ctx *ctx, uint64_t *occ_packet, int64_t occ
         ARVX_HIP(ctx->pool_scratch.reserve(2 * (size_t)nwg * sizeof(int) + 64));
         int *d_wgsum = (int *)ctx->pool_scratch.p;
         unsigned long long *pk = (unsigned long long *)ctx->pool_state_packets.p;
-        hipLaunchKernelGGL(arvx::occ_pack_classify_kernel<false>, dim3(nwg), dim3(256), 0, ctx->stream, g, og,
-                           zl0, n, pk, d_wgsum, (unsigned long long *)nullptr);
-        hipLaunchKernelGGL(arvx::occ_pack_classify_kernel<true>, dim3(nwg), dim3(256), 0, ctx->stream, g, og,
-                           zl0, n, pk + S, d_wgsum + nwg, (unsigned long long *)nullptr);
-        hipLaunchKernelGGL(arvx::occ_pack_write_kernel<false>, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0,
-                           ctx->stream, g, og, zl0, n, n, d_wgsum, nwg, pk);
-        hipLaunchKernelGGL(arvx::occ_pack_write_kernel<true>, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0,
-                           ctx->stream, g, og, zl0, n, n, d_wgsum + nwg, nwg, pk + S);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::occ_pack_classify_kernel<false>, nwg, 256, g, og, zl0, n, pk, d_wgsum,
+                        nullptr));
+        ARVX_TRY(launch(ctx, arvx::occ_pack_classify_kernel<true>, nwg, 256, g, og, zl0, n, pk + S,
+                        d_wgsum + nwg, nullptr));
+        ARVX_TRY(launch(ctx, arvx::occ_pack_write_kernel<false>, blocks_for(nb, 4), 256, g, og, zl0, n, n,
+                        d_wgsum, nwg, pk));
+        ARVX_TRY(launch(ctx, arvx::occ_pack_write_kernel<true>, blocks_for(nb, 4), 256, g, og, zl0, n, n,
+                        d_wgsum + nwg, nwg, pk + S));
         // the two counts first (16 bytes through their page-locked count words)
         ARVX_HIP(hipMemcpyAsync(&ctx->word(Ctx::kPacketOcc), pk, 8, hipMemcpyDeviceToHost, ctx->stream));
         ARVX_HIP(hipMemcpyAsync(&ctx->word(Ctx::kPacketSeen), pk + S, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1362,11 +1367,8 @@ int arvx_handle_unseen(arvx_ctx *ctx) {
     arvx::CarveParams g;
     carve_geometry(ctx, g);
     const size_t nrec = arvx::rec_count(g);
-    hipLaunchKernelGGL(arvx::rec_handle_unseen_kernel, dim3((unsigned)((nrec * 32 + 255) / 256)),
-                       dim3(256), 0, ctx->stream, (uint32_t *)ctx->rec(), nrec, g.ccode,
-                       g.cyShift + g.czShift + 2);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::rec_handle_unseen_kernel, blocks_for(nrec * 32), 256, (uint32_t *)ctx->rec(), nrec,
+                  g.ccode, g.cyShift + g.czShift + 2);
 }
 
 int arvx_host_register(void *ptr, size_t bytes) {
@@ -1393,16 +1395,12 @@ int arvx_state_device_ptr(arvx_ctx *ctx, void **ptr, size_t *bytes) {
 // X % 64 == 0 and an 8-byte aligned destination: the tile-wise pack (state_kernels.h)
 static int launch_pack_tiles(Ctx *ctx, int global, void *dev_words) {
     if (int mrc = need_rec(ctx, true)) return mrc;
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
+    arvx::CarveParams g = record_params(ctx);
     const int zl0 = ctx->z0 - ctx->ze0, nz = ctx->z1 - ctx->z0;
     const int ntz = ((zl0 + nz - 1) >> 3) - (zl0 >> 3) + 1;
     const size_t tiles = (size_t)g.tilesX * g.tilesY * ntz;
-    hipLaunchKernelGGL(arvx::pack_occupancy_tile_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0,
-                       ctx->stream, g, zl0, nz, global, (unsigned long long *)dev_words);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::pack_occupancy_tile_kernel, blocks_for(tiles, 4), 256, g, zl0, nz, global,
+                  (unsigned long long *)dev_words);
 }
 
 int arvx_pack_occupancy(arvx_ctx *ctx, void *dev_words) {
@@ -1413,47 +1411,36 @@ int arvx_pack_occupancy(arvx_ctx *ctx, void *dev_words) {
     if (ctx->X % 32 == 0 && (uintptr_t)dev_words % 4 == 0) {
         // straight from the records: 2 bits per voxel in, 1 out
         if (int mrc = need_rec(ctx, true)) return mrc;
-        arvx::CarveParams g;
-        carve_geometry(ctx, g);
-        g.rec = ctx->rec();
+        arvx::CarveParams g = record_params(ctx);
         const int nz = ctx->z1 - ctx->z0;
         const size_t nwords = (size_t)(ctx->X / 32) * ctx->Y * nz;
-        hipLaunchKernelGGL(arvx::pack_occupancy_rec_kernel, dim3((unsigned)((nwords + 255) / 256)),
-                           dim3(256), 0, ctx->stream, g, ctx->z0 - ctx->ze0, nz, 0,
-                           (uint32_t *)dev_words);
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        return launch(ctx, arvx::pack_occupancy_rec_kernel, blocks_for(nwords), 256, g, ctx->z0 - ctx->ze0, nz,
+                      0, (uint32_t *)dev_words);
     }
     if (ctx->X % 8 == 0 && ((size_t)ctx->X * ctx->Y) % 32 == 0 && (uintptr_t)dev_words % 4 == 0) {
         if (int mrc = need_rec(ctx, true)) return mrc;
-        arvx::CarveParams g;
-        carve_geometry(ctx, g);
-        g.rec = ctx->rec();
+        arvx::CarveParams g = record_params(ctx);
         const int nz = ctx->z1 - ctx->z0;
         const size_t nwords = ((size_t)ctx->X * ctx->Y * nz / 8 + 3) / 4;
-        hipLaunchKernelGGL(arvx::pack_occupancy_rec8_kernel, dim3((unsigned)((nwords + 255) / 256)),
-                           dim3(256), 0, ctx->stream, g, ctx->z0 - ctx->ze0, nz, 0,
-                           (uint32_t *)dev_words);
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        return launch(ctx, arvx::pack_occupancy_rec8_kernel, blocks_for(nwords), 256, g, ctx->z0 - ctx->ze0, nz,
+                      0, (uint32_t *)dev_words);
     }
     // odd row lengths: through the byte form
     if (int mrc = records_into_bytes(ctx, ctx->z0 - ctx->ze0, ctx->z1 - ctx->z0)) return mrc;
     if (ctx->nvox % 32 == 0 && (uintptr_t)ctx->owned() % 16 == 0 && (uintptr_t)dev_words % 4 == 0) {
         const size_t nwords = ctx->nvox / 32;
-        hipLaunchKernelGGL(arvx::pack_occupancy32_kernel, dim3((unsigned)((nwords + 255) / 256)),
-                           dim3(256), 0, ctx->stream, ctx->owned(), nwords, (uint32_t *)dev_words);
+        ARVX_TRY(launch(ctx, arvx::pack_occupancy32_kernel, blocks_for(nwords), 256, ctx->owned(), nwords,
+                        (uint32_t *)dev_words));
     } else if (ctx->nvox % 32 == 0 && (uintptr_t)ctx->owned() % 8 == 0) {
         const size_t nbytes = ctx->nvox / 8;
-        hipLaunchKernelGGL(arvx::pack_occupancy8_kernel, dim3((unsigned)((nbytes + 255) / 256)),
-                           dim3(256), 0, ctx->stream, ctx->owned(), nbytes, (uint8_t *)dev_words);
+        ARVX_TRY(launch(ctx, arvx::pack_occupancy8_kernel, blocks_for(nbytes), 256, ctx->owned(), nbytes,
+                        (uint8_t *)dev_words));
     } else {
         const size_t nround = (ctx->nvox + 255) / 256;
         const unsigned grid = (unsigned)(nround < 8192 ? (nround ? nround : 1) : 8192);
-        hipLaunchKernelGGL(arvx::pack_occupancy_kernel, dim3(grid), dim3(256), 0, ctx->stream,
-                           ctx->owned(), ctx->nvox, (uint32_t *)dev_words);
+        ARVX_TRY(launch(ctx, arvx::pack_occupancy_kernel, grid, 256, ctx->owned(), ctx->nvox,
+                        (uint32_t *)dev_words));
     }
-    ARVX_HIP(hipGetLastError());
     return ARVX_OK;
 }
 
@@ -1467,39 +1454,26 @@ int arvx_pack_occupancy_global(arvx_ctx *ctx, void *dev_global_words) {
         return launch_pack_tiles(ctx, 1, dev_global_words);
     if (ctx->X % 32 == 0) {
         if (int mrc = need_rec(ctx, true)) return mrc;
-        arvx::CarveParams g;
-        carve_geometry(ctx, g);
-        g.rec = ctx->rec();
+        arvx::CarveParams g = record_params(ctx);
         const int nz = ctx->z1 - ctx->z0;
         const size_t nwords = (size_t)(ctx->X / 32) * ctx->Y * nz;
-        hipLaunchKernelGGL(arvx::pack_occupancy_rec_kernel, dim3((unsigned)((nwords + 255) / 256)),
-                           dim3(256), 0, ctx->stream, g, ctx->z0 - ctx->ze0, nz, 1,
-                           (uint32_t *)dev_global_words);
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        return launch(ctx, arvx::pack_occupancy_rec_kernel, blocks_for(nwords), 256, g, ctx->z0 - ctx->ze0, nz,
+                      1, (uint32_t *)dev_global_words);
     }
     if (ctx->X % 8 == 0) {  // (X * Y % 64 == 0 above)
         if (int mrc = need_rec(ctx, true)) return mrc;
-        arvx::CarveParams g;
-        carve_geometry(ctx, g);
-        g.rec = ctx->rec();
+        arvx::CarveParams g = record_params(ctx);
         const int nz = ctx->z1 - ctx->z0;
         const size_t nwords = (size_t)ctx->X * ctx->Y * nz / 32;
-        hipLaunchKernelGGL(arvx::pack_occupancy_rec8_kernel, dim3((unsigned)((nwords + 255) / 256)),
-                           dim3(256), 0, ctx->stream, g, ctx->z0 - ctx->ze0, nz, 1,
-                           (uint32_t *)dev_global_words);
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        return launch(ctx, arvx::pack_occupancy_rec8_kernel, blocks_for(nwords), 256, g, ctx->z0 - ctx->ze0, nz,
+                      1, (uint32_t *)dev_global_words);
     }
     if (int mrc = records_into_bytes(ctx, ctx->z0 - ctx->ze0, ctx->z1 - ctx->z0)) return mrc;
     // plane % 64 == 0 and an aligned allocation: every plane starts on an 8-byte boundary
     const size_t nbytes = ctx->nvox / 8;
-    hipLaunchKernelGGL(arvx::pack_occupancy_global8_kernel, dim3((unsigned)((nbytes + 255) / 256)),
-                       dim3(256), 0, ctx->stream, ctx->owned(), plane, ctx->z1 - ctx->z0,
-                       ctx->stripe_world > 1 ? 0 : ctx->z0, ctx->stripe_world, ctx->stripe_rank,
-                       (uint8_t *)dev_global_words);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::pack_occupancy_global8_kernel, blocks_for(nbytes), 256, ctx->owned(), plane,
+                  ctx->z1 - ctx->z0, ctx->stripe_world > 1 ? 0 : ctx->z0, ctx->stripe_world,
+                  ctx->stripe_rank, (uint8_t *)dev_global_words);
 }
 
 // ---- compressed occupancy exchange -----------------------------------------------------
@@ -1526,16 +1500,11 @@ int arvx_occupancy_compress(arvx_ctx *ctx, const void *dev_words, int64_t n_word
                                         (size_t)nwg * sizeof(int) + 64));
     long long *d_wgoff = (long long *)ctx->pool_xscratch.p;  // nwg + 1 offsets, last = total
     int *d_wgsum = (int *)(d_wgoff + nwg + 1);
-    hipLaunchKernelGGL(arvx::occ_classify_kernel, dim3(nwg), dim3(256), 0, ctx->stream,
-                       (const unsigned long long *)dev_words, n, (unsigned long long *)dev_packet,
-                       d_wgsum);
-    hipLaunchKernelGGL(arvx::mc_scan_blocks_kernel, dim3(1), dim3(256), 0, ctx->stream, d_wgsum, nwg,
-                       d_wgoff);
-    hipLaunchKernelGGL(arvx::occ_write_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0,
-                       ctx->stream, (const unsigned long long *)dev_words, n, (long long)cap_words64,
-                       d_wgoff, nwg, (unsigned long long *)dev_packet);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    const unsigned long long *words = (const unsigned long long *)dev_words;
+    unsigned long long *packet = (unsigned long long *)dev_packet;
+    ARVX_TRY(launch(ctx, arvx::occ_classify_kernel, nwg, 256, words, n, packet, d_wgsum));
+    ARVX_TRY(launch(ctx, arvx::mc_scan_blocks_kernel, 1, 256, d_wgsum, nwg, d_wgoff));
+    return launch(ctx, arvx::occ_write_kernel, blocks_for(nb, 4), 256, words, n, cap_words64, d_wgoff, nwg, packet);
 }
 
 int arvx_occupancy_pack_compress(arvx_ctx *ctx, void *dev_packet, int64_t cap_words64,
@@ -1549,9 +1518,7 @@ int arvx_occupancy_pack_compress(arvx_ctx *ctx, void *dev_packet, int64_t cap_wo
     if (ctx->X % 32 || plane % 64)
         return fail(ARVX_ERR_INVALID, "needs X %% 32 == 0 and X*Y %% 64 == 0 (X=%d, Y=%d)", ctx->X, ctx->Y);
     if (int mrc = need_rec(ctx, true)) return mrc;
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
+    arvx::CarveParams g = record_params(ctx);
     const int zl0 = ctx->z0 - ctx->ze0, nz = ctx->z1 - ctx->z0;
     const long long n = (long long)(plane / 64) * nz, nb = (n + 63) / 64;
     if (2 * n >= (1ll << 32)) return fail(ARVX_ERR_INVALID, "slab too large for the fused packet (%lld words)", n);
@@ -1564,13 +1531,11 @@ int arvx_occupancy_pack_compress(arvx_ctx *ctx, void *dev_packet, int64_t cap_wo
     ARVX_HIP(ctx->pool_xscratch.reserve((size_t)(nwg + 1) * sizeof(long long) +
                                         (size_t)nwg * sizeof(int) + 64));
     int *d_wgsum = (int *)((long long *)ctx->pool_xscratch.p + nwg + 1);
-    hipLaunchKernelGGL(arvx::occ_pack_classify_kernel, dim3(nwg), dim3(256), 0, ctx->stream, g, og, zl0, n,
-                       (unsigned long long *)dev_packet, d_wgsum, (unsigned long long *)dev_full_words);
-    hipLaunchKernelGGL(arvx::occ_pack_write_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0,
-                       ctx->stream, g, og, zl0, n, (long long)cap_words64, d_wgsum, nwg,
-                       (unsigned long long *)dev_packet);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    unsigned long long *packet = (unsigned long long *)dev_packet;
+    ARVX_TRY(launch(ctx, arvx::occ_pack_classify_kernel<false>, nwg, 256, g, og, zl0, n, packet, d_wgsum,
+                    (unsigned long long *)dev_full_words));
+    return launch(ctx, arvx::occ_pack_write_kernel<false>, blocks_for(nb, 4), 256, g, og, zl0, n, cap_words64,
+                  d_wgsum, nwg, packet);
 }
 
 int arvx_occupancy_expand(arvx_ctx *ctx, const void *dev_packets, int world, int self_rank,
@@ -1586,12 +1551,9 @@ int arvx_occupancy_expand(arvx_ctx *ctx, const void *dev_packets, int world, int
     const long long n = n_words64, nb = (n + 63) / 64;
     const long long S = arvx::occ_packet_header(n) + cap_words64;
     const long long per = (nb + 2 * arvx::kExpandChunks - 1) / (2 * arvx::kExpandChunks);
-    hipLaunchKernelGGL(arvx::occ_expand_kernel, dim3((unsigned)((per * world + 3) / 4)), dim3(256), 0,
-                       ctx->stream, (const unsigned long long *)dev_packets, S, world, self_rank, n,
-                       (long long)cap_words64, (unsigned long long *)dev_full_words, dev_overflow,
-                       0ll);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::occ_expand_kernel, blocks_for(per * world, 4), 256,
+                  (const unsigned long long *)dev_packets, S, world, self_rank, n, cap_words64,
+                  (unsigned long long *)dev_full_words, dev_overflow, 0ll);
 }
 
 int arvx_occupancy_expand_striped(arvx_ctx *ctx, const void *dev_packets, int world,
@@ -1617,12 +1579,9 @@ int arvx_occupancy_expand_striped_others(arvx_ctx *ctx, const void *dev_packets,
     const long long n = n_words64, nb = (n + 63) / 64;
     const long long S = arvx::occ_packet_header(n) + cap_words64;
     const long long per = (nb + 2 * arvx::kExpandChunks - 1) / (2 * arvx::kExpandChunks);
-    hipLaunchKernelGGL(arvx::occ_expand_kernel, dim3((unsigned)((per * world + 3) / 4)), dim3(256), 0,
-                       ctx->stream, (const unsigned long long *)dev_packets, S, world, self_rank, n,
-                       (long long)cap_words64, (unsigned long long *)dev_full_words, dev_overflow,
-                       (long long)words_per_group);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::occ_expand_kernel, blocks_for(per * world, 4), 256,
+                  (const unsigned long long *)dev_packets, S, world, self_rank, n, cap_words64,
+                  (unsigned long long *)dev_full_words, dev_overflow, words_per_group);
 }
 
 // ---- carve -------------------------------------------------------------------
@@ -1698,15 +1657,11 @@ static int launch_carve_stream(Ctx *ctx, arvx::CarveParams p, int ncu) {
 #endif
     // (the chunks of 64 views are a template parameter: up to 64 views, or up to 256)
     const bool left = ctx->assoc == ARVX_ASSOC_LEFT, one = p.nchunks == 1;
-    if (left && one)
-        hipLaunchKernelGGL((arvx::carve_stream_kernel<true, 1>), dim3(G), dim3(256), 0, ctx->stream, p);
-    else if (left)
-        hipLaunchKernelGGL((arvx::carve_stream_kernel<true, arvx::kMaxChunks>), dim3(G), dim3(256), 0, ctx->stream, p);
-    else if (one)
-        hipLaunchKernelGGL((arvx::carve_stream_kernel<false, 1>), dim3(G), dim3(256), 0, ctx->stream, p);
-    else
-        hipLaunchKernelGGL((arvx::carve_stream_kernel<false, arvx::kMaxChunks>), dim3(G), dim3(256), 0, ctx->stream, p);
-    ARVX_HIP(hipGetLastError());
+    void (*stream)(arvx::CarveParams) = left && one ? arvx::carve_stream_kernel<true, 1>
+                                        : left      ? arvx::carve_stream_kernel<true, arvx::kMaxChunks>
+                                        : one       ? arvx::carve_stream_kernel<false, 1>
+                                                    : arvx::carve_stream_kernel<false, arvx::kMaxChunks>;
+    ARVX_TRY(launch(ctx, stream, G, 256, p));
     ctx->form = Form::Lazy;
     ctx->cstate_tiles = ncoarse;
     ctx->path_bits = ARVX_PATH_STREAM | ARVX_PATH_FRESH | ARVX_PATH_LAZY_CODES;
@@ -1752,10 +1707,9 @@ static int rect_cache_prepare(Ctx *ctx, arvx::CarveParams &p) {
             return ARVX_OK;
         }
         ctx->word(Ctx::kRectMiss) = 0;
-        hipLaunchKernelGGL(arvx::rect_cache_block_kernel<false>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)),
-                           dim3(256), 0, ctx->stream, p, (uint32_t *)ctx->pool_rect.p, n,
-                           ctx->word_dev(Ctx::kRectMiss), (unsigned long long *)nullptr);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::rect_cache_block_kernel<false>,
+                        (unsigned)std::min<size_t>((n + 255) / 256, 65536), 256, p,
+                        (uint32_t *)ctx->pool_rect.p, n, ctx->word_dev(Ctx::kRectMiss), nullptr));
         ARVX_SYNC(ctx);
         if (ctx->word(Ctx::kRectMiss)) {  // a rectangle too large for an entry: computed as before
             ctx->word(Ctx::kRectMiss) = 0;
@@ -1794,12 +1748,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     const bool split = cull && !(flags & ARVX_CARVE_FUSED) && p.nchunks <= arvx::kMaxChunks;
     static const bool two_launches = experiment_flag("ARVX_COARSE_SPLIT");
     const size_t ncoarse = (size_t)p.coarseX * p.coarseY * p.coarseZ;
-    if (ctx->ncu <= 0) {
-        ctx->ncu = 256;
-        (void)hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-        if (ctx->ncu <= 0) ctx->ncu = 256;
-    }
-    const int ncu = ctx->ncu;
+    const int ncu = compute_units(ctx);
     size_t layout_when_done = 0;
     bool lazy = false;
     ctx->path_bits = ctx->path_dense_grid = 0;  // (arvx_last_carve_path)
@@ -1896,9 +1845,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
             // (16 tiles per workgroup where that still leaves a workgroup per compute unit:
             // fewer appends to the list's counter; 4 on small grids)
             if (p.nchunks > arvx::kMaxChunks) {  // (only the fused kernel takes that many views)
-                hipLaunchKernelGGL(arvx::carve_coarse_wave_kernel, dim3((unsigned)((ncoarse + 3) / 4)),
-                                   dim3(256), 0, ctx->stream, p);
-                ARVX_HIP(hipGetLastError());
+                ARVX_TRY(launch(ctx, arvx::carve_coarse_wave_kernel, blocks_for(ncoarse, 4), 256, p));
             } else {
                 const int cw = ncoarse >= (size_t)16 * ncu ? arvx::kCoarseWaves : 4;
                 p.coarsePerWg = cw;
@@ -1906,10 +1853,8 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
                 const size_t pairs = (size_t)cw * (size_t)(p.v1 - p.v0);
                 const unsigned threads =
                     (unsigned)std::min<size_t>(64 * arvx::kCoarseWaves, (pairs + 63) / 64 * 64);
-                hipLaunchKernelGGL(arvx::carve_coarse_kernel,
-                                   dim3((unsigned)((ncoarse + cw - 1) / cw)),
-                                   dim3(std::max(threads, 64u)), 0, ctx->stream, p);
-                ARVX_HIP(hipGetLastError());
+                ARVX_TRY(launch(ctx, arvx::carve_coarse_kernel, (unsigned)((ncoarse + cw - 1) / cw),
+                                std::max(threads, 64u), p));
             }
         }
     }
@@ -1932,15 +1877,10 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     if (split) {
         // coarse tiles: classified, and the decided ones written as constant records, one
         // workgroup each
-        if (lazy) {
-            // (carve_coarse_kernel above did everything)
-        } else if (two_launches)
-            hipLaunchKernelGGL(arvx::carve_fill_kernel, dim3((unsigned)ncoarse), dim3(256), 0,
-                               ctx->stream, p);
-        else
-            hipLaunchKernelGGL(arvx::carve_coarse_fill_kernel, dim3((unsigned)ncoarse), dim3(256),
-                               0, ctx->stream, p);
-        ARVX_HIP(hipGetLastError());
+        // (lazy: carve_coarse_kernel above did everything)
+        if (!lazy)
+            ARVX_TRY(launch(ctx, two_launches ? arvx::carve_fill_kernel : arvx::carve_coarse_fill_kernel,
+                            (unsigned)ncoarse, 256, p));
         // the others: a fixed grid walks the list (8 waves per SIMD)
         static const int cgrid_env = experiment_int("ARVX_CLASSIFY_WGS");
         const unsigned cgrid = cgrid_env > 0 ? (unsigned)cgrid_env : (unsigned)ncu * 8u;
@@ -1961,11 +1901,10 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
             ctx->rect_streak = 0;
         }
         if (dense)  // one workgroup per listed coarse tile and turn
-            hipLaunchKernelGGL(arvx::carve_classify_dense_kernel, dim3((unsigned)ncu * (unsigned)ARVX_DENSE_WGS_PER_CU), dim3(256),
-                               0, ctx->stream, p);
+            ARVX_TRY(launch(ctx, arvx::carve_classify_dense_kernel,
+                            (unsigned)ncu * (unsigned)ARVX_DENSE_WGS_PER_CU, 256, p));
         else
-            hipLaunchKernelGGL(arvx::carve_classify_kernel, dim3(cgrid), dim3(256), 0, ctx->stream, p);
-        ARVX_HIP(hipGetLastError());
+            ARVX_TRY(launch(ctx, arvx::carve_classify_kernel, cgrid, 256, p));
         const unsigned pgrid = (unsigned)(p.nwaves / 4);
 #ifdef ARVX_TIMELINE
         if (int rc = timeline(ctx, (size_t)pgrid * 4, 64, p)) return rc;  // one record per WAVE of the persistent kernel
@@ -1979,57 +1918,29 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         // the fp32 filter in front of the exact projection (carve_kernels.h, filtered_view_blocks):
         // for callers whose masks leave most blocks of an item to be projected (ARVX_CARVE_FILTER)
         const bool filter = (flags & ARVX_CARVE_FILTER) != 0;
-        if (blocks && filter && left && may_split)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, true, false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && filter && left && fresh)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, false, true, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && filter && left)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, false, false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && filter && may_split)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<false, true, false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && filter && fresh)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<false, false, true, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && filter)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<false, false, false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else
 #endif
-        if (cached && left)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, false, true, false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (cached)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<false, false, true, false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && left && may_split)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && left && fresh)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && left)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<true, false>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && may_split)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks && fresh)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<false, false, true>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (blocks)
-            hipLaunchKernelGGL((arvx::carve_exact_blocks_kernel<false, false>), dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else if (left)
-            hipLaunchKernelGGL(arvx::carve_exact_kernel<true>, dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        else
-            hipLaunchKernelGGL(arvx::carve_exact_kernel<false>, dim3(pgrid), dim3(256), 0,
-                               ctx->stream, p);
-        ARVX_HIP(hipGetLastError());
+        // the exact kernel's instantiation: that of the first line whose condition holds
+        void (*exact)(arvx::CarveParams) =
+#ifdef ARVX_EXPERIMENTS
+            blocks && filter && left && may_split ? arvx::carve_exact_blocks_kernel<true, true, false, true>
+            : blocks && filter && left && fresh   ? arvx::carve_exact_blocks_kernel<true, false, true, true>
+            : blocks && filter && left            ? arvx::carve_exact_blocks_kernel<true, false, false, true>
+            : blocks && filter && may_split       ? arvx::carve_exact_blocks_kernel<false, true, false, true>
+            : blocks && filter && fresh           ? arvx::carve_exact_blocks_kernel<false, false, true, true>
+            : blocks && filter                    ? arvx::carve_exact_blocks_kernel<false, false, false, true>
+            :
+#endif
+            cached && left                ? arvx::carve_exact_blocks_kernel<true, false, true, false, true>
+            : cached                      ? arvx::carve_exact_blocks_kernel<false, false, true, false, true>
+            : blocks && left && may_split ? arvx::carve_exact_blocks_kernel<true, true>
+            : blocks && left && fresh     ? arvx::carve_exact_blocks_kernel<true, false, true>
+            : blocks && left              ? arvx::carve_exact_blocks_kernel<true, false>
+            : blocks && may_split         ? arvx::carve_exact_blocks_kernel<false, true>
+            : blocks && fresh             ? arvx::carve_exact_blocks_kernel<false, false, true>
+            : blocks                      ? arvx::carve_exact_blocks_kernel<false, false>
+            : left                        ? arvx::carve_exact_kernel<true>
+                                          : arvx::carve_exact_kernel<false>;
+        ARVX_TRY(launch(ctx, exact, pgrid, 256, p));
         ctx->carve_layout = layout_when_done;
         ++ctx->carve_seq;
         // (arvx_last_carve_path: all of it once every launch is out, or nothing)
@@ -2046,11 +1957,8 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
 #ifdef ARVX_TIMELINE
     if (int rc = timeline(ctx, grid, 32, p)) return rc;
 #endif
-    if (ctx->assoc == ARVX_ASSOC_LEFT)
-        hipLaunchKernelGGL(arvx::carve_fused_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, p);
-    else
-        hipLaunchKernelGGL(arvx::carve_fused_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, p);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, ctx->assoc == ARVX_ASSOC_LEFT ? arvx::carve_fused_kernel<true> : arvx::carve_fused_kernel<false>,
+                    grid, 256, p));
     ctx->path_bits = (cull ? ARVX_PATH_FUSED : ARVX_PATH_BRUTE_FORCE) | (fresh ? ARVX_PATH_FRESH : 0u);
     ctx->rect_streak = 0;
     return ARVX_OK;
@@ -2113,8 +2021,7 @@ int arvx_last_carve_path(arvx_ctx *ctx, uint32_t out[4]) {
 int arvx_carve_votes(arvx_ctx *ctx, int max_misses, unsigned flags) {
     ARVX_CHECK_CTX(ctx);
     if (!ctx->views_ready) return fail(ARVX_ERR_STATE, "arvx_set_views (with masks) has not been called");
-    if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
-        return fail(ARVX_ERR_STATE, "arvx_carve_votes needs a whole-grid context");
+    if (!whole_grid(ctx)) return fail(ARVX_ERR_STATE, "arvx_carve_votes needs a whole-grid context");
     if (max_misses < 0 || max_misses > 65535)
         return fail(ARVX_ERR_INVALID, "max_misses %d: must be in [0, 65535]", max_misses);
     if (ctx->V > 65535) return fail(ARVX_ERR_INVALID, "%d views: the counts are 16 bits wide", ctx->V);
@@ -2135,8 +2042,7 @@ int arvx_carve_votes(arvx_ctx *ctx, int max_misses, unsigned flags) {
     ctx->form = Form::Records;
     arvx::VoteCarveParams q;
     arvx::CarveParams &p = q.g;
-    carve_geometry(ctx, p);
-    p.rec = ctx->rec();
+    p = record_params(ctx);
     p.ccode = nullptr;
     carve_views(ctx, p);
     p.v0 = 0;
@@ -2148,10 +2054,9 @@ int arvx_carve_votes(arvx_ctx *ctx, int max_misses, unsigned flags) {
     q.cull = (flags & ARVX_VOTES_NO_CULL) ? 0 : 1;
     const size_t rows8 = ((size_t)p.tilesY * p.tilesZ + 7) / 8 * 8;
     const unsigned grid = (unsigned)(rows8 * p.tilesX);
-    by_assoc(ctx, [&](auto left) {
-        hipLaunchKernelGGL(arvx::carve_votes_kernel<decltype(left)::value>, dim3(grid), dim3(256), 0, ctx->stream, q);
-    });
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(by_assoc(ctx, [&](auto left) {
+        return launch(ctx, arvx::carve_votes_kernel<decltype(left)::value>, grid, 256, q);
+    }));
     ctx->votes_ready = (flags & ARVX_VOTES_COUNTS) != 0;
     return ARVX_OK;
 }
@@ -2296,19 +2201,17 @@ static arvx::VoteParams vote_params(const Ctx *ctx, int zglob0) {
 // pool_col_bits / pool_col_rank.  The list's length is not known before the compaction has run: the
 // kernels stop at the capacity the buffers were sized for, and a list that outgrew it is compacted
 // and worked on again with room for all of it (run_lists).  Per attempt:
-// reserve(cap) sizes the caller's buffers, launch(vp) enqueues its kernels on the list vp describes
+// reserve(cap) sizes the caller's buffers, enqueue(vp) launches its kernels on the list vp describes
 // (length on the device, in vp.n_dev; vp.rgba / depth / has / mode are the caller's to fill), and
 // settle() reads what they left after the synchronisation.
 extern "C++" {  // (a template, inside the C-ABI's extern "C" block)
-template <class Reserve, class Launch, class Settle>
-static int surface_list(Ctx *ctx, Reserve reserve, Launch launch, Settle settle, long long *total_out) {
-    const int XW = (ctx->X + 63) / 64;
+template <class Reserve, class Enqueue, class Settle>
+static int surface_list(Ctx *ctx, Reserve reserve, Enqueue enqueue, Settle settle, long long *total_out) {
     const int Zext = ctx->ze1 - ctx->ze0;
     int c_lo, c_hi, f_lo, f_hi;
     stage_ranges(ctx, 0, c_lo, c_hi, f_lo, f_hi);
-    const arvx::BitGrid gext{ctx->X, ctx->Y, Zext, XW};
-    const size_t row_words = (size_t)XW * ctx->Y;
-    const size_t nw_ext = row_words * Zext;
+    const arvx::BitGrid gext = bit_grid(ctx, Zext);
+    const size_t nw_ext = bit_words(gext);
     // the surface plane stays with the context: with its ranks it is the index of the colour
     // list (closure and mesh look colours up through it)
     ARVX_HIP(ctx->pool_col_bits.reserve(nw_ext * sizeof(unsigned long long)));
@@ -2328,9 +2231,8 @@ static int surface_list(Ctx *ctx, Reserve reserve, Launch launch, Settle settle,
     // compaction, its number of set bits
     int *d_counts = nullptr;
     if (int rc = chunk_counts(ctx, nw_ext, &d_counts)) return rc;
-    hipLaunchKernelGGL(arvx::bit_surface_count_kernel, dim3((unsigned)((nw_ext + 255) / 256)), dim3(256), 0,
-                       ctx->stream, d_occ, gext, c_lo - ctx->ze0, c_hi - ctx->ze0, d_surf, d_counts);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::bit_surface_count_kernel, blocks_for(nw_ext), 256, d_occ, gext, c_lo - ctx->ze0,
+                    c_hi - ctx->ze0, d_surf, d_counts));
     const double v = (double)ctx->X * ctx->Y * Zext;
     ListRoom lists[] = {{Ctx::kSurface, list_cap(ctx->pool_surf_index, sizeof(int), first_list_cap(v, v)), 0}};
     const long long &cap = lists[0].cap;
@@ -2346,9 +2248,7 @@ static int surface_list(Ctx *ctx, Reserve reserve, Launch launch, Settle settle,
         vp.index = ctx->d_surf_index;
         vp.n = cap;
         vp.n_dev = d_total;
-        if (int rc = launch(vp)) return rc;
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        return enqueue(vp);
     };
     if (int rc = run_lists(ctx, lists, attempt, settle)) return rc;
     *total_out = lists[0].total;
@@ -2370,28 +2270,22 @@ static int color_pass(Ctx *ctx, int mode, bool visible, float tol) {
         if (visible) ARVX_HIP(ctx->pool_vis_views.reserve((size_t)cap * sizeof(int)));
         return ARVX_OK;
     };
-    auto launch = [&](arvx::VoteParams vp) -> int {
-        const long long cap = vp.n;
+    auto enqueue = [&](arvx::VoteParams vp) -> int {
         vp.mode = mode;
         vp.rgba = ctx->d_surf_rgba;
         vp.depth = ctx->d_surf_depth;
         vp.has = ctx->d_surf_has;
-        if (visible) {
-            if (int rc = launch_visible_vote(ctx, vp, tol)) return rc;
-        } else {
-            by_assoc(ctx, [&](auto left) {
-                hipLaunchKernelGGL(arvx::color_vote_kernel<decltype(left)::value>,
-                                   dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, vp);
-            });
-        }
-        return ARVX_OK;
+        if (visible) return launch_visible_vote(ctx, vp, tol);
+        return by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::color_vote_kernel<decltype(left)::value>, blocks_for(vp.n), 256, vp);
+        });
     };
     auto settle = [&]() -> int {
         if (visible && ctx->word(Ctx::kVisNeed) >= 0) ctx->vis_large_need = ctx->word(Ctx::kVisNeed);
         return ARVX_OK;
     };
     long long total = 0;
-    if (int rc = surface_list(ctx, reserve, launch, settle, &total)) return rc;
+    if (int rc = surface_list(ctx, reserve, enqueue, settle, &total)) return rc;
     ctx->surf_count = total;
     ctx->surf_host_count = -1;  // the host copies of the list are fetched when somebody asks
     if (total == 0) {
@@ -2426,9 +2320,8 @@ static int launch_depth_buffers(Ctx *ctx, const int *index, long long cap, const
     unsigned *n_large = (unsigned *)ctx->pool_vis_large.p;
     arvx::SplatRect *large = (arvx::SplatRect *)((uint8_t *)ctx->pool_vis_large.p + 64);
     const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
-    hipLaunchKernelGGL(arvx::vis_clear_kernel, dim3((unsigned)std::min<size_t>((nz + 255) / 256, 8 * ncu)),
-                       dim3(256), 0, ctx->stream, zbuf, nz, n_large);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::vis_clear_kernel, (unsigned)std::min<size_t>((nz + 255) / 256, 8 * ncu), 256,
+                    zbuf, nz, n_large));
     arvx::SplatParams sp;
     sp.index = index;
     sp.cap = cap;
@@ -2446,14 +2339,11 @@ static int launch_depth_buffers(Ctx *ctx, const int *index, long long cap, const
     sp.large_cap = large_cap;
     // (the x grid strides over the list: its capacity can be several times its length)
     const dim3 sgrid((unsigned)std::min<long long>((cap + 255) / 256, 1024), (unsigned)ctx->V);
-    by_assoc(ctx, [&](auto left) {
-        hipLaunchKernelGGL(arvx::vis_splat_kernel<decltype(left)::value>, sgrid, dim3(256), 0, ctx->stream, sp);
-    });
-    ARVX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(arvx::vis_splat_large_kernel, dim3((unsigned)(4 * ncu)), dim3(256), 0, ctx->stream,
-                       (const arvx::SplatRect *)large, (const unsigned *)n_large, large_cap, zbuf, ctx->W,
-                       ctx->H, ctx->word_dev(Ctx::kVisNeed));
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(by_assoc(ctx, [&](auto left) {
+        return launch(ctx, arvx::vis_splat_kernel<decltype(left)::value>, sgrid, 256, sp);
+    }));
+    ARVX_TRY(launch(ctx, arvx::vis_splat_large_kernel, (unsigned)(4 * ncu), 256, large, n_large, large_cap,
+                    zbuf, ctx->W, ctx->H, ctx->word_dev(Ctx::kVisNeed)));
     *zbuf_out = zbuf;
     return ARVX_OK;
 }
@@ -2469,11 +2359,9 @@ static int launch_visible_vote(Ctx *ctx, const arvx::VoteParams &vp, float tol) 
     q.zbuf = zbuf;
     q.tol = tol;
     q.views = (int *)ctx->pool_vis_views.p;
-    by_assoc(ctx, [&](auto left) {
-        hipLaunchKernelGGL(arvx::vis_vote_kernel<decltype(left)::value>, dim3((unsigned)((cap + 255) / 256)),
-                           dim3(256), 0, ctx->stream, q);
+    return by_assoc(ctx, [&](auto left) {
+        return launch(ctx, arvx::vis_vote_kernel<decltype(left)::value>, blocks_for(cap), 256, q);
     });
-    return ARVX_OK;
 }
 
 int arvx_color_visible(arvx_ctx *ctx, int mode, float tolerance) {
@@ -2481,7 +2369,7 @@ int arvx_color_visible(arvx_ctx *ctx, int mode, float tolerance) {
     if (int rc = color_refusals(ctx, mode)) return rc;
     if (std::isnan(tolerance) || tolerance < 0.f)
         return fail(ARVX_ERR_INVALID, "tolerance %g: must be >= 0 (finite or +inf)", (double)tolerance);
-    if (ctx->z0 != 0 || ctx->z1 != ctx->Z)
+    if (!whole_grid(ctx))  // (stripes: refused above)
         return fail(ARVX_ERR_STATE, "arvx_color_visible needs a whole-grid context (the depth buffers "
                                     "need every surface voxel)");
     return color_pass(ctx, mode, true, tolerance);
@@ -2501,7 +2389,7 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
         return fail(ARVX_ERR_INVALID, "tolerance %g: must be >= 0 (finite or +inf)", (double)tolerance);
     if (min_views < 1) return fail(ARVX_ERR_INVALID, "min_views %d: must be >= 1", min_views);
     if (max_iterations < 1) return fail(ARVX_ERR_INVALID, "max_iterations %d: must be >= 1", max_iterations);
-    if (ctx->z0 != 0 || ctx->z1 != ctx->Z)
+    if (!whole_grid(ctx))  // (stripes: refused above)
         return fail(ARVX_ERR_STATE, "arvx_photo_carve needs a whole-grid context (the depth buffers "
                                     "need every surface voxel)");
     if (int frc = fills_without_colours(ctx)) return frc;
@@ -2510,17 +2398,13 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
     // closure_fills ending the lazy state)
     if (int mrc = need_rec(ctx)) return mrc;
     ctx->drop(Event::PhotoCarve);
-    const int XW = (ctx->X + 63) / 64;
     const int Zext = ctx->ze1 - ctx->ze0;
-    const size_t nw_ext = (size_t)XW * ctx->Y * Zext;
+    const size_t nw_ext = bit_words(bit_grid(ctx, Zext));
     // the removal plane, and the removal counter in front of the per-entry words
     ARVX_HIP(ctx->pool_photo_plane.reserve(nw_ext * sizeof(unsigned long long)));
     ARVX_HIP(ctx->pool_photo_rm.reserve(64 + 64 * sizeof(unsigned long long)));
     ARVX_HIP(hipMemsetAsync(ctx->pool_photo_rm.p, 0, sizeof(unsigned long long), ctx->stream));
     unsigned long long *d_plane = (unsigned long long *)ctx->pool_photo_plane.p;
-    arvx::CarveParams rp;
-    carve_geometry(ctx, rp);
-    rp.rec = ctx->rec();
     const double max_var = (double)max_std * (double)max_std;
     long long removed_k = 0, removed_all = 0;
     int it = 0;
@@ -2533,7 +2417,7 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
         }
         return ARVX_OK;
     };
-    auto launch = [&](const arvx::VoteParams &vp) -> int {
+    auto enqueue = [&](const arvx::VoteParams &vp) -> int {
         ctx->word(Ctx::kPhotoRemoved) = -1;  // (photo_plane_kernel leaves the iteration's removals there)
         const long long cap = vp.n;
         uint32_t *zbuf = nullptr;
@@ -2546,19 +2430,13 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
         q.min_views = min_views;
         q.removed = (unsigned long long *)ctx->pool_photo_rm.p;
         q.rm = (unsigned long long *)((uint8_t *)ctx->pool_photo_rm.p + 64);
-        by_assoc(ctx, [&](auto left) {
-            hipLaunchKernelGGL(arvx::photo_consist_kernel<decltype(left)::value>,
-                               dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, ctx->stream, q);
-        });
-        ARVX_HIP(hipGetLastError());
-        const unsigned gw = (unsigned)((nw_ext + 255) / 256);
-        hipLaunchKernelGGL(arvx::photo_plane_kernel, dim3(gw), dim3(256), 0, ctx->stream,
-                           (const arvx::SparseWord *)ctx->pool_col_rank.p, nw_ext, (const unsigned long long *)q.rm,
-                           cap, vp.n_dev, d_plane, q.removed, ctx->word_dev(Ctx::kPhotoRemoved));
-        ARVX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(arvx::rec_andnot_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, Zext,
-                           (const unsigned long long *)d_plane);
-        return ARVX_OK;
+        ARVX_TRY(by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::photo_consist_kernel<decltype(left)::value>, blocks_for(cap), 256, q);
+        }));
+        ARVX_TRY(launch(ctx, arvx::photo_plane_kernel, blocks_for(nw_ext), 256,
+                        (const arvx::SparseWord *)ctx->pool_col_rank.p, nw_ext, q.rm, cap, vp.n_dev, d_plane,
+                        q.removed, ctx->word_dev(Ctx::kPhotoRemoved)));
+        return records_apply(ctx, d_plane, Zext, false);
     };
     auto settle = [&]() -> int {
         if (ctx->word(Ctx::kVisNeed) >= 0) ctx->vis_large_need = ctx->word(Ctx::kVisNeed);
@@ -2570,7 +2448,7 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
     // attempt decides and removes nothing)
     while (it < max_iterations) {
         long long total = 0;
-        if (int rc = surface_list(ctx, reserve, launch, settle, &total)) return rc;
+        if (int rc = surface_list(ctx, reserve, enqueue, settle, &total)) return rc;
         ++it;
         removed_all += removed_k;
         if (removed_k == 0) break;
@@ -2587,7 +2465,7 @@ int arvx_photo_carve(arvx_ctx *ctx, float max_std, int min_views, float toleranc
 static int components_refusals(const Ctx *ctx, int connectivity) {
     if (connectivity != 6 && connectivity != 26)
         return fail(ARVX_ERR_INVALID, "connectivity %d: must be 6 or 26", connectivity);
-    if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
+    if (!whole_grid(ctx))
         return fail(ARVX_ERR_STATE, "the components need a whole-grid context (a component may cross "
                                     "any plane)");
     return ARVX_OK;
@@ -2605,8 +2483,8 @@ struct ComponentsRule {
 static int components_run(Ctx *ctx, int connectivity, const ComponentsRule *rule, long long *count,
                           long long *kept, long long *removed) {
     ctx->comp_ready = false;  // (the buffers of an earlier labelling are written over)
-    const arvx::BitGrid g{ctx->X, ctx->Y, ctx->Z, (ctx->X + 63) / 64};
-    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
+    const arvx::BitGrid g = bit_grid(ctx);
+    const size_t nwords = bit_words(g);
     ARVX_HIP(ctx->pool_comp_planes.reserve(3 * nwords * sizeof(unsigned long long)));
     ARVX_HIP(ctx->pool_comp_label.reserve(ctx->nvox * sizeof(int)));
     ARVX_HIP(ctx->pool_comp_rank.reserve(nwords * sizeof(arvx::SparseWord)));
@@ -2619,65 +2497,37 @@ static int components_run(Ctx *ctx, int connectivity, const ComponentsRule *rule
     constexpr size_t kEntry = 2 * sizeof(int) + 4;  // label, size, keep byte (padded)
     ListRoom lists[1] = {{Ctx::kComponents, list_cap(ctx->pool_comp_table, kEntry, 1024), 0}};
     long long cap = 0;
-    auto launch = [&]() -> int {
+    auto attempt = [&]() -> int {
         cap = lists[0].cap;
         ARVX_HIP(ctx->pool_comp_table.reserve((size_t)cap * kEntry));
         int *label = (int *)ctx->pool_comp_table.p, *size = label + cap;
         uint8_t *keep = (uint8_t *)(size + cap);
         if (int rc = launch_bit_pack(ctx, g, 0, 0, occ, nullptr)) return rc;
-        const unsigned gv = (unsigned)((ctx->nvox + 255) / 256), gw = (unsigned)((nwords + 255) / 256);
-        hipLaunchKernelGGL(arvx::comp_init_kernel, dim3(gv), dim3(256), 0, ctx->stream,
-                           (const unsigned long long *)occ, g, L);
-        ARVX_HIP(hipGetLastError());
-        if (connectivity == 6)
-            hipLaunchKernelGGL(arvx::comp_link_kernel<6>, dim3(gv), dim3(256), 0, ctx->stream,
-                               (const unsigned long long *)occ, g, L);
-        else
-            hipLaunchKernelGGL(arvx::comp_link_kernel<26>, dim3(gv), dim3(256), 0, ctx->stream,
-                               (const unsigned long long *)occ, g, L);
-        ARVX_HIP(hipGetLastError());
+        const unsigned gv = blocks_for(ctx->nvox), gw = blocks_for(nwords);
+        ARVX_TRY(launch(ctx, arvx::comp_init_kernel, gv, 256, occ, g, L));
+        ARVX_TRY(launch(ctx, connectivity == 6 ? arvx::comp_link_kernel<6> : arvx::comp_link_kernel<26>, gv, 256,
+                        occ, g, L));
         int *counts = nullptr;
         if (int rc = chunk_counts(ctx, nwords, &counts)) return rc;
-        hipLaunchKernelGGL(arvx::comp_roots_kernel, dim3(gw), dim3(256), 0, ctx->stream,
-                           (const unsigned long long *)occ, g, L, roots, counts);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::comp_roots_kernel, gw, 256, occ, g, L, roots, counts));
         ARVX_HIP(hipMemsetAsync(size, 0, (size_t)cap * sizeof(int), ctx->stream));
         ARVX_HIP(hipMemsetAsync(ctl, 0, 64, ctx->stream));
         const long long *d_total = nullptr;
         if (int rc = bit_compact(ctx, roots, nwords, g, cap, label, rank, Ctx::kComponents, &d_total)) return rc;
-        hipLaunchKernelGGL(arvx::comp_sizes_kernel, dim3(gw), dim3(256), 0, ctx->stream,
-                           (const unsigned long long *)occ, g, (const int *)L, (const arvx::SparseWord *)rank,
-                           d_total, cap, size);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::comp_sizes_kernel, gw, 256, occ, g, L, rank, d_total, cap, size));
         if (!rule) return ARVX_OK;
         ctx->word(Ctx::kCompKept) = ctx->word(Ctx::kCompRemoved) = -1;
-        const unsigned gk = (unsigned)((cap + 255) / 256);
-        if (rule->largest) {
-            hipLaunchKernelGGL(arvx::comp_best_kernel, dim3(gk), dim3(256), 0, ctx->stream, (const int *)label,
-                               (const int *)size, d_total, cap, ctl);
-            ARVX_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(arvx::comp_decide_kernel, dim3(gk), dim3(256), 0, ctx->stream, (const int *)label,
-                           (const int *)size, d_total, cap, rule->min_voxels, rule->largest, ctl, keep);
-        ARVX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(arvx::comp_remove_kernel, dim3(gw), dim3(256), 0, ctx->stream,
-                           (const unsigned long long *)occ, g, (const int *)L, (const arvx::SparseWord *)rank,
-                           (const uint8_t *)keep, d_total, cap, gone);
-        ARVX_HIP(hipGetLastError());
-        arvx::CarveParams rp;
-        carve_geometry(ctx, rp);
-        rp.rec = ctx->rec();
-        hipLaunchKernelGGL(arvx::rec_andnot_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, g.Z,
-                           (const unsigned long long *)gone);
-        ARVX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(arvx::comp_publish_kernel, dim3(1), dim3(1), 0, ctx->stream,
-                           (const unsigned long long *)ctl, ctx->word_dev(Ctx::kCompKept),
-                           ctx->word_dev(Ctx::kCompRemoved));
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        const unsigned gk = blocks_for(cap);
+        if (rule->largest) ARVX_TRY(launch(ctx, arvx::comp_best_kernel, gk, 256, label, size, d_total, cap, ctl));
+        ARVX_TRY(launch(ctx, arvx::comp_decide_kernel, gk, 256, label, size, d_total, cap, rule->min_voxels,
+                        rule->largest, ctl, keep));
+        ARVX_TRY(launch(ctx, arvx::comp_remove_kernel, gw, 256, occ, g, L, rank, keep, d_total, cap, gone));
+        ARVX_TRY(records_apply(ctx, gone, g.Z, false));
+        return launch(ctx, arvx::comp_publish_kernel, 1, 1, ctl, ctx->word_dev(Ctx::kCompKept),
+                      ctx->word_dev(Ctx::kCompRemoved));
     };
     // one synchronisation (two when the table outgrows its room: the truncated attempt removes nothing)
-    if (int rc = run_lists(ctx, lists, launch)) return rc;
+    if (int rc = run_lists(ctx, lists, attempt)) return rc;
     ctx->comp_count = lists[0].total;
     ctx->comp_cap = cap;
     ctx->comp_conn = connectivity;
@@ -2746,7 +2596,7 @@ int arvx_components_keep(arvx_ctx *ctx, int connectivity, int64_t min_voxels, un
 // ---- signed distance field and ball morphology (distance_kernels.h) -----------------------------
 
 static int distance_refusals(const Ctx *ctx) {
-    if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
+    if (!whole_grid(ctx))
         return fail(ARVX_ERR_STATE, "the distance field needs a whole-grid context (the nearest site may "
                                     "lie in any plane)");
     const long long x = ctx->X + 1ll, y = ctx->Y + 1ll, z = ctx->Z + 1ll;
@@ -2759,16 +2609,11 @@ static int distance_refusals(const Ctx *ctx) {
 // the buffers of arvx_distance and arvx_morph; planes[k]: the k-th of the three bit planes
 static int distance_reserve(Ctx *ctx, const arvx::BitGrid &g, unsigned long long *planes[3], unsigned *grid_y,
                             unsigned *grid_z) {
-    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
-    if (ctx->ncu <= 0) {
-        ctx->ncu = 256;
-        (void)hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
-        if (ctx->ncu <= 0) ctx->ncu = 256;
-    }
+    const size_t nwords = bit_words(g);
     // a column pass: a lane per column and sign, a workgroup per 256 lanes, at most 4 per compute unit
     // (8 are 9 % faster at 512^3 and take twice the stack memory: DESIGN.md 4.12)
     // -- the others' lanes are taken in turn --, each with a stack region of (len + 2) * 256 entries
-    const size_t most = (size_t)std::max(ctx->ncu, 1) * 4;
+    const size_t most = (size_t)std::max(compute_units(ctx), 1) * 4;
     *grid_y = (unsigned)std::min((2 * (size_t)g.X * g.Z + 255) / 256, most);
     *grid_z = (unsigned)std::min((2 * (size_t)g.X * g.Y + 255) / 256, most);
     const size_t stack = std::max((size_t)*grid_y * (g.Y + 2), (size_t)*grid_z * (g.Z + 2)) * 256 * sizeof(int2);
@@ -2783,22 +2628,16 @@ static int distance_reserve(Ctx *ctx, const arvx::BitGrid &g, unsigned long long
 // the three passes: the field of bit plane `occ` into pool_dist_field
 static int distance_run(Ctx *ctx, const arvx::BitGrid &g, const unsigned long long *occ, int border_empty,
                         unsigned grid_y, unsigned grid_z) {
-    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
     int *S = (int *)ctx->pool_dist_field.p;
     int2 *stack = (int2 *)ctx->pool_dist_stack.p;
     const size_t per_wg = 4 * (size_t)arvx::kDistWordsPerWave;
-    hipLaunchKernelGGL(arvx::dist_row_kernel, dim3((unsigned)((nwords + per_wg - 1) / per_wg)), dim3(256), 0,
-                       ctx->stream, occ, g, border_empty, S);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::dist_row_kernel, blocks_for(bit_words(g), per_wg), 256, occ, g, border_empty, S));
     // along y: column (x, z) starts at z * X * Y + x, its values X apart
-    hipLaunchKernelGGL(arvx::dist_column_kernel, dim3(grid_y), dim3(256), 0, ctx->stream, S,
-                       (long long)g.X * g.Z, g.Y, (long long)g.X, g.X, (long long)g.X * g.Y, border_empty, stack);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::dist_column_kernel, grid_y, 256, S, (long long)g.X * g.Z, g.Y, g.X, g.X,
+                    (long long)g.X * g.Y, border_empty, stack));
     // along z: column (x, y) starts at y * X + x, its values X * Y apart
-    hipLaunchKernelGGL(arvx::dist_column_kernel, dim3(grid_z), dim3(256), 0, ctx->stream, S,
-                       (long long)g.X * g.Y, g.Z, (long long)g.X * g.Y, g.X, (long long)g.X, border_empty, stack);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::dist_column_kernel, grid_z, 256, S, (long long)g.X * g.Y, g.Z,
+                  (long long)g.X * g.Y, g.X, g.X, border_empty, stack);
 }
 
 int arvx_distance(arvx_ctx *ctx, unsigned flags) {
@@ -2806,7 +2645,7 @@ int arvx_distance(arvx_ctx *ctx, unsigned flags) {
     if (flags & ~ARVX_DISTANCE_BORDER_OCCUPIED) return fail(ARVX_ERR_INVALID, "unknown flag bits 0x%x", flags);
     if (int rc = distance_refusals(ctx)) return rc;
     ctx->dist_ready = false;  // (the field of an earlier call is written over)
-    const arvx::BitGrid g{ctx->X, ctx->Y, ctx->Z, (ctx->X + 63) / 64};
+    const arvx::BitGrid g = bit_grid(ctx);
     unsigned long long *planes[3];
     unsigned gy = 0, gz = 0;
     if (int rc = distance_reserve(ctx, g, planes, &gy, &gz)) return rc;
@@ -2837,8 +2676,7 @@ int arvx_morph(arvx_ctx *ctx, int op, int64_t radius_sq, int64_t *removed, int64
     // every record exists before a bit is cleared or set (rec_andnot_bitgrid_kernel and
     // rec_or_bitgrid_kernel write records only): a lazy state ends here, as in arvx_components_keep
     if (int mrc = need_rec(ctx)) return mrc;
-    const arvx::BitGrid g{ctx->X, ctx->Y, ctx->Z, (ctx->X + 63) / 64};
-    const size_t nwords = (size_t)g.XW * g.Y * g.Z;
+    const arvx::BitGrid g = bit_grid(ctx);
     unsigned long long *planes[3];
     unsigned gy = 0, gz = 0;
     if (int rc = distance_reserve(ctx, g, planes, &gy, &gz)) return rc;
@@ -2848,34 +2686,23 @@ int arvx_morph(arvx_ctx *ctx, int op, int64_t radius_sq, int64_t *removed, int64
     const int *S = (const int *)ctx->pool_dist_field.p;
     const int R = (int)radius_sq;
     const size_t per_wg = 4 * (size_t)arvx::kDistWordsPerWave;  // (words of a dist_threshold_kernel workgroup)
-    const unsigned gt = (unsigned)((nwords + per_wg - 1) / per_wg), gw = (unsigned)((nwords + 255) / 256);
+    const unsigned gt = blocks_for(bit_words(g), per_wg);
     ARVX_HIP(hipMemsetAsync(d_count, 0, sizeof *d_count, ctx->stream));
     if (int rc = launch_bit_pack(ctx, g, 0, 0, occ, nullptr)) return rc;
     // the field of the state; for OPEN and CLOSE the first half's set as a plane, and the field of that
     if (int rc = distance_run(ctx, g, occ, 1, gy, gz)) return rc;
     if (op == ARVX_MORPH_OPEN || op == ARVX_MORPH_CLOSE) {
-        hipLaunchKernelGGL(arvx::dist_threshold_kernel, dim3(gt), dim3(256), 0, ctx->stream, S, g, R, grows ? 1 : 0,
-                           0, (const unsigned long long *)occ, mid, d_count);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::dist_threshold_kernel, gt, 256, S, g, R, grows ? 1 : 0, 0, occ, mid,
+                        d_count));
         // (CLOSE: the erosion of the dilated set leaves the grid's edge alone)
         if (int rc = distance_run(ctx, g, mid, grows ? 0 : 1, gy, gz)) return rc;
     }
     // what leaves (ERODE; OPEN: after the dilation of the eroded set) or joins (DILATE; CLOSE: after
     // the erosion of the dilated set) the model, against the occupancy the call started from
     const int second_grows = op == ARVX_MORPH_DILATE || op == ARVX_MORPH_OPEN;
-    hipLaunchKernelGGL(arvx::dist_threshold_kernel, dim3(gt), dim3(256), 0, ctx->stream, S, g, R, second_grows,
-                       grows ? 2 : 1, (const unsigned long long *)occ, change, d_count);
-    ARVX_HIP(hipGetLastError());
-    arvx::CarveParams rp;
-    carve_geometry(ctx, rp);
-    rp.rec = ctx->rec();
-    if (grows)
-        hipLaunchKernelGGL(arvx::rec_or_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, g.Z,
-                           (const unsigned long long *)change);
-    else
-        hipLaunchKernelGGL(arvx::rec_andnot_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, g.Z,
-                           (const unsigned long long *)change);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::dist_threshold_kernel, gt, 256, S, g, R, second_grows, grows ? 2 : 1, occ,
+                    change, d_count));
+    ARVX_TRY(records_apply(ctx, change, g.Z, grows));
     ctx->word(Ctx::kMorphChanged) = -1;
     ARVX_HIP(hipMemcpyAsync(&ctx->word(Ctx::kMorphChanged), d_count, sizeof(long long), hipMemcpyDeviceToHost,
                             ctx->stream));
@@ -2912,12 +2739,10 @@ int arvx_color_samples(arvx_ctx *ctx, int64_t n, const int64_t *index, int views
                             ctx->stream));
     arvx::VoteParams vp = vote_params(ctx, ctx->z0);  // (indices run over the owned planes)
     vp.n = n;
-    const unsigned grid = (unsigned)((total + 255) / 256);
-    by_assoc(ctx, [&](auto left) {
-        hipLaunchKernelGGL(arvx::color_samples_kernel<decltype(left)::value>, dim3(grid), dim3(256), 0,
-                           ctx->stream, vp, d_idx, d_out);
-    });
-    ARVX_HIP(hipGetLastError());
+    const unsigned grid = blocks_for(total);
+    ARVX_TRY(by_assoc(ctx, [&](auto left) {
+        return launch(ctx, arvx::color_samples_kernel<decltype(left)::value>, grid, 256, vp, d_idx, d_out);
+    }));
     ARVX_HIP(hipMemcpyAsync(out, d_out, total * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);
     return ARVX_OK;
@@ -3052,9 +2877,7 @@ int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen) {
     if (int frc = fills_without_colours(ctx)) return frc;
     if (int mrc = need_rec(ctx)) return mrc;
     if (!rgba) return fail(ARVX_ERR_INVALID, "null rgba");
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
+    arvx::CarveParams g = record_params(ctx);
     const int zown = ctx->z0 - ctx->ze0;
     if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
         return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d",
@@ -3063,12 +2886,11 @@ int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen) {
     const size_t nchunk = std::min(chunk, ctx->nvox);
     float4 *d_out = nullptr;
     ARVX_HIP(hipMalloc(&d_out, nchunk * sizeof(float4)));
-    int rc = ARVX_OK;
-    for (size_t i0 = 0; i0 < ctx->nvox && rc == ARVX_OK; i0 += chunk) {
+    auto export_chunk = [&](size_t i0) -> int {  // (returns early on a failure: the caller frees d_out)
         const size_t n = std::min(chunk, ctx->nvox - i0);
         const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, 16384);
-        hipLaunchKernelGGL(arvx::export_fill_kernel, dim3(grid), dim3(256), 0, ctx->stream, g,
-                           zown, i0, n, paint_plane(ctx), d_out, apply_unseen);
+        ARVX_TRY(launch(ctx, arvx::export_fill_kernel, grid, 256, g, zown, i0, n, paint_plane(ctx), d_out,
+                        apply_unseen));
         // entries of an ascending list (numbered over the context's planes) in owned voxels
         // [i0, i0 + n)
         const long long own_base = (long long)ctx->X * ctx->Y * zown;
@@ -3083,28 +2905,24 @@ int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen) {
             long long first, last;
             list_range(ctx->h_surf_index, first, last);
             if (last > first)
-                hipLaunchKernelGGL(arvx::export_scatter_kernel,
-                                   dim3((unsigned)((last - first + 255) / 256)), dim3(256), 0,
-                                   ctx->stream, ctx->d_surf_index, ctx->d_surf_rgba, first, last,
-                                   g, zown, paint_plane(ctx), i0, d_out, apply_unseen);
+                ARVX_TRY(launch(ctx, arvx::export_scatter_kernel, blocks_for(last - first), 256,
+                                ctx->d_surf_index, ctx->d_surf_rgba, first, last, g, zown, paint_plane(ctx),
+                                i0, d_out, apply_unseen));
         }
         if (ctx->closure_ready && ctx->clo_count > 0) {
             if (int rc = clo_host(ctx)) return rc;
             long long first, last;
             list_range(ctx->h_clo_index, first, last);
             if (last > first)
-                hipLaunchKernelGGL(arvx::export_overlay_kernel,
-                                   dim3((unsigned)((last - first + 255) / 256)), dim3(256), 0,
-                                   ctx->stream, ctx->d_clo_index, (const float4 *)ctx->d_clo_rgba,
-                                   first, last, (size_t)own_base, i0, d_out);
+                ARVX_TRY(launch(ctx, arvx::export_overlay_kernel, blocks_for(last - first), 256, ctx->d_clo_index,
+                                (const float4 *)ctx->d_clo_rgba, first, last, own_base, i0, d_out));
         }
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(rgba + 4 * i0, d_out, n * sizeof(float4), hipMemcpyDeviceToHost,
-                               ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = arvx::fail_hip(e, "export chunk", __FILE__, __LINE__);
-    }
+        ARVX_HIP(hipMemcpyAsync(rgba + 4 * i0, d_out, n * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
+        ARVX_HIP(hipStreamSynchronize(ctx->stream));
+        return ARVX_OK;
+    };
+    int rc = ARVX_OK;
+    for (size_t i0 = 0; i0 < ctx->nvox && rc == ARVX_OK; i0 += chunk) rc = export_chunk(i0);
     (void)hipFree(d_out);
     return rc;
 }
@@ -3115,22 +2933,18 @@ int arvx_selftest_divide(arvx_ctx *ctx, int64_t n, const float *a0, const float 
     if (n < 1 || !a0 || !a1 || !b || !out) return fail(ARVX_ERR_INVALID, "bad argument");
     float *d = nullptr;
     ARVX_HIP(hipMalloc(&d, (size_t)n * 7 * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(d, a0, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + n, a1, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d + 2 * n, b, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(arvx::selftest_divide_kernel, dim3((unsigned)((n + 255) / 256)),
-                           dim3(256), 0, ctx->stream, d, d + n, d + 2 * n, (size_t)n, d + 3 * n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out, d + 3 * n, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    auto run = [&]() -> int {  // (returns early on a failure: d is freed below)
+        ARVX_HIP(hipMemcpyAsync(d, a0, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        ARVX_HIP(hipMemcpyAsync(d + n, a1, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        ARVX_HIP(hipMemcpyAsync(d + 2 * n, b, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+        ARVX_TRY(launch(ctx, arvx::selftest_divide_kernel, blocks_for(n), 256, d, d + n, d + 2 * n, n, d + 3 * n));
+        ARVX_HIP(hipMemcpyAsync(out, d + 3 * n, (size_t)n * 16, hipMemcpyDeviceToHost, ctx->stream));
+        ARVX_HIP(hipStreamSynchronize(ctx->stream));
+        return ARVX_OK;
+    };
+    const int rc = run();
     (void)hipFree(d);
-    if (e != hipSuccess) return arvx::fail_hip(e, "selftest_divide", __FILE__, __LINE__);
-    return ARVX_OK;
+    return rc;
 }
 
 int arvx_selftest_project(arvx_ctx *ctx, int64_t n, const float M[12], float voxel_size,
@@ -3139,11 +2953,11 @@ int arvx_selftest_project(arvx_ctx *ctx, int64_t n, const float M[12], float vox
     if (!M) return fail(ARVX_ERR_INVALID, "null M");
     arvx::SelftestMatrix m;
     memcpy(m.m, M, sizeof m.m);
-    const unsigned grid = (unsigned)((n + 255) / 256);
+    const unsigned grid = blocks_for(n);
     return selftest_xyz(ctx, n, xyz, (size_t)n * 5, rows_uv, [&](int *d_xyz, float *d_out) {
-        by_assoc(ctx, [&](auto left) {
-            hipLaunchKernelGGL(arvx::selftest_project_kernel<decltype(left)::value>, dim3(grid), dim3(256), 0,
-                               ctx->stream, m, voxel_size, d_xyz, (long long)n, d_out, d_out + 3 * n);
+        return by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::selftest_project_kernel<decltype(left)::value>, grid, 256, m, voxel_size,
+                          d_xyz, n, d_out, d_out + 3 * n);
         });
     });
 }
@@ -3156,8 +2970,7 @@ int arvx_selftest_depth(arvx_ctx *ctx, int64_t n, const float campos[3], float v
     memset(&m, 0, sizeof m);
     memcpy(m.m, campos, 3 * sizeof(float));
     return selftest_xyz(ctx, n, xyz, (size_t)n, depth, [&](int *d_xyz, float *d_out) {
-        hipLaunchKernelGGL(arvx::selftest_depth_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256),
-                           0, ctx->stream, m, voxel_size, d_xyz, (long long)n, d_out);
+        return launch(ctx, arvx::selftest_depth_kernel, blocks_for(n), 256, m, voxel_size, d_xyz, n, d_out);
     });
 }
 
@@ -3204,9 +3017,7 @@ int arvx_selftest_round(arvx_ctx *ctx, int64_t *mismatches) {
     const unsigned ranges[2][2] = {{0x00000000u, 0x4B800000u}, {0x80000000u, 0xBEFFFFFFu}};
     for (const auto &r : ranges) {
         const unsigned long long n = (unsigned long long)r[1] - r[0] + 1;
-        hipLaunchKernelGGL(arvx::selftest_round_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256),
-                           0, ctx->stream, r[0], r[1], d_bad);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::selftest_round_kernel, blocks_for(n), 256, r[0], r[1], d_bad));
     }
     unsigned long long bad = 0;
     ARVX_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
@@ -3238,10 +3049,9 @@ int arvx_selftest_rect_cache(arvx_ctx *ctx, int64_t *mismatches) {
     unsigned long long *d_bad = (unsigned long long *)ctx->pool_scratch.p;
     ARVX_HIP(hipMemsetAsync(d_bad, 0, sizeof *d_bad, ctx->stream));
     const size_t n = rect_entries(ctx, p);
-    hipLaunchKernelGGL(arvx::rect_cache_block_kernel<true>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 65536)),
-                       dim3(256), 0, ctx->stream, p, (uint32_t *)ctx->pool_rect.p, n, (long long *)nullptr,
-                       d_bad);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::rect_cache_block_kernel<true>,
+                    (unsigned)std::min<size_t>((n + 255) / 256, 65536), 256, p, (uint32_t *)ctx->pool_rect.p,
+                    n, nullptr, d_bad));
     unsigned long long bad = 0;
     ARVX_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
     ARVX_SYNC(ctx);
@@ -3295,17 +3105,14 @@ int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const flo
         ARVX_HIP(ctx->pool_scratch.reserve((size_t)n * 3 * sizeof(float) + 64));
         ARVX_HIP(hipMemcpyAsync(ctx->pool_scratch.p, rgb, (size_t)n * 3 * sizeof(float),
                                 hipMemcpyHostToDevice, ctx->stream));
-        hipLaunchKernelGGL(arvx::rgb_to_rgba_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                           ctx->stream, (const float *)ctx->pool_scratch.p, (long long)n,
-                           ctx->d_surf_rgba);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::rgb_to_rgba_kernel, blocks_for(n), 256, (const float *)ctx->pool_scratch.p, n,
+                        ctx->d_surf_rgba));
         ARVX_SYNC(ctx);  // (the scratch buffer is reused below)
         ARVX_HIP(hipMemsetAsync(ctx->d_surf_depth, 0, (size_t)n * sizeof(float), ctx->stream));
         ARVX_HIP(hipMemsetAsync(ctx->d_surf_has, 1, (size_t)n, ctx->stream));
         // the list's plane + ranks (what arvx_color leaves behind)
-        const int XW = (ctx->X + 63) / 64;
-        const arvx::BitGrid gown{ctx->X, ctx->Y, ctx->ze1 - ctx->ze0, XW};  // the context's planes
-        const size_t nw = (size_t)XW * gown.Y * gown.Z;
+        const arvx::BitGrid gown = bit_grid(ctx, ctx->ze1 - ctx->ze0);  // the context's planes
+        const size_t nw = bit_words(gown);
         const int nblk = (int)((nw + arvx::kBitBlock - 1) / arvx::kBitBlock);
         ARVX_HIP(ctx->pool_col_bits.reserve(nw * sizeof(unsigned long long)));
         ARVX_HIP(ctx->pool_col_rank.reserve(nw * sizeof(arvx::SparseWord)));
@@ -3315,9 +3122,7 @@ int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const flo
         long long *d_off = (long long *)ctx->pool_scratch.p;
         int *d_cnt = (int *)(d_off + nblk + 1);
         ARVX_HIP(hipMemsetAsync(bits, 0, nw * sizeof(unsigned long long), ctx->stream));
-        hipLaunchKernelGGL(arvx::bits_from_index_kernel, dim3((unsigned)((n + 255) / 256)),
-                           dim3(256), 0, ctx->stream, ctx->d_surf_index, (long long)n, gown, bits);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::bits_from_index_kernel, blocks_for(n), 256, ctx->d_surf_index, n, gown, bits));
         long long total = 0;
         if (int rc = bit_compact_count(ctx, bits, nw, d_cnt, d_off, &total)) return rc;
         if (int rc = bit_compact_write(ctx, bits, nw, gown, d_off, nullptr,
@@ -3362,11 +3167,9 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     if (int mrc = need_rec(ctx, true)) return mrc;
     // filled = dilate(occupied, box of radius r) and not occupied, on bit planes over the
     // context's planes
-    const int XW = (ctx->X + 63) / 64;
     const int Zext = ctx->ze1 - ctx->ze0;
-    const arvx::BitGrid g{ctx->X, ctx->Y, Zext, XW};
-    const size_t row_words = (size_t)XW * g.Y;
-    const size_t nwords = row_words * g.Z;
+    const arvx::BitGrid g = bit_grid(ctx, Zext);
+    const size_t nwords = bit_words(g);
     const bool paints = apply_unseen || ctx->paint_valid;  // somebody is UNSEEN_COLOR
     ARVX_HIP(ctx->pool_scratch.reserve(3 * nwords * sizeof(unsigned long long) + 64));
     ARVX_HIP(ctx->pool_clo_bits.reserve(nwords * sizeof(unsigned long long)));
@@ -3374,7 +3177,7 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     unsigned long long *d_occ = (unsigned long long *)ctx->pool_scratch.p;
     unsigned long long *d_unseen = d_occ + nwords, *d_b = d_unseen + nwords;
     unsigned long long *d_fill = (unsigned long long *)ctx->pool_clo_bits.p;
-    const unsigned gw = (unsigned)((nwords + 255) / 256);
+    const unsigned gw = blocks_for(nwords);
     if (ctx->planes_seq == ctx->state_seq && !ctx->paint_valid && ctx->planes_words == nwords &&
         ctx->pool_state_planes.cap >= 2 * nwords * 8) {
         // the colour pass's planes are the state's (nothing but handleUnseen ran since): what the
@@ -3383,24 +3186,20 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
         const unsigned long long *p_occ = (const unsigned long long *)ctx->pool_state_planes.p;
         const unsigned long long *p_nseen = p_occ + nwords;
         const bool merge = ctx->planes_unseen || apply_unseen;
-        hipLaunchKernelGGL(arvx::bit_dilate_xy_kernel, dim3(gw), dim3(256), 0, ctx->stream, p_occ,
-                           merge ? p_nseen : (const unsigned long long *)nullptr, g, radius, d_b, d_occ);
+        ARVX_TRY(launch(ctx, arvx::bit_dilate_xy_kernel, gw, 256, p_occ, merge ? p_nseen : nullptr, g, radius, d_b,
+                        d_occ));
         if (!merge) d_occ = const_cast<unsigned long long *>(p_occ);
         d_unseen = const_cast<unsigned long long *>(p_nseen);  // (read only where `paints`)
     } else {
         if (int rc = launch_bit_pack(ctx, g, 1, apply_unseen ? 1 : 0, d_occ, paints ? d_unseen : nullptr))
             return rc;
-        hipLaunchKernelGGL(arvx::bit_dilate_xy_kernel, dim3(gw), dim3(256), 0, ctx->stream,
-                           (const unsigned long long *)d_occ, (const unsigned long long *)nullptr, g, radius, d_b,
-                           (unsigned long long *)nullptr);
+        ARVX_TRY(launch(ctx, arvx::bit_dilate_xy_kernel, gw, 256, d_occ, nullptr, g, radius, d_b, nullptr));
     }
     // (halo planes outside [f_lo, f_hi): their boxes reach planes this context knows nothing
     // about -- not filled here, their owners do it: zeros)
     int *d_counts = nullptr;
     if (int rc = chunk_counts(ctx, nwords, &d_counts)) return rc;
-    arvx::CarveParams rp;
-    carve_geometry(ctx, rp);
-    rp.rec = ctx->rec();
+    arvx::CarveParams rp = record_params(ctx);
     // Coarse tiles that exist only as their code: the few that receive a voxel are marked by the fill
     // plane's producer and written out by rec_or_bitgrid_lazy_kernel, the others stay codes (grids
     // whose rows and planes fill whole tiles; else every tile is written out first, as in round 4)
@@ -3409,10 +3208,8 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     const bool lazy_or = ctx->form == Form::Lazy && ctx->Y % 8 == 0 && Zext % 8 == 0;
     arvx::CoarseMark mark{lazy_or ? (uint8_t *)ctx->pool_ccode.p : nullptr, rp.coarseX, rp.coarseY, rp.cyShift,
                           rp.czShift};
-    hipLaunchKernelGGL(arvx::bit_dilate_z_count_kernel, dim3(gw), dim3(256), 0, ctx->stream, d_b, g,
-                       radius, (const unsigned long long *)d_occ, f_lo - ctx->ze0, f_hi - ctx->ze0, d_fill,
-                       d_counts, mark);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::bit_dilate_z_count_kernel, gw, 256, d_b, g, radius, d_occ, f_lo - ctx->ze0,
+                    f_hi - ctx->ze0, d_fill, d_counts, mark));
     // The filled voxels are occupied from now on (their w is count / count = 1; the fill kernel reads
     // the occupancy from the bit planes, not from the records).  Launched HERE, right behind the
     // producer that marked the tiles: from this launch on the marks and the records agree, whatever
@@ -3422,12 +3219,10 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
     ctx->drop(Event::Closure);  // (the state changes here: tiles an earlier carve emptied may be occupied again)
     ctx->closure_fills = true;
     if (lazy_or)
-        hipLaunchKernelGGL(arvx::rec_or_bitgrid_lazy_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, g.Z,
-                           (const unsigned long long *)d_fill, (const uint8_t *)ctx->pool_ccode.p);
+        ARVX_TRY(launch(ctx, arvx::rec_or_bitgrid_lazy_kernel, gw, 256, rp, g.Z, d_fill,
+                        (const uint8_t *)ctx->pool_ccode.p));
     else
-        hipLaunchKernelGGL(arvx::rec_or_bitgrid_kernel, dim3(gw), dim3(256), 0, ctx->stream, rp, 0, g.Z,
-                           d_fill);
-    ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::rec_or_bitgrid_kernel, gw, 256, rp, 0, g.Z, d_fill));
     // The list of the filled voxels: compacted and coloured in buffers sized before its length is known (run_lists).
     const double v = (double)nwords * 64.0;
     ListRoom lists[] = {{Ctx::kClosure, list_cap(ctx->pool_clo_index, sizeof(int), first_list_cap(v, v)), 0}};
@@ -3448,16 +3243,8 @@ int arvx_closure(arvx_ctx *ctx, int kernel_size, int apply_unseen) {
         cp.radius = radius;
         cp.col = colour_list(ctx);
         cp.col_rgba = ctx->d_surf_rgba;
-        if (radius == 1)
-            hipLaunchKernelGGL(arvx::closure_fill_kernel<true>, dim3((unsigned)((cap + 255) / 256)),
-                               dim3(256), 0, ctx->stream, cp, ctx->d_clo_index, cap, d_total,
-                               (float4 *)ctx->d_clo_rgba);
-        else
-            hipLaunchKernelGGL(arvx::closure_fill_kernel<false>, dim3((unsigned)((cap + 255) / 256)),
-                               dim3(256), 0, ctx->stream, cp, ctx->d_clo_index, cap, d_total,
-                               (float4 *)ctx->d_clo_rgba);
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        return launch(ctx, radius == 1 ? arvx::closure_fill_kernel<true> : arvx::closure_fill_kernel<false>,
+                      blocks_for(cap), 256, cp, ctx->d_clo_index, cap, d_total, (float4 *)ctx->d_clo_rgba);
     };
     if (int rc = run_lists(ctx, lists, attempt)) return rc;
     const long long total = lists[0].total;
@@ -3545,26 +3332,15 @@ static int mc_cells_launch(Ctx *ctx, long long cap, const long long **d_total) {
     mp.zbits = (unsigned long long *)ctx->pool_scratch.p;
     int *d_off = (int *)(mp.zbits + nzw);  // ncol column offsets
     int *d_cnt = d_off + ncol + 1;
-    {
-        arvx::CarveParams g;
-        carve_geometry(ctx, g);
-        g.rec = ctx->rec();
-        hipLaunchKernelGGL(arvx::mc_zpack_rec_kernel,
-                           dim3((unsigned)((size_t)g.tilesX * g.tilesY * mp.ZW)), dim3(256), 0,
-                           ctx->stream, g, mp);
-        ARVX_HIP(hipGetLastError());
-    }
-    const unsigned nblk = (unsigned)((ncol + 255) / 256);
-    hipLaunchKernelGGL(arvx::mc_count_kernel, dim3(nblk), dim3(256), 0, ctx->stream, mp, d_cnt);
-    ARVX_HIP(hipGetLastError());
+    const arvx::CarveParams g = record_params(ctx);
+    ARVX_TRY(launch(ctx, arvx::mc_zpack_rec_kernel, (unsigned)((size_t)g.tilesX * g.tilesY * mp.ZW), 256, g, mp));
+    const unsigned nblk = blocks_for(ncol);
+    ARVX_TRY(launch(ctx, arvx::mc_count_kernel, nblk, 256, mp, d_cnt));
     // the columns' offsets in the list: one launch
     if (int rc = scan_counts(ctx, d_cnt, nullptr, ncol, nullptr, d_off, Ctx::kCells, d_total)) return rc;
     ARVX_HIP(ctx->pool_mc_cells.reserve((size_t)cap * sizeof(int4)));
     ctx->d_mc_cells = (void *)ctx->pool_mc_cells.p;
-    hipLaunchKernelGGL(arvx::mc_write_kernel, dim3(nblk), dim3(256), 0, ctx->stream, mp, d_off, cap,
-                       (int4 *)ctx->d_mc_cells);
-    ARVX_HIP(hipGetLastError());
-    return ARVX_OK;
+    return launch(ctx, arvx::mc_write_kernel, nblk, 256, mp, d_off, cap, (int4 *)ctx->d_mc_cells);
 }
 // room for the cell list before its length is known: what the last list needed, or a surface's share
 static long long mc_cells_cap(const Ctx *ctx) {
@@ -3575,8 +3351,7 @@ static long long mc_cells_cap(const Ctx *ctx) {
 // what the two meshes' kernels read of the state and its colours
 static arvx::McMeshParams mesh_params(const Ctx *ctx, int apply_unseen) {
     arvx::McMeshParams mp;
-    carve_geometry(ctx, mp.g);
-    mp.g.rec = ctx->rec();
+    mp.g = record_params(ctx);
     mp.paint = paint_plane(ctx);
     mp.apply_unseen = apply_unseen ? 1 : 0;
     mp.col = colour_list(ctx);
@@ -3660,11 +3435,9 @@ int arvx_mc_mesh(arvx_ctx *ctx, int apply_unseen, int64_t *triangles) {
         const long long *d_ntris = nullptr;
         if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, Ctx::kTris, &d_ntris))
             return rc;
-        hipLaunchKernelGGL(arvx::mc_mesh_kernel, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0,
-                           ctx->stream, mp, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, tcap, d_off,
-                           (float *)ctx->pool_mesh_verts.p, (unsigned *)ctx->pool_mesh_rgb.p);
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        return launch(ctx, arvx::mc_mesh_kernel, blocks_for(ccap), 256, mp, (const int4 *)ctx->d_mc_cells, ccap,
+                      d_ncells, tcap, d_off, (float *)ctx->pool_mesh_verts.p,
+                      (unsigned *)ctx->pool_mesh_rgb.p);
     };
     if (int rc = run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }))
         return rc;
@@ -3711,7 +3484,7 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     ARVX_CHECK_CTX(ctx);
     if (int frc = fills_without_colours(ctx)) return frc;
     if (!vertices || !triangles) return fail(ARVX_ERR_INVALID, "null argument");
-    if (ctx->stripe_world > 1 || ctx->z0 != 0 || ctx->z1 != ctx->Z)
+    if (!whole_grid(ctx))
         return fail(ARVX_ERR_STATE, "arvx_mc_mesh_welded needs a whole-grid context (vertex indices "
                                     "are ranks in the whole grid)");
     if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
@@ -3726,9 +3499,8 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     *vertices = *triangles = 0;
     // the vertex plane: occupied voxels with an empty 6-neighbour, in the occupancy the cell walk
     // reads (the records: closure fills included); its chunk counts come with it
-    const int XW = (ctx->X + 63) / 64;
-    const arvx::BitGrid g{ctx->X, ctx->Y, ctx->Z, XW};
-    const size_t nw = (size_t)XW * ctx->Y * ctx->Z;
+    const arvx::BitGrid g = bit_grid(ctx);
+    const size_t nw = bit_words(g);
     ARVX_HIP(ctx->pool_weld_planes.reserve(2 * nw * sizeof(unsigned long long)));
     ARVX_HIP(ctx->pool_weld_rank.reserve(nw * sizeof(arvx::SparseWord)));
     unsigned long long *d_occ = (unsigned long long *)ctx->pool_weld_planes.p, *d_vtx = d_occ + nw;
@@ -3736,9 +3508,8 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     if (int rc = launch_bit_pack(ctx, g, 0, 0, d_occ, nullptr)) return rc;
     int *d_counts = nullptr;
     if (int rc = chunk_counts(ctx, nw, &d_counts)) return rc;
-    hipLaunchKernelGGL(arvx::bit_surface_count_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0,
-                       ctx->stream, d_occ, g, 0, ctx->Z, d_vtx, d_counts);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::bit_surface_count_kernel, blocks_for(nw), 256, d_occ, g, 0, ctx->Z, d_vtx,
+                    d_counts));
     // room: what the last welded mesh needed, or a surface's share of the voxels
     const long long cells = mc_cells_cap(ctx);
     ListRoom lists[] = {{Ctx::kCells, cells, 0},
@@ -3761,15 +3532,12 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
         int *d_off = (int *)ctx->pool_mesh_off.p;
         if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, Ctx::kTris, nullptr))
             return rc;
-        hipLaunchKernelGGL(arvx::mc_weld_tri_kernel, dim3((unsigned)((ccap + 255) / 256)), dim3(256), 0,
-                           ctx->stream, mp, arvx::SparseList{d_rank}, (const int4 *)ctx->d_mc_cells, ccap,
-                           d_ncells, tcap, d_off, (unsigned *)ctx->pool_weld_faces.p);
-        ARVX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(arvx::mc_weld_vertex_kernel, dim3((unsigned)((vcap + 255) / 256)), dim3(256), 0,
-                           ctx->stream, mp, (const int *)ctx->pool_weld_index.p, vcap, d_nverts,
-                           (float *)ctx->pool_weld_verts.p, (float *)ctx->pool_weld_rgb.p);
-        ARVX_HIP(hipGetLastError());
-        return ARVX_OK;
+        ARVX_TRY(launch(ctx, arvx::mc_weld_tri_kernel, blocks_for(ccap), 256, mp, arvx::SparseList{d_rank},
+                        (const int4 *)ctx->d_mc_cells, ccap, d_ncells, tcap, d_off,
+                        (unsigned *)ctx->pool_weld_faces.p));
+        return launch(ctx, arvx::mc_weld_vertex_kernel, blocks_for(vcap), 256, mp,
+                      (const int *)ctx->pool_weld_index.p, vcap, d_nverts, (float *)ctx->pool_weld_verts.p,
+                      (float *)ctx->pool_weld_rgb.p);
     };
     if (int rc = run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }))
         return rc;
@@ -3812,7 +3580,7 @@ int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, f
 static int smooth_csr(Ctx *ctx) {
     const long long V = ctx->weld_verts, T = ctx->weld_tris;
     const long long ncap = std::min(26 * V, 6 * T), icap = 3 * T;
-    const unsigned blocks_v = (unsigned)((V + 1 + 255) / 256), blocks_t = (unsigned)((T + 255) / 256);
+    const unsigned blocks_v = blocks_for(V + 1), blocks_t = blocks_for(T);
     // masks (V) | incidence counts (V + 1) | neighbour counts (V + 1) | their two offsets (V + 1 each)
     ARVX_HIP(ctx->pool_smooth_csr.reserve((size_t)(5 * V + 4) * sizeof(int)));
     ARVX_HIP(ctx->pool_smooth_nbr.reserve((size_t)std::max(ncap, 1ll) * sizeof(unsigned)));
@@ -3824,29 +3592,20 @@ static int smooth_csr(Ctx *ctx) {
     const int *index = (const int *)ctx->pool_weld_index.p;
     ARVX_HIP(hipMemsetAsync(masks, 0, (size_t)(2 * V + 1) * sizeof(int), ctx->stream));  // masks, icount
     if (T > 0) {
-        hipLaunchKernelGGL(arvx::mc_smooth_adjacency_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T,
-                           V, index, ctx->X, ctx->Y, masks, icount);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::mc_smooth_adjacency_kernel, blocks_t, 256, faces, T, V, index, ctx->X,
+                        ctx->Y, masks, icount));
     }
-    hipLaunchKernelGGL(arvx::mc_smooth_degree_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
-                       (const unsigned *)masks, V, ncount);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::mc_smooth_degree_kernel, blocks_v, 256, masks, V, ncount));
     // (a total no call reads)
     if (int rc = scan_counts(ctx, ncount, nullptr, V + 1, nullptr, noff, Ctx::kSmoothScan, nullptr)) return rc;
     if (int rc = scan_counts(ctx, icount, nullptr, V + 1, nullptr, ioff, Ctx::kSmoothScan, nullptr)) return rc;
-    hipLaunchKernelGGL(arvx::mc_smooth_neighbours_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
-                       (const unsigned *)masks, V, index, ctx->X, ctx->Y,
-                       arvx::SparseList{(const arvx::SparseWord *)ctx->pool_weld_rank.p}, (const int *)noff,
-                       ncap, nbr);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::mc_smooth_neighbours_kernel, blocks_v, 256, masks, V, index, ctx->X, ctx->Y,
+                    arvx::SparseList{(const arvx::SparseWord *)ctx->pool_weld_rank.p}, noff, ncap, nbr));
     if (T > 0) {
-        hipLaunchKernelGGL(arvx::mc_smooth_incidence_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T,
-                           V, icount, (const int *)ioff, icap, inc);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::mc_smooth_incidence_kernel, blocks_t, 256, faces, T, V, icount, ioff, icap,
+                        inc));
     }
-    hipLaunchKernelGGL(arvx::mc_smooth_sort_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
-                       (const int *)ioff, V, icap, inc);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::mc_smooth_sort_kernel, blocks_v, 256, ioff, V, icap, inc));
     ctx->smooth_csr_ready = true;
     return ARVX_OK;
 }
@@ -3868,7 +3627,7 @@ int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu) {
     const long long ncap = std::min(26 * V, 6 * T), icap = 3 * T;
     const unsigned *faces = (const unsigned *)ctx->pool_weld_faces.p;
     int *noff = (int *)ctx->pool_smooth_csr.p + V + 2 * (V + 1), *ioff = noff + V + 1;
-    const unsigned blocks_v = (unsigned)((V + 255) / 256), blocks_t = (unsigned)((T + 255) / 256);
+    const unsigned blocks_v = blocks_for(V), blocks_t = blocks_for(T);
     // the steps: welded positions -> buffer 1 -> buffer 2 -> buffer 1 ...
     ARVX_HIP(ctx->pool_smooth_verts.reserve((size_t)6 * V * sizeof(float)));
     float *buf[3] = {(float *)ctx->pool_weld_verts.p, (float *)ctx->pool_smooth_verts.p,
@@ -3876,24 +3635,20 @@ int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu) {
     int q = 0;
     for (int s = 0; s < 2 * iterations; ++s) {
         const int next = q == 1 ? 2 : 1;
-        hipLaunchKernelGGL(arvx::mc_smooth_step_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
-                           (const float *)buf[q], V, (const int *)noff, ncap,
-                           (const unsigned *)ctx->pool_smooth_nbr.p, (s & 1) ? mu : lambda, buf[next]);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::mc_smooth_step_kernel, blocks_v, 256, buf[q], V, noff, ncap,
+                        (const unsigned *)ctx->pool_smooth_nbr.p, (s & 1) ? mu : lambda, buf[next]));
         q = next;
     }
     // the normals of the final positions
     ARVX_HIP(ctx->pool_smooth_cross.reserve((size_t)std::max(3 * T, 1ll) * sizeof(float)));
     ARVX_HIP(ctx->pool_smooth_normals.reserve((size_t)3 * V * sizeof(float)));
     if (T > 0) {
-        hipLaunchKernelGGL(arvx::mc_smooth_cross_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T,
-                           (const float *)buf[q], V, (float *)ctx->pool_smooth_cross.p);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::mc_smooth_cross_kernel, blocks_t, 256, faces, T, buf[q], V,
+                        (float *)ctx->pool_smooth_cross.p));
     }
-    hipLaunchKernelGGL(arvx::mc_smooth_normal_kernel, dim3(blocks_v), dim3(256), 0, ctx->stream,
-                       (const int *)ioff, V, icap, (const unsigned *)ctx->pool_smooth_inc.p,
-                       (const float *)ctx->pool_smooth_cross.p, T, (float *)ctx->pool_smooth_normals.p);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::mc_smooth_normal_kernel, blocks_v, 256, ioff, V, icap,
+                    (const unsigned *)ctx->pool_smooth_inc.p, (const float *)ctx->pool_smooth_cross.p, T,
+                    (float *)ctx->pool_smooth_normals.p));
     ctx->smooth_q = q;
     ctx->smooth_ready = true;
     return ARVX_OK;
@@ -3966,19 +3721,14 @@ int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices
     if (int rc = compact_control(ctx, (size_t)((T + arvx::kScanChunk - 1) / arvx::kScanChunk), nullptr)) return rc;
     int *d_counts = nullptr;
     if (int rc = chunk_counts(ctx, ncw, &d_counts)) return rc;
-    hipLaunchKernelGGL(arvx::mc_decimate_plane_kernel, dim3((unsigned)((ncw + 255) / 256)), dim3(256), 0,
-                       ctx->stream, d_vtx, d, d_cbits, d_counts);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::mc_decimate_plane_kernel, blocks_for(ncw), 256, d_vtx, d, d_cbits, d_counts));
     const long long *d_nverts = nullptr;
     if (int rc = bit_compact(ctx, d_cbits, ncw, cg, vcap, d_cidx, d_crank, Ctx::kDecVerts, &d_nverts)) return rc;
-    hipLaunchKernelGGL(arvx::mc_decimate_vertex_kernel, dim3((unsigned)((vcap + 255) / 256)), dim3(256), 0,
-                       ctx->stream, (const int *)d_cidx, vcap, d_nverts, d, vtx, V, q,
-                       (const float *)ctx->pool_weld_rgb.p, (float *)ctx->pool_dec_verts.p,
-                       (float *)ctx->pool_dec_rgb.p, (int *)ctx->pool_dec_members.p);
-    ARVX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(arvx::mc_decimate_map_kernel, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, ctx->stream,
-                       (const int *)ctx->pool_weld_index.p, V, d, arvx::SparseList{d_crank}, d_map);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::mc_decimate_vertex_kernel, blocks_for(vcap), 256, d_cidx, vcap, d_nverts, d, vtx,
+                    V, q, (const float *)ctx->pool_weld_rgb.p, (float *)ctx->pool_dec_verts.p,
+                    (float *)ctx->pool_dec_rgb.p, (int *)ctx->pool_dec_members.p));
+    ARVX_TRY(launch(ctx, arvx::mc_decimate_map_kernel, blocks_for(V), 256, (const int *)ctx->pool_weld_index.p, V,
+                    d, arvx::SparseList{d_crank}, d_map));
     if (T > 0) {
         ARVX_HIP(ctx->pool_dec_faces.reserve((size_t)T * 6 * sizeof(unsigned)));
         ARVX_HIP(ctx->pool_dec_flags.reserve((size_t)T * 2 * sizeof(int)));
@@ -3986,20 +3736,15 @@ int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices
         const unsigned *faces = (const unsigned *)ctx->pool_weld_faces.p;
         unsigned *d_slots = (unsigned *)ctx->pool_dec_slots.p;
         int *d_flags = (int *)ctx->pool_dec_flags.p, *d_off = d_flags + T;
-        const unsigned blocks_t = (unsigned)((T + 255) / 256);
+        const unsigned blocks_t = blocks_for(T);
         ARVX_HIP(hipMemsetAsync(d_slots, 0xff, (size_t)vcap * arvx::kDecSlots * sizeof(unsigned), ctx->stream));
-        hipLaunchKernelGGL(arvx::mc_decimate_claim_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T, V,
-                           (const int *)d_map, (const int *)d_cidx, vcap, d_nverts, d, d_slots);
-        ARVX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(arvx::mc_decimate_flag_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T, V,
-                           (const int *)d_map, (const int *)d_cidx, vcap, d_nverts, d, (const unsigned *)d_slots,
-                           d_flags);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::mc_decimate_claim_kernel, blocks_t, 256, faces, T, V, d_map, d_cidx, vcap,
+                        d_nverts, d, d_slots));
+        ARVX_TRY(launch(ctx, arvx::mc_decimate_flag_kernel, blocks_t, 256, faces, T, V, d_map, d_cidx, vcap,
+                        d_nverts, d, d_slots, d_flags));
         if (int rc = scan_counts(ctx, d_flags, nullptr, T, nullptr, d_off, Ctx::kDecTris, nullptr)) return rc;
-        hipLaunchKernelGGL(arvx::mc_decimate_write_kernel, dim3(blocks_t), dim3(256), 0, ctx->stream, faces, T, V,
-                           (const int *)d_map, (const int *)d_flags, (const int *)d_off, T,
-                           (unsigned *)ctx->pool_dec_faces.p);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::mc_decimate_write_kernel, blocks_t, 256, faces, T, V, d_map, d_flags,
+                        d_off, T, (unsigned *)ctx->pool_dec_faces.p));
     }
     ARVX_SYNC(ctx);
     const long long nverts = host_total(ctx, Ctx::kDecVerts), ntris = T > 0 ? host_total(ctx, Ctx::kDecTris) : 0;
@@ -4074,9 +3819,8 @@ static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *
     arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
     arvx::SplatRect *large = (arvx::SplatRect *)((uint8_t *)ctx->pool_render_large.p + 64);
     const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
-    hipLaunchKernelGGL(arvx::render_clear_kernel, dim3((unsigned)std::min<size_t>((npix + 255) / 256, 8 * ncu)),
-                       dim3(256), 0, ctx->stream, keys, npix, head);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::render_clear_kernel, (unsigned)std::min<size_t>((npix + 255) / 256, 8 * ncu),
+                    256, keys, npix, head));
     // the background: the caller's rows, packed in the staging buffer, or zeros
     if (background) {
         if (!ctx->render_bg_done) ARVX_HIP(hipEventCreateWithFlags(&ctx->render_bg_done, hipEventDisableTiming));
@@ -4111,19 +3855,14 @@ static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *
         sp.large_cap = large_cap;
         // (the grid strides over the list)
         const dim3 sgrid((unsigned)std::min<long long>((n + 255) / 256, 8 * ncu));
-        by_assoc(ctx, [&](auto left) {
-            hipLaunchKernelGGL(arvx::render_splat_kernel<decltype(left)::value>, sgrid, dim3(256), 0, ctx->stream, sp);
-        });
-        ARVX_HIP(hipGetLastError());
-        hipLaunchKernelGGL(arvx::render_splat_large_kernel, dim3((unsigned)(4 * ncu)), dim3(256), 0, ctx->stream,
-                           (const arvx::SplatRect *)large, (const unsigned *)&head->n_large, large_cap, keys, W,
-                           ctx->word_dev(Ctx::kRenderNeed));
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::render_splat_kernel<decltype(left)::value>, sgrid, 256, sp);
+        }));
+        ARVX_TRY(launch(ctx, arvx::render_splat_large_kernel, (unsigned)(4 * ncu), 256, large, &head->n_large,
+                        large_cap, keys, W, ctx->word_dev(Ctx::kRenderNeed)));
     }
-    hipLaunchKernelGGL(arvx::render_resolve_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
-                       ctx->stream, (const unsigned long long *)keys, npix, (const float *)ctx->pool_weld_rgb.p,
-                       render_id(ctx), render_depth(ctx), render_bgr(ctx));
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::render_resolve_kernel, blocks_for(npix), 256, keys, npix,
+                    (const float *)ctx->pool_weld_rgb.p, render_id(ctx), render_depth(ctx), render_bgr(ctx)));
     ctx->render_ready = true;
     return ARVX_OK;
 }
@@ -4171,13 +3910,9 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]) {
     const size_t npix = (size_t)ctx->W * ctx->H;
     arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
     for (int k = 0; k < 3; ++k) ctx->word(Ctx::kRenderAgree + k) = -1;
-    hipLaunchKernelGGL(arvx::render_agreement_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0,
-                       ctx->stream, (const int *)render_id(ctx), npix,
-                       (const uint32_t *)(ctx->bg() + (size_t)view * ctx->bgWords), head->counts);
-    ARVX_HIP(hipGetLastError());
-    hipLaunchKernelGGL(arvx::render_counts_out_kernel, dim3(1), dim3(64), 0, ctx->stream,
-                       (const unsigned long long *)head->counts, ctx->word_dev(Ctx::kRenderAgree));
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::render_agreement_kernel, blocks_for(npix), 256, render_id(ctx), npix,
+                    ctx->bg() + (size_t)view * ctx->bgWords, head->counts));
+    ARVX_TRY(launch(ctx, arvx::render_counts_out_kernel, 1, 64, head->counts, ctx->word_dev(Ctx::kRenderAgree)));
     ARVX_SYNC(ctx);
     ctx->render_need = std::max(ctx->word(Ctx::kRenderNeed), 0ll);
     for (int k = 0; k < 3; ++k) {
@@ -4210,7 +3945,7 @@ int arvx_closure_download32(arvx_ctx *ctx, int32_t *index, float *rgba) {
 int arvx_fast_carve(arvx_ctx *ctx) {
     ARVX_CHECK_CTX(ctx);
     if (!ctx->views_ready) return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
-    if (ctx->z0 != 0 || ctx->z1 != ctx->Z || ctx->stripe_world > 1)
+    if (!whole_grid(ctx))
         return fail(ARVX_ERR_STATE,
                     "arvx_fast_carve needs the whole grid in one context (connectivity is global)");
     ctx->drop(Event::FastCarve);
@@ -4252,9 +3987,7 @@ int arvx_fast_carve(arvx_ctx *ctx) {
 
     // carvable = what the dense carve clears on a fresh model: carved into records of its own
     if (int rc = ensure_records(ctx, ctx->pool_flood_rec)) return rc;
-    arvx::CarveParams g;
-    carve_geometry(ctx, g);
-    g.rec = ctx->rec();
+    arvx::CarveParams g = record_params(ctx);
     // (the coarse tiles that carve settles as a whole exist only as their codes, as in the model's
     // own lazy state: no N / 4 bytes of constants written here and read back by the conversion)
     const size_t ncoarse_f = (size_t)g.coarseX * g.coarseY * g.coarseZ;
@@ -4265,21 +3998,17 @@ int arvx_fast_carve(arvx_ctx *ctx) {
     // of LDS, twice that for the way back)
     const int chunk = std::min(arvx::kFloodChunk, fp.XW);
     const size_t lds_words = (size_t)64 * (chunk + 1);
-    hipLaunchKernelGGL(arvx::flood_open_from_rec_kernel, dim3((unsigned)(g.tilesY * g.tilesZ)),
-                       dim3(256), lds_words * sizeof(unsigned long long), ctx->stream, g,
-                       (const uint16_t *)ctx->pool_flood_rec.p, (const uint8_t *)d_carv_code, fp);
-    ARVX_HIP(hipGetLastError());
+    ARVX_TRY(launch(ctx, arvx::flood_open_from_rec_kernel, (unsigned)(g.tilesY * g.tilesZ), 256,
+                    Lds{lds_words * sizeof(unsigned long long)}, g, (const uint16_t *)ctx->pool_flood_rec.p,
+                    d_carv_code, fp));
     // whole-tile pre-pass (fast_carve_kernels.h): seeds every completely open tile
     // that is connected to the origin tile through completely open tiles
     if (prepass) {
         const size_t tile_bytes = 2 * (size_t)tile_rows * sizeof(unsigned long long);
-        hipLaunchKernelGGL(arvx::flood_tile_full_kernel, dim3(tile_rows), dim3(256), 0,
-                           ctx->stream, fp, d_tiles, d_dirty);
-        hipLaunchKernelGGL(arvx::flood_tile_fill_kernel, dim3(1), dim3(1024), tile_bytes,
-                           ctx->stream, d_tiles, d_tiles + tile_rows, tilesY, tilesZ);
-        hipLaunchKernelGGL(arvx::flood_tile_seed_kernel, dim3(tile_rows), dim3(256), 0,
-                           ctx->stream, fp, d_tiles + tile_rows);
-        ARVX_HIP(hipGetLastError());
+        ARVX_TRY(launch(ctx, arvx::flood_tile_full_kernel, tile_rows, 256, fp, d_tiles, d_dirty));
+        ARVX_TRY(launch(ctx, arvx::flood_tile_fill_kernel, 1, 1024, Lds{tile_bytes}, d_tiles,
+                        d_tiles + tile_rows, tilesY, tilesZ));
+        ARVX_TRY(launch(ctx, arvx::flood_tile_seed_kernel, tile_rows, 256, fp, d_tiles + tile_rows));
     }
     // per-tile wake flags, two buffers swapped every launch; without the pre-pass
     // (which sets the first buffer) all tiles are awake at first
@@ -4298,9 +4027,7 @@ int arvx_fast_carve(arvx_ctx *ctx) {
             fp.dirty_cur = d_dirty + (launched & 1) * (size_t)gflood;
             fp.dirty_next = d_dirty + ((launched + 1) & 1) * (size_t)gflood;
             fp.changed = flags + k;
-            hipLaunchKernelGGL(arvx::flood_step_kernel, dim3(gflood), dim3(256), 0, ctx->stream,
-                               fp);
-            ARVX_HIP(hipGetLastError());
+            ARVX_TRY(launch(ctx, arvx::flood_step_kernel, gflood, 256, fp));
         }
         ARVX_HIP(hipMemcpyAsync(changed, flags, 8 * sizeof(int), hipMemcpyDeviceToHost,
                                 ctx->stream));
@@ -4309,12 +4036,9 @@ int arvx_fast_carve(arvx_ctx *ctx) {
         if (launched >= max_launches) return fail(ARVX_ERR_HIP, "flood fill did not converge");
         if (round >= 1 && batch < 8) batch *= 2;
     }
-    {
-        const unsigned rows = (unsigned)((g.coarseY << g.cyShift) * (g.coarseZ << g.czShift));
-        hipLaunchKernelGGL(arvx::flood_apply_rec_kernel, dim3(rows), dim3(256),
-                           2 * lds_words * sizeof(unsigned long long), ctx->stream, g, fp);
-    }
-    ARVX_HIP(hipGetLastError());
+    const unsigned rows = (unsigned)((g.coarseY << g.cyShift) * (g.coarseZ << g.czShift));
+    ARVX_TRY(launch(ctx, arvx::flood_apply_rec_kernel, rows, 256, Lds{2 * lds_words * sizeof(unsigned long long)},
+                    g, fp));
     ctx->form = Form::Records;  // the records now hold every voxel's state
     ARVX_SYNC(ctx);
     // (arvx_last_fast_carve_path: all of it once the carve is through, or nothing)

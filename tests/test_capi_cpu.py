@@ -28,6 +28,18 @@ def test_header_symbols_are_exported(arvx):
     assert lib.arvx_version() == 100
 
 
+def test_every_launch_goes_through_the_checked_helper():
+    # the host convention ("One checked launch"): launch() is the only place of
+    # arvx_capi.hip that launches a kernel, and it checks the launch itself
+    text = open(os.path.join(ROOT, "ar_voxel_project_amd", "csrc", "arvx_capi.hip")).read()
+    assert len(re.findall(r"\bhipLaunchKernelGGL\b", text)) == 1
+    helper = text[text.index("static int launch("):]
+    helper = helper[:helper.index("\n}\n")]
+    assert "hipLaunchKernelGGL" in helper and "hipGetLastError()" in helper and "fail_hip" in helper
+    stray = [n + 1 for n, line in enumerate(text.splitlines()) if line.strip() == "ARVX_HIP(hipGetLastError());"]
+    assert not stray, f"hand-written launch checks at lines {stray}"
+
+
 def test_no_torch_types_in_boundary():
     text = open(HEADER).read()
     assert "torch" not in text and "at::" not in text and "#include <hip" not in text
