@@ -55,6 +55,7 @@ def build_host_tests() -> str:
     build_smooth_host_test()
     build_decimate_host_test()
     build_morph_host_test()
+    build_refine_host_test()
     return os.path.join(ROOT, "tests", "cpp", "test_host")
 
 
@@ -81,6 +82,13 @@ def build_morph_host_test() -> str:
     (include/arvx/postprocessing.hpp) on a Model from a file, built as build_weld_host_test builds its
     test."""
     return _build_host_test("test_morph_host")
+
+
+def build_refine_host_test() -> str:
+    """g++ -> tests/cpp/test_refine_host: arvx::marchingCubesMeshRefined
+    (include/arvx/marching_cubes.hpp) on a scene from a file, built as build_weld_host_test builds its
+    test."""
+    return _build_host_test("test_refine_host")
 
 
 def _build_host_test(name: str) -> str:

@@ -85,6 +85,7 @@ SYMBOLS = [
     "arvx_mc_mesh_download_faces", "arvx_mc_mesh_welded", "arvx_mc_mesh_welded_download",
     "arvx_mc_mesh_smooth", "arvx_mc_mesh_smooth_download",
     "arvx_mc_mesh_decimate", "arvx_mc_mesh_decimate_download",
+    "arvx_mc_mesh_refined", "arvx_mc_mesh_refined_download",
     "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
@@ -233,6 +234,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.arvx_mc_mesh_decimate.argtypes = [p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.arvx_mc_mesh_decimate_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_void_p]
+    if hasattr(lib, "arvx_mc_mesh_refined"):
+        lib.arvx_mc_mesh_refined.argtypes = [p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.arvx_mc_mesh_refined_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]
     if hasattr(lib, "arvx_color_visible"):
         lib.arvx_color_visible.argtypes = [p, C.c_int, C.c_float]
         lib.arvx_surface_visible_download.argtypes = [p, C.POINTER(C.c_int32)]
@@ -919,6 +924,35 @@ class Context:
         self._ck(self._lib.arvx_mc_mesh_decimate_download(
             self._h, *[a.ctypes.data if a is not None else None for a in out]))
         return tuple(out)
+
+    def mc_mesh_refined(self, bisections: int = 6, apply_unseen: bool = False, vertex_colors: bool = False,
+                        details: bool = False):
+        """Marching cubes with one vertex per cut edge, placed where the edge leaves the visual hull
+        by `bisections` bisection steps against the views' masks (arvx_mc_mesh_refined; 0: plain
+        midpoints): (verts (Vr, 3) float32 in voxel units, faces (T, 3) uint32, face_rgb (T, 3)
+        uint32[, vertex_rgb (Vr, 3) float32 when vertex_colors][, edges (Vr, 4) int32 -- the occupied
+        end and the direction to the empty one, + 8 where the edge is no silhouette edge --, cut (Vr,)
+        int32, the position in units of 2^-(bisections+1), when details])."""
+        nv, nt = self.mc_mesh_refined_count(bisections, apply_unseen)
+        verts = np.empty((nv, 3), np.float32)
+        records = np.empty((nt, 6), np.uint32)  # i0, i1, i2, r, g, b
+        vrgb = np.empty((nv, 3), np.float32) if vertex_colors else None
+        edges = np.empty((nv, 4), np.int32) if details else None
+        cut = np.empty(nv, np.int32) if details else None
+        self._ck(self._lib.arvx_mc_mesh_refined_download(
+            self._h, verts.ctypes.data, records.ctypes.data,
+            *[a.ctypes.data if a is not None else None for a in (vrgb, edges, cut)]))
+        out = (verts, np.ascontiguousarray(records[:, :3]), np.ascontiguousarray(records[:, 3:]))
+        if vertex_colors:
+            out += (vrgb,)
+        return out + (edges, cut) if details else out
+
+    def mc_mesh_refined_count(self, bisections: int = 6, apply_unseen: bool = False):
+        """arvx_mc_mesh_refined without the download: (Vr, T); the mesh stays on the device."""
+        nv, nt = C.c_int64(), C.c_int64()
+        self._ck(self._lib.arvx_mc_mesh_refined(self._h, int(apply_unseen), int(bisections), C.byref(nv),
+                                                C.byref(nt)))
+        return int(nv.value), int(nt.value)
 
     def render(self, M, W: int, H: int, background=None, download: bool = True):
         """arvx_render: the welded mesh's vertex voxels drawn into the camera M (3 x 4, world ->

@@ -37,6 +37,7 @@
 #include "mc_weld_kernels.h"
 #include "mc_smooth_kernels.h"
 #include "mc_decimate_kernels.h"
+#include "mc_refine_kernels.h"
 #include "visibility_kernels.h"
 #include "photo_kernels.h"
 #include "components_kernels.h"
@@ -327,7 +328,9 @@ static int bit_compact(Ctx *ctx, const unsigned long long *bits, size_t nwords, 
     int *other = (int *)ctx->pool_chunk_counts.p + (size_t)(ctx->counts_cur ^ 1) * ctx->counts_stride;
     ARVX_TRY(launch(ctx, arvx::bit_compact_counted_kernel, (unsigned)nchunks, 256, bits, nwords, g, cur,
                     other, cap, d_index, d_words, d_total, ctx->word_dev(w)));
-    ctx->counts_clean[ctx->counts_cur ^ 1] = true;
+    // (it clears one entry per chunk of THIS plane: a buffer that a longer plane's producer added into
+    // -- the refined mesh's edge plane has three bits per lattice point -- stays marked for a fill)
+    ctx->counts_clean[ctx->counts_cur ^ 1] = ctx->counts_used[ctx->counts_cur ^ 1] <= nchunks;
     if (d_total_out) *d_total_out = d_total;
     return ARVX_OK;
 }
@@ -345,6 +348,7 @@ static int chunk_counts(Ctx *ctx, size_t nwords, int **counts) {
     if (!ctx->counts_clean[k])  // (first use, or a call that failed between producer and compaction)
         ARVX_HIP(hipMemsetAsync(buf, 0, ctx->counts_stride * sizeof(int), ctx->stream));
     ctx->counts_clean[k] = false;  // the producer is about to add into it
+    ctx->counts_used[k] = n;
     ctx->counts_cur = k;
     *counts = buf;
     return ARVX_OK;
@@ -3773,6 +3777,118 @@ int arvx_mc_mesh_decimate_download(arvx_ctx *ctx, float *verts, uint32_t *faces,
         ARVX_HIP(hipMemcpyAsync(members, ctx->pool_dec_members.p, Vd * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (V > 0 && map)
         ARVX_HIP(hipMemcpyAsync(map, ctx->pool_dec_map.p, V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+// The refined mesh (mc_refine_kernels.h): occupancy plane, edge plane, cells, triangles and the
+// bisection, all launched before the call's ONE synchronisation, as in arvx_mc_mesh_welded; the three
+// lists' lengths come back together, and a mesh that outgrew its buffers is built once more with room
+// for all of it.  Its buffers are its own: the welded mesh and what was made of it stay as they were.
+int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_t *vertices,
+                         int64_t *triangles) {
+    ARVX_CHECK_CTX(ctx);
+    if (!vertices || !triangles) return fail(ARVX_ERR_INVALID, "null argument");
+    if (bisections < 0 || bisections > 10) return fail(ARVX_ERR_INVALID, "bisections %d (0..10)", bisections);
+    if (!whole_grid(ctx))
+        return fail(ARVX_ERR_STATE, "arvx_mc_mesh_refined needs a whole-grid context (vertex indices "
+                                    "are ranks in the whole grid)");
+    if (std::max({ctx->X, ctx->Y, ctx->Z}) > 4096)
+        return fail(ARVX_ERR_STATE, "a grid side above 4096: the cut positions would not be exact in fp32");
+    const arvx::BitGrid eg = arvx::refine_edge_grid(ctx->X, ctx->Y, ctx->Z);
+    if ((long long)eg.X * eg.Y * eg.Z > (long long)INT32_MAX)
+        return fail(ARVX_ERR_STATE, "3 (X+1)(Y+1)(Z+1) > INT32_MAX: the edge keys do not fit 32 bits");
+    if (bisections > 0 && !ctx->views_ready)
+        return fail(ARVX_ERR_STATE, "the bisection needs views with masks (arvx_set_views)");
+    if (int frc = fills_without_colours(ctx)) return frc;
+    if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
+        return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d", ctx->closure_unseen);
+    ctx->free_mc();
+    ctx->ref_ready = false;
+    ctx->ref_verts = ctx->ref_tris = 0;
+    *vertices = *triangles = 0;
+    // the occupancy the cell walk reads (the records: closure fills included), then the edge plane
+    // with its chunk counts
+    const arvx::BitGrid g = bit_grid(ctx);
+    const size_t nw = bit_words(g), new_ = bit_words(eg);
+    ARVX_HIP(ctx->pool_ref_planes.reserve((nw + new_) * sizeof(unsigned long long)));
+    ARVX_HIP(ctx->pool_ref_rank.reserve(new_ * sizeof(arvx::SparseWord)));
+    unsigned long long *d_occ = (unsigned long long *)ctx->pool_ref_planes.p, *d_edge = d_occ + nw;
+    arvx::SparseWord *d_rank = (arvx::SparseWord *)ctx->pool_ref_rank.p;
+    if (int rc = launch_bit_pack(ctx, g, 0, 0, d_occ, nullptr)) return rc;
+    int *d_counts = nullptr;
+    if (int rc = chunk_counts(ctx, new_, &d_counts)) return rc;
+    ARVX_TRY(launch(ctx, arvx::mc_refine_plane_kernel, blocks_for(new_), 256, d_occ, g, eg, d_edge, d_counts));
+    arvx::RefineViews vw{};
+    if (ctx->views_ready)  // (without masks only bisections == 0 gets here: every cut is the midpoint)
+        vw = arvx::RefineViews{ctx->M(), ctx->bg(), ctx->V, ctx->W, ctx->H, ctx->bgWords, ctx->s};
+    // room: what the last refined mesh needed, or a surface's share of the voxels (three cut edges
+    // per surface voxel, about)
+    const long long cells = mc_cells_cap(ctx);
+    ListRoom lists[] = {{Ctx::kCells, cells, 0},
+                        {Ctx::kTris, list_cap(ctx->pool_ref_faces, 6 * sizeof(unsigned), 2 * cells), 0},
+                        {Ctx::kRefVerts, list_cap(ctx->pool_ref_index, sizeof(int), 3 * cells), 0}};
+    const long long &ccap = lists[0].cap, &tcap = lists[1].cap, &vcap = lists[2].cap;
+    auto attempt = [&]() -> int {
+        ARVX_HIP(ctx->pool_ref_index.reserve((size_t)vcap * sizeof(int)));
+        ARVX_HIP(ctx->pool_ref_verts.reserve((size_t)vcap * 3 * sizeof(float)));
+        ARVX_HIP(ctx->pool_ref_rgb.reserve((size_t)vcap * 3 * sizeof(float)));
+        ARVX_HIP(ctx->pool_ref_edges.reserve((size_t)vcap * 5 * sizeof(int)));  // 4 ints of edge, then n
+        ARVX_HIP(ctx->pool_ref_faces.reserve((size_t)tcap * 6 * sizeof(unsigned)));
+        const long long *d_nverts = nullptr;
+        if (int rc = bit_compact(ctx, d_edge, new_, eg, vcap, (int *)ctx->pool_ref_index.p, d_rank,
+                                 Ctx::kRefVerts, &d_nverts))
+            return rc;
+        const long long *d_ncells = nullptr;
+        if (int rc = mc_cells_launch(ctx, ccap, &d_ncells)) return rc;
+        const arvx::McMeshParams mp = mesh_params(ctx, apply_unseen);
+        ARVX_HIP(ctx->pool_mesh_off.reserve((size_t)(ccap + 1) * sizeof(int)));
+        int *d_off = (int *)ctx->pool_mesh_off.p;
+        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, Ctx::kTris, nullptr))
+            return rc;
+        ARVX_TRY(launch(ctx, arvx::mc_refine_tri_kernel, blocks_for(ccap), 256, mp, arvx::SparseList{d_rank}, eg,
+                        (const int4 *)ctx->d_mc_cells, ccap, d_ncells, tcap, d_off,
+                        (unsigned *)ctx->pool_ref_faces.p));
+        int *d_edges = (int *)ctx->pool_ref_edges.p;
+        return by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::mc_refine_vertex_kernel<decltype(left)::value>, blocks_for(vcap), 256, mp, vw,
+                          d_occ, g, (const int *)ctx->pool_ref_index.p, vcap, d_nverts, bisections,
+                          (float *)ctx->pool_ref_verts.p, (float *)ctx->pool_ref_rgb.p, d_edges,
+                          d_edges + 4 * vcap);
+        });
+    };
+    if (int rc = run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }))
+        return rc;
+    const long long ncells = lists[0].total, ntris = lists[1].total, nverts = lists[2].total;
+    if (ncells == 0) ctx->d_mc_cells = nullptr;
+    ctx->mc_count = ncells;
+    ctx->mc_ready = true;
+    ctx->ref_verts = nverts;
+    ctx->ref_tris = ntris;
+    ctx->ref_cap = vcap;
+    ctx->ref_ready = true;
+    *vertices = nverts;
+    *triangles = ntris;
+    return ARVX_OK;
+}
+
+int arvx_mc_mesh_refined_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb,
+                                  int32_t *edges, int32_t *cut) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->ref_ready) return fail(ARVX_ERR_STATE, "no refined mesh (call arvx_mc_mesh_refined)");
+    const size_t Vr = (size_t)ctx->ref_verts, T = (size_t)ctx->ref_tris;
+    const int *d_edges = (const int *)ctx->pool_ref_edges.p;
+    if (Vr > 0 && verts)
+        ARVX_HIP(hipMemcpyAsync(verts, ctx->pool_ref_verts.p, Vr * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if (T > 0 && faces)
+        ARVX_HIP(hipMemcpyAsync(faces, ctx->pool_ref_faces.p, T * 24, hipMemcpyDeviceToHost, ctx->stream));
+    if (Vr > 0 && vertex_rgb)
+        ARVX_HIP(hipMemcpyAsync(vertex_rgb, ctx->pool_ref_rgb.p, Vr * 12, hipMemcpyDeviceToHost, ctx->stream));
+    if (Vr > 0 && edges)
+        ARVX_HIP(hipMemcpyAsync(edges, d_edges, Vr * 16, hipMemcpyDeviceToHost, ctx->stream));
+    if (Vr > 0 && cut)
+        ARVX_HIP(hipMemcpyAsync(cut, d_edges + 4 * (size_t)ctx->ref_cap, Vr * 4, hipMemcpyDeviceToHost,
+                                ctx->stream));
     ARVX_SYNC(ctx);
     return ARVX_OK;
 }

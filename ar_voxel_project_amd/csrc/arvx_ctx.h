@@ -76,6 +76,7 @@ struct Ctx {
         kSmoothScan,                    // arvx_mc_mesh_smooth's offset scans: a total nobody reads
         kComponents,                    // the component table's length (arvx_components[_keep])
         kDecVerts, kDecTris,            // arvx_mc_mesh_decimate: decimated vertices, surviving faces
+        kRefVerts,                      // arvx_mc_mesh_refined: cut edges (kCells and kTris carry its other lists)
         kDeviceTotals,
         kPhotoRemoved = kDeviceTotals,  // voxels an iteration of arvx_photo_carve removed
         kVisNeed,                       // large footprints the visible pass wanted to list
@@ -102,6 +103,7 @@ struct Ctx {
     size_t counts_stride = 0;
     int counts_cur = 0;
     bool counts_clean[2] = {false, false};
+    size_t counts_used[2] = {0, 0};  // chunks of the plane whose producer last added into each buffer
     unsigned long long compact_tickets = 0;  // tickets all launches so far have taken
     uint32_t compact_epoch = 0;
     long long surf_host_count = -1;  // entries of h_surf_index / h_surf_has that are valid (-1: fetch)
@@ -305,7 +307,7 @@ struct Ctx {
     // those calls against it.  Every entry point calls drop() once, after its refusals and before its
     // work, so that a refused call leaves the context as it was.  (The closure calls it where its fills
     // go into the state: the colour pass's planes it starts from are those of the state before.)  The
-    // mesh products (mc_ready, weld_ready, smooth_*, dec_ready) are not here: each lives until the next
+    // mesh products (mc_ready, weld_ready, smooth_*, dec_ready, ref_ready) are not here: each lives until the next
     // call of its own stage.  The render of the welded mesh (arvx_render) is: it shows the state the
     // mesh was built from, so whatever replaces that state drops it (and so does the next
     // arvx_mc_mesh_welded).
@@ -408,6 +410,14 @@ struct Ctx {
         pool_dec_faces, pool_dec_flags, pool_dec_slots;
     int64_t dec_verts = 0, dec_tris = 0;
     bool dec_ready = false;
+    // arvx_mc_mesh_refined: the occupancy plane and the edge plane behind it, the edge plane's ranks
+    // and list (the keys), and the refined mesh (positions, vertex colours, face records; per vertex
+    // 4 ints of edge description, then -- ref_cap entries in -- the cut numerators), sized by the
+    // list protocol and kept
+    DevPool pool_ref_planes, pool_ref_rank, pool_ref_index, pool_ref_verts, pool_ref_rgb, pool_ref_faces,
+        pool_ref_edges;
+    int64_t ref_verts = 0, ref_tris = 0, ref_cap = 0;
+    bool ref_ready = false;
 
     // arvx_render: the W x H keys, the images (id | depth | bgr), the large-footprint list behind
     // its header (render_kernels.h), all sized at first use and kept.  Count words: kRenderNeed, then

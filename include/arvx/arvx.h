@@ -758,6 +758,63 @@ int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices
 int arvx_mc_mesh_decimate_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb,
                                    int32_t *members, int32_t *map);
 
+/* The refined mesh: marching cubes with one vertex per cut edge, placed where the edge leaves the
+ * visual hull (the classic visual-hull refinement; an extension beyond the reference, whose
+ * VertexInterp snaps every cut edge to its occupied corner).  The views' background bit planes and
+ * matrices say for any point of space whether it lies in the hull, so a few bisection steps along a
+ * cut edge find where it leaves.  Definition, on a whole-grid context, its current state,
+ * apply_unseen and an integer bisections = B, 0 <= B <= 10:
+ *   - cells: the cells, their order and their cube indices are those of arvx_mc_cells;
+ *   - cut edges: a lattice edge between two points one step apart along x, y or z of which exactly
+ *     one is occupied (out of the grid counts as empty; occupied as arvx_mc_cells reads it, closure
+ *     fills included).  Its lower end is q (the componentwise minimum), its axis a in {0, 1, 2};
+ *   - vertices: one per cut edge, ascending by the key
+ *     (((q.z+1) * (Y+1) + (q.y+1)) * (X+1) + (q.x+1)) * 3 + a.  Vr of them;
+ *   - faces: the T triangles of arvx_mc_mesh for the same state in the same order.  Corner k of
+ *     triangle t came from edge e of its cell, between corners e % 8 and MC_SECOND[e]
+ *     (include/arvx/mc_tables.hpp, kSecondCorner); it becomes the index of that cut edge's vertex.
+ *     r, g, b are arvx_mc_mesh's face_rgb[t], unchanged.  So T is arvx_mc_mesh's T, no face repeats
+ *     an index, and every vertex is used;
+ *   - inside(p), for a point p = (px, py, pz) in fp32 voxel coordinates: there is no view in which p
+ *     projects into the image onto a background pixel.  The projection is the carve's own with
+ *     coordinates in place of integers: world = (py * s, px * s, (-pz) * s, 1) in fp32, the rows'
+ *     fp64 products summed in the context's grouping and rounded to fp32, the two quotients IEEE
+ *     fp32 divisions, rounding std::round; a non-finite or out-of-range value or a pixel outside the
+ *     image means the view does not see p.  For integer p this is exactly what arvx_carve tests;
+ *   - cut position: for an edge with occupied end A and empty end E, a SILHOUETTE edge is one with
+ *     inside(A) && !inside(E).  For it: lo = 0, hi = 2^B; B times: mid = (lo + hi) / 2, and if
+ *     inside(A + (mid / 2^B) (E - A)) then lo = mid, else hi = mid; then n = lo + hi.  Every other
+ *     edge -- one the silhouettes do not explain: a pit cut by photo carving, an eroded or dilated
+ *     surface, an uploaded state -- takes n = 2^B, the midpoint.  The vertex is A with n / 2^(B+1)
+ *     added to or subtracted from its component along the axis, towards E.  With B <= 10 and no grid
+ *     side above 4096 every such value is exact in fp32.  B = 0 is plain midpoint marching cubes;
+ *   - vertex colour: the colour arvx_mc_mesh_welded gives the occupied end's voxel, with the same
+ *     precedence (UNSEEN paint, closure, colour pass, MODEL_COLOR).
+ * arvx_mc_mesh_refined builds it with ONE host synchronisation, for the counts, and returns Vr and
+ * T.  Its buffers are sized by the list protocol of the other meshes (what the last call needed, or
+ * a surface's share; a mesh that outgrew them is built once more) and nothing falls back to the
+ * host.  Device memory beside the outputs (44 Vr + 24 T bytes): the occupancy plane (1 bit per
+ * voxel) and the edge plane with its ranks (3 bits and 6 bytes per 8 lattice points), kept.
+ * arvx_mc_mesh_refined_download copies 3 Vr floats of positions (voxel units), 6 T uints of face
+ * records {i0, i1, i2, r, g, b}, 3 Vr floats of vertex colours, 4 Vr ints of edges -- x, y, z of the
+ * OCCUPIED end, then the direction to the empty end: 0 +x, 1 -x, 2 +y, 3 -y, 4 +z, 5 -z, plus 8
+ * when the edge is not a silhouette edge -- and Vr ints of n; any pointer may be null.
+ * Refusals.  ARVX_ERR_STATE: a slab or a striped context; views set without masks, or no views at
+ * all, when B > 0 (B = 0 needs none: no edge is a silhouette edge then); a state holding a closure's
+ * fills whose list is gone, as for arvx_mc_mesh; a grid side above 4096, or a grid with
+ * 3 (X+1)(Y+1)(Z+1) > INT32_MAX, whose keys do not fit 32 bits; a download before a mesh.
+ * ARVX_ERR_INVALID: B outside [0, 10]; null count pointers.  A refused call leaves the previous
+ * refined mesh as it was.
+ * The refined mesh lives until the next arvx_mc_mesh_refined.  It is a snapshot of the state and the
+ * views at the call and touches no other product -- the unwelded, welded, smoothed and decimated
+ * meshes and a render stay as they were; like arvx_mc_mesh_welded it runs arvx_mc_cells itself.
+ * Out of scope: smoothing, decimating or rendering this mesh; normals; slabs and multi-GPU; colour
+ * interpolation along the edge. */
+int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_t *vertices,
+                         int64_t *triangles);
+int arvx_mc_mesh_refined_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb,
+                                  int32_t *edges, int32_t *cut);
+
 /* ---- render (extension beyond the reference) -------------------------------------------------
  * Draws the welded mesh's vertex voxels into a camera view: the model over a photograph, the voxel
  * under a pixel, a carve checked against its own silhouettes.  Definition, on a whole-grid context

@@ -647,6 +647,51 @@ inline bool marchingCubesDecimated(Model *model, float scale = 1.0f, Vec3f trans
                                         });
 }
 
+// ---- refined mesh (an extension beyond the reference) --------------------------------------------
+//
+// Marching cubes with one vertex per cut edge, placed where the edge leaves the visual hull of the
+// views' masks by `bisections` bisection steps (arvx_mc_mesh_refined, defined in include/arvx/arvx.h;
+// 0: plain edge midpoints).  The views are bound as carveVotes binds them -- matrices and masks; they
+// need not be the views the model was carved with, though only those explain its surface.  The
+// triangles, their order and their colours are marchingCubesMesh's; the vertices are shared.  The
+// device does all of it and there is no host route: a model with fractional w, whose vertices the
+// reference interpolates by w, is refused with an exception.
+inline SimpleMesh marchingCubesMeshRefined(const Intrinsics &intr, Model *model, const std::vector<View> &views,
+                                           int bisections = 6, float threshold = 0.5f) {
+    if (!(threshold > 0.f)) return SimpleMesh();
+    bool on_device = false;
+    (void)model->inside_state(threshold, on_device);
+    if (!on_device)
+        throw Error(ARVX_ERR_STATE, "marchingCubesMeshRefined: the model has voxels with fractional w; the refined "
+                                    "mesh is built on the device from models whose w are all 0 or 1");
+    (void)detail::bind_views(intr, *model, views, false);
+    model->set_colors_on_device(false);  // (arvx_set_views drops the context's colour list)
+    int apply_unseen = 0;
+    arvx_ctx *ctx = detail::mesh_context(model, apply_unseen);
+    int64_t nv = 0, nt = 0;
+    detail::check(arvx_mc_mesh_refined(ctx, apply_unseen, bisections, &nv, &nt), "arvx_mc_mesh_refined");
+    SimpleMesh mesh;
+    HostVector<Vec3f> &mv = mesh.GetVertices();
+    HostVector<Triangle> &mt = mesh.GetTriangles();
+    mv.resize((size_t)nv);  // (recycled memory, not zeroed: host_pool.hpp)
+    mt.resize((size_t)nt);
+    detail::check(arvx_mc_mesh_refined_download(ctx, nv ? mv[0].data() : nullptr, nt ? &mt[0].idx0 : nullptr,
+                                                nullptr, nullptr, nullptr),
+                  "arvx_mc_mesh_refined_download");
+    return mesh;
+}
+
+// marchingCubes writing the refined mesh: the views and the bisections, then marchingCubes'
+// arguments, log lines and Benchmark stage.
+inline bool marchingCubesRefined(const Intrinsics &intr, Model *model, const std::vector<View> &views,
+                                 int bisections = 6, float scale = 1.0f, Vec3f translation = Vec3f(0, 0, 0),
+                                 float threshold = 0.5f, std::string outFileName = "out/mesh.off") {
+    return detail::marching_cubes_write(model, scale, translation, threshold, outFileName,
+                                        [&](Model *m, float t) {
+                                            return marchingCubesMeshRefined(intr, m, views, bisections, t);
+                                        });
+}
+
 namespace detail {
 // carve(..., intermediateMeshes = true) without a caller-supplied hook writes what the
 // reference writes after every view (src/VoxelCarving.cpp:65-68): the model so far, moved

@@ -229,7 +229,7 @@ int main(int argc, char *argv[]) {
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
         {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"},
-        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}};
+        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -240,6 +240,9 @@ int main(int argc, char *argv[]) {
                      "  -smooth=N (the welded mesh after N Taubin iterations, lambda 0.5, mu -0.53),\n"
                      "  -decimate=C (the welded mesh -- after -smooth=N, if given -- with the vertices of\n"
                      "    every cube of C^3 voxels merged into one, 1 <= C <= 64; 0, the default: off),\n"
+                     "  -refine=B (in place of the plain mesh: one vertex per cut edge, placed where the edge\n"
+                     "    leaves the masks' visual hull by B bisection steps, 0 <= B <= 10; 0: edge midpoints;\n"
+                     "    not together with -smooth or -decimate),\n"
                      "  -visible=true (-color=1|2 over the views in which each voxel is visible),\n"
                      "  -visibleTol=T (its depth tolerance in voxel edges, default 3),\n"
                      "  -misses=K (-carve=1: empty a voxel only when more than K views see it as\n"
@@ -297,6 +300,16 @@ int main(int argc, char *argv[]) {
         if (morphs > 1) {
             std::cerr << "At most one of -erode, -dilate, -open and -close may be given.";
             return 1;
+        }
+        if (!parser.str("refine").empty()) {
+            if (parser.i("refine") < 0 || 10 < parser.i("refine")) {
+                std::cerr << "Invalid refine argument.";
+                return 1;
+            }
+            if (parser.i("smooth") > 0 || parser.i("decimate") > 0) {
+                std::cerr << "-refine writes a mesh of its own: it cannot be combined with -smooth or -decimate.";
+                return 1;
+            }
         }
     }
     Inputs in;
@@ -473,8 +486,12 @@ int main(int argc, char *argv[]) {
         if (parser.b("postprocessing")) arvx::applyClosure(&model, 3);
         // -weld (an extension beyond the reference): the same mesh with shared vertices;
         // -smooth=N (N > 0): that mesh after N Taubin iterations; -decimate=C (C > 0): the welded
-        // (and smoothed) mesh reduced by vertex clustering
-        if (parser.i("decimate") > 0)
+        // (and smoothed) mesh reduced by vertex clustering; -refine=B: marching cubes with one vertex
+        // per cut edge, moved to where the edge leaves the masks' visual hull
+        if (!parser.str("refine").empty())
+            arvx::marchingCubesRefined(in.intr, &model, in.views, parser.i("refine"), parser.f("scale"),
+                                       modelTranslation, 0.5f, parser.str("outFile"));
+        else if (parser.i("decimate") > 0)
             arvx::marchingCubesDecimated(&model, parser.f("scale"), modelTranslation, 0.5f, parser.str("outFile"),
                                          parser.i("decimate"), std::max(parser.i("smooth"), 0));
         else if (parser.i("smooth") > 0)
