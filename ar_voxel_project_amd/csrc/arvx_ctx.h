@@ -302,13 +302,14 @@ struct Ctx {
     // SetViews set_views, SetImages set_images, Color color, UploadColors upload_colors, HandleUnseen
     // handle_unseen, Closure closure, Carve carve and carve_votes, FastCarve fast_carve, UploadState
     // upload_state, UploadPlanes upload_planes, Reset reset, PhotoCarve photo_carve, ComponentsKeep
-    // keep_components, MorphShrink and MorphGrow morph (by its op).  ProjectionAssoc, UploadHalo and the
-    // render column have no restatement there.  tests/test_stage_sequences_gpu.py replays orders of
+    // keep_components, MorphShrink and MorphGrow morph (by its op).  The render column is restated by
+    // CtxModel.rendered, from the render's paragraph in arvx.h; ProjectionAssoc and UploadHalo have no
+    // restatement there.  tests/test_stage_sequences_gpu.py replays orders of
     // those calls against it.  Every entry point calls drop() once, after its refusals and before its
     // work, so that a refused call leaves the context as it was.  (The closure calls it where its fills
     // go into the state: the colour pass's planes it starts from are those of the state before.)  The
     // mesh products (mc_ready, weld_ready, smooth_*, dec_ready, ref_ready) are not here: each lives until the next
-    // call of its own stage.  The render of the welded mesh (arvx_render) is: it shows the state the
+    // call of its own stage (CtxModel holds them as well, and the sequences download them after other calls).  The render of the welded mesh (arvx_render) is: it shows the state the
     // mesh was built from, so whatever replaces that state drops it (and so does the next
     // arvx_mc_mesh_welded).
     enum class Event {

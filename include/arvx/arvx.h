@@ -646,7 +646,14 @@ int arvx_closure_download32(arvx_ctx *ctx, int32_t *index, float *rgba);
  * ProcessVoxel on this list alone builds the same mesh.  Slab contexts list the
  * cells whose upper plane they own (global z; the last slab also those above the
  * grid); striped contexts are refused.  Valid for 0 < threshold <= 1, which
- * covers the 0.5 every reference call site passes. */
+ * covers the 0.5 every reference call site passes.
+ * The list is a snapshot of the occupancy at the walk.  It lives until the next walk: the next
+ * arvx_mc_cells, arvx_mc_mesh, arvx_mc_mesh_welded or arvx_mc_mesh_refined (each runs the walk
+ * itself; a call of theirs that is refused leaves the list).  No other call touches it -- a carve, an
+ * upload or a reset replaces the state and leaves the list of the state before; before the first walk
+ * arvx_mc_cells_download answers ARVX_ERR_STATE.  Only arvx_mc_cells returns the length: a caller
+ * that downloads the list a mesh call left sizes its buffer by the bound, one cell per lattice cell,
+ * (X+1) * (Y+1) * (owned planes + 1). */
 int arvx_mc_cells(arvx_ctx *ctx, int64_t *count);
 int arvx_mc_cells_download(arvx_ctx *ctx, int32_t *cells);
 
@@ -659,7 +666,12 @@ int arvx_mc_cells_download(arvx_ctx *ctx, int32_t *cells);
  * else the closure's colour, else the colour pass's, else MODEL_COLOR.  Whole-grid contexts and
  * slabs with enough halo planes (arvx_ctx_create_slab_halo): a slab builds the triangles of the
  * cells arvx_mc_cells lists for it (global z).  Runs arvx_mc_cells itself; the order is the
- * reference's. */
+ * reference's.
+ * The mesh is a snapshot of the state and the colours at the call.  It lives until the next arvx_mc_mesh
+ * (a refused one leaves it): no call that replaces the state, the views or the colours touches it, and
+ * neither do arvx_mc_cells, arvx_mc_mesh_welded, arvx_mc_mesh_refined and what is made of their meshes.
+ * Before the first arvx_mc_mesh the mesh has no triangle: the two downloads return ARVX_OK and copy
+ * nothing. */
 int arvx_mc_mesh(arvx_ctx *ctx, int apply_unseen, int64_t *triangles);
 int arvx_mc_mesh_download(arvx_ctx *ctx, float *verts, uint32_t *face_rgb);
 /* The same triangles with whole face records, 6 uints per triangle: the vertex numbers 3t,
@@ -685,7 +697,13 @@ int arvx_mc_mesh_download_faces(arvx_ctx *ctx, float *verts, uint32_t *faces);
  * contexts only (slab and striped contexts: ARVX_ERR_STATE).  arvx_mc_mesh_welded_download copies
  * 3V floats of positions (voxel units), 6T uints of face records {i0, i1, i2, r, g, b} -- the C++
  * layer's Triangle -- and, if vertex_rgb is not null, 3V floats of vertex colours.  Runs
- * arvx_mc_cells itself; the unwelded mesh of an earlier arvx_mc_mesh stays valid. */
+ * arvx_mc_cells itself; the unwelded mesh of an earlier arvx_mc_mesh stays valid.
+ * The welded mesh is a snapshot of the state and the colours at the call, vertex colours included.  It
+ * lives until the next arvx_mc_mesh_welded: a call that replaces the state, the views or the colours
+ * leaves it, and arvx_mc_mesh_smooth, arvx_mc_mesh_decimate and the render keep working on it.  A new
+ * welded mesh ends the smoothed mesh, the decimated mesh and the render of the old one.  A refused call
+ * (fills whose list is gone, a closure computed with the other apply_unseen) leaves the previous mesh
+ * and everything made of it; before the first mesh the download answers ARVX_ERR_STATE. */
 int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int64_t *triangles);
 int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb);
 
@@ -709,7 +727,9 @@ int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, f
  * It does not synchronise.  The adjacency is built at the first call on a welded mesh and reused
  * by the next ones; arvx_mc_mesh_welded_download keeps returning the lattice positions.
  * arvx_mc_mesh_smooth_download copies 3V floats of positions and 3V floats of unit normals; either
- * pointer may be null (ARVX_ERR_STATE before the first arvx_mc_mesh_smooth on the welded mesh). */
+ * pointer may be null (ARVX_ERR_STATE before the first arvx_mc_mesh_smooth on the welded mesh).
+ * The smoothed mesh is replaced by the next arvx_mc_mesh_smooth and ended by the next
+ * arvx_mc_mesh_welded; nothing else touches it. */
 int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu);
 int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals);
 
@@ -854,8 +874,14 @@ int arvx_mc_mesh_refined_download(arvx_ctx *ctx, float *verts, uint32_t *faces, 
  * arvx_render_agreement when the views were set with masks == NULL.  ARVX_ERR_INVALID: a null M or
  * a non-finite entry of it, W or H out of range, bg_stride < 3 W, a view outside [0, V), null
  * counts.  A refused call leaves the previous render as it was.
- * The render lives until the next render, the next arvx_mc_mesh_welded, or a call that replaces the
- * state the mesh was built from (carve, fast carve, photo carve, state upload, reset).  Device
+ * The render always draws the held welded mesh with the colours that mesh was built with, also after
+ * the state has moved on.  It lives until the next render, the next arvx_mc_mesh_welded, or a call that
+ * replaces the state the mesh was built from: every call that replaces occupied or seen bits other than
+ * arvx_handle_unseen and arvx_closure -- carve, vote carve, fast carve, photo carve,
+ * arvx_components_keep, arvx_morph (all four ops, a radius of 0 too), the state uploads and reset.  The
+ * colour calls, arvx_set_views, arvx_set_images, arvx_handle_unseen, arvx_closure, arvx_components,
+ * arvx_distance, arvx_mc_cells, arvx_mc_mesh, arvx_mc_mesh_refined, arvx_mc_mesh_smooth and
+ * arvx_mc_mesh_decimate keep it.  Device
  * memory, sized at first use and kept: W * H * 8 bytes of keys, the three images (W * H * 11
  * bytes) and the large-footprint list. */
 int arvx_render(arvx_ctx *ctx, const float M[12], int W, int H, const uint8_t *background,

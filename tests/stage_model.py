@@ -16,11 +16,23 @@ use: the vote carve (tests/vote_carve.py) and its counts, photo-consistency carv
 (tests/photo_carve.py), the components' labelling and arvx_components_keep (tests/components.py), the
 distance field and arvx_morph (tests/distance.py).  The vote counts, the labelling and the field are
 results of the context like the colour and closure lists: CtxModel holds them for as long as arvx.h
-says they live, and their downloads are refused before and after.  Not restated: arvx_render*, the
-smoothed and decimated meshes, arvx_color_visible and arvx_ctx_set_projection_assoc."""
+says they live, and their downloads are refused before and after.
+
+So are the products: the cell list, the unwelded, welded, smoothed, decimated and refined meshes, the
+render of the welded mesh and the visible colour pass, each on the numpy restatement its own tests
+use (tests/mesh_weld.py, mesh_smooth.py, mesh_decimate.py, mesh_refine.py, render.py,
+visibility.py).  A product is BUILT by a call (mc_cells_build, mc_mesh_build, weld, smooth, decimate,
+refine, render / render_view / render_agreement, color_visible) and held from then on until arvx.h
+says it ends; its download (mc_cells_list, mc_mesh_held, welded_held, smooth_held, decimate_held,
+refined_held, render_held, surface_visible, view_depth) is an observation of its own that builds
+nothing, so that a sequence can ask for a product after other calls have run.  Not restated:
+arvx_ctx_set_projection_assoc."""
 import numpy as np
 
-from tests import components, distance, mesh_weld, occ_codec, photo_carve, vote_carve
+from tests import (components, distance, mesh_decimate, mesh_refine, mesh_smooth, mesh_weld, occ_codec,
+                   photo_carve, vote_carve)
+from tests import render as render_np
+from tests import visibility
 
 OCC, SEEN, PAINT = 1, 2, 4
 MODEL_COLOR = np.array([50, 168, 141, 1], np.float32)
@@ -158,6 +170,31 @@ class CtxModel:
         self.counts = None     # (background, inside) of a vote carve that kept its counts
         self.comp = None       # per-voxel labels of the last components()
         self.field = None      # [occupancy bytes, border_occupied, the field once somebody asked] of distance()
+        # the products, each None until its first build
+        self.cells = None      # the cell list of the last arvx_mc_cells / mesh that ran it
+        self.mesh = None       # (verts, face_rgb) of the last arvx_mc_mesh
+        self.welded = None     # dict of the last arvx_mc_mesh_welded: verts, faces, face_rgb, vrgb, index
+        self.smoothed = None   # (positions, normals) of the last smooth on self.welded
+        self.decimated = None  # the five arrays of the last decimate on self.welded
+        self.refined = None    # the five arrays of the last arvx_mc_mesh_refined, and its silhouette flags
+        self.rendered = None   # render.Rendered of the last render of self.welded
+        self.visible = None    # (the colour list it filled, visible-view counts, depth buffers)
+
+    RENDER_SIZES = [(96, 72), (50, 37)]  # (the views' size and one that is not)
+
+    def render_camera(self, cam, size):
+        """Camera `cam` of the render cameras -- random ones, none of them a view of the scene --
+        for image size RENDER_SIZES[size]."""
+        from tests import scenes
+        sc = self.sc
+        cams = getattr(sc, "render_cams", None)
+        if cams is None:
+            cams = sc.render_cams = {}
+        if size not in cams:
+            W, H = self.RENDER_SIZES[size]
+            cams[size] = np.ascontiguousarray(scenes.random_cameras(4, 0.512, seed=977 + size, W=W, H=H)[2],
+                                              np.float32)
+        return cams[size][cam]
 
     def resolve(self, name, args):
         """Concrete arguments of an operation recorded with a seed: ("upload_state", seed),
@@ -174,6 +211,12 @@ class CtxModel:
             occ = np.flatnonzero(self.st & OCC)
             idx = occ[rng.random(len(occ)) < 0.4]
             return idx, rng.integers(0, 256, size=(len(idx), 3)).astype(np.float32)
+        if name == "render":  # (camera, size, background seed or None) -> (M, W, H, background)
+            cam, size, bg = args
+            W, H = self.RENDER_SIZES[size]
+            back = None if bg is None else \
+                np.random.default_rng(bg).integers(0, 256, size=(H, W, 3), dtype=np.uint8)
+            return self.render_camera(cam, size), W, H, back
         return args
 
     # ---- calls ----------------------------------------------------------------------------
@@ -192,6 +235,9 @@ class CtxModel:
         if not keep_paint:
             self.paint = None
         self._state_results_gone()
+        # arvx.h, the render: it "lives until ... a call that replaces the state the mesh was built
+        # from"; every caller of this method is in that list, handleUnseen and the closure are not
+        self.rendered = None
 
     def _fills_ok(self):
         if self.fills and self.clo is None:
@@ -416,11 +462,15 @@ class CtxModel:
             self.field[2] = distance.signed_sq(self.field[0], (sc.X, sc.Y, sc.Z), self.field[1])
         return self.field[2]
 
+    def _cells_now(self):
+        """The cell list of the occupancy as it is now -- worked out when mc_cells_list asks for it,
+        from the occupancy kept here (as distance() does with its field)."""
+        return [np.packbits((self.st & OCC).astype(bool)), None]
+
     def mc_cells(self):
-        sc = self.sc
-        occ = np.zeros((self.N, 4), np.float32)
-        occ[:, 3] = self.st & OCC
-        return sc.oracle.mc_cells(sc.X, sc.Y, sc.Z, occ)
+        """arvx_mc_cells and its download at once."""
+        self.mc_cells_build()
+        return self.mc_cells_list()
 
     def mc_model(self, apply_unseen):
         """The model the meshes are built from: the state's occupancy in export_model's colours."""
@@ -430,11 +480,182 @@ class CtxModel:
         return m
 
     def mc_mesh(self, apply_unseen):
-        sc = self.sc
-        return sc.oracle.mc_mesh(sc.X, sc.Y, sc.Z, self.mc_model(apply_unseen))
+        """arvx_mc_mesh and its download at once."""
+        self.mc_mesh_build(apply_unseen)
+        return self.mc_mesh_held()
 
     def mc_mesh_welded(self, apply_unseen):
-        return mesh_weld.weld(*self.mc_mesh(apply_unseen))
+        """arvx_mc_mesh_welded and its download (without the vertex colours) at once."""
+        self.weld(apply_unseen)
+        return self.welded_held()[:3]
+
+    # ---- the products: builds ---------------------------------------------------------------
+    def mc_cells_build(self):
+        """arvx_mc_cells -> the number of cells.  The list is a function of the occupancy at the
+        call; no later call but the next cell walk touches it."""
+        self.cells = self._cells_now()
+        return len(self.mc_cells_list())
+
+    def mc_mesh_build(self, apply_unseen):
+        """arvx_mc_mesh -> T.  "Runs arvx_mc_cells itself"."""
+        sc = self.sc
+        model = self.mc_model(apply_unseen)  # (the refusals)
+        self.mesh = sc.oracle.mc_mesh(sc.X, sc.Y, sc.Z, model)
+        self.cells = self._cells_now()
+        return len(self.mesh[1])
+
+    def weld(self, apply_unseen):
+        """arvx_mc_mesh_welded -> (V, T).  A new welded mesh ends the smoothed and the decimated
+        mesh and the render of the old one; a refused call leaves all of them."""
+        sc = self.sc
+        model = self.mc_model(apply_unseen)
+        verts, faces, face_rgb = mesh_weld.weld(*sc.oracle.mc_mesh(sc.X, sc.Y, sc.Z, model))
+        index = mesh_weld.lattice_index(verts, sc.X, sc.Y)
+        self.welded = dict(verts=verts, faces=faces, face_rgb=face_rgb, index=index,
+                           vrgb=np.ascontiguousarray(model[index, :3]), nbr=None, inc=None)
+        self.cells = self._cells_now()
+        self.smoothed = self.decimated = self.rendered = None
+        return len(verts), len(faces)
+
+    def smooth(self, iterations, lam, mu):
+        """arvx_mc_mesh_smooth on the last welded mesh; the neighbour and incidence structures are
+        the mesh's and are kept with it."""
+        w = self.welded
+        if w is None:
+            raise Refused("no welded mesh")
+        V = len(w["verts"])
+        if w["nbr"] is None:
+            w["nbr"] = mesh_smooth.neighbours(V, w["faces"])
+            w["inc"] = mesh_smooth.incidences(V, w["faces"])
+        self.smoothed = mesh_smooth.smooth(w["verts"], w["faces"], iterations, lam, mu, w["nbr"], w["inc"])
+
+    def decimate(self, cell, source):
+        """arvx_mc_mesh_decimate(cell, source: 0 LATTICE, 1 SMOOTHED) -> (Vd, Td)."""
+        w = self.welded
+        if w is None:
+            raise Refused("no welded mesh")
+        if source == 1 and self.smoothed is None:
+            raise Refused("no smoothed mesh on this welded mesh")
+        records = np.concatenate([w["faces"], w["face_rgb"]], axis=1).astype(np.uint32).reshape(-1, 6)
+        d = mesh_decimate.decimate(w["verts"], records, cell, self.smoothed[0] if source == 1 else None, w["vrgb"])
+        self.decimated = (d["verts"], d["records"].reshape(-1, 6), d["rgb"], d["members"], d["map"])
+        return len(d["verts"]), len(d["records"])
+
+    def refine(self, bisections, apply_unseen):
+        """arvx_mc_mesh_refined -> (Vr, T): a snapshot of the state and the views at the call."""
+        sc = self.sc
+        if bisections > 0 and self.views is None:
+            raise Refused("the bisection needs views")
+        model = self.mc_model(apply_unseen)
+        occ = ((self.st & OCC) != 0).reshape(sc.Z, sc.Y, sc.X)
+        v = self._v() if self.views is not None else slice(0, 0)
+        r = mesh_refine.refine(occ, sc.s, sc.M[v], sc.masks[v], bisections,
+                               rgb=model[:, :3].reshape(sc.Z, sc.Y, sc.X, 3))
+        records = np.concatenate([r["faces"], r["face_rgb"]], axis=1).astype(np.uint32).reshape(-1, 6)
+        self.refined = (r["verts"], records, r["vertex_rgb"], r["edges"], r["cut"], r["silhouette"])
+        self.cells = self._cells_now()
+        return len(r["verts"]), len(records)
+
+    def _render(self, M, W, H, background):
+        w, sc = self.welded, self.sc
+        if w is None:
+            raise Refused("no welded mesh")
+        # the held mesh with the colours it was built with, whatever the state is by now
+        self.rendered = render_np.render(M, sc.s, w["index"], w["vrgb"], sc.X, sc.Y, W, H, background)
+
+    def render(self, M, W, H, background):
+        self._render(M, W, H, background)
+
+    def _view_camera(self, view):
+        if self.welded is None:
+            raise Refused("no welded mesh")
+        if self.views is None:
+            raise Refused("render_view without views")
+        sc = self.sc
+        k = self.views[0] + view
+        return k, sc.M[k], sc.masks.shape[2], sc.masks.shape[1]
+
+    def render_view(self, view):
+        _, M, W, H = self._view_camera(view)
+        self._render(M, W, H, None)
+
+    def render_agreement(self, view):
+        """-> (covered and foreground, covered and background, uncovered and foreground); the render
+        stays as the current one."""
+        k, M, W, H = self._view_camera(view)
+        self._render(M, W, H, None)
+        return render_np.agreement(self.rendered.id, self.sc.masks[k])
+
+    def color_visible(self, mode, tol_voxels):
+        """arvx_color_visible with a tolerance of tol_voxels voxel edges: it fills the colour list,
+        with the colour list's lifetime."""
+        if self.views is None or not self.images:
+            raise Refused("color_visible without views / images")
+        sc, v = self.sc, self._v()
+        base = np.zeros((self.N, 4), np.float32)
+        base[(self.st & OCC) != 0] = (-1, -1, -1, 1)
+        r = visibility.color_visible(sc.X, sc.Y, sc.Z, sc.s, sc.M[v], sc.campos[v], sc.images[v], mode, base,
+                                     np.float32(tol_voxels) * sc.s)
+        idx = r.index[r.has]
+        self.colors = (idx, r.rgba[idx, :3].copy())
+        self.clo = None
+        self.visible = (self.colors, r.views[r.has].astype(np.int32), r.zbuf)
+
+    # ---- the products: downloads that build nothing -------------------------------------------
+    def mc_cells_list(self):
+        if self.cells is None:
+            raise Refused("no cell list")
+        if self.cells[1] is None:
+            sc = self.sc
+            occ = np.zeros((self.N, 4), np.float32)
+            occ[:, 3] = np.unpackbits(self.cells[0])[:self.N]
+            self.cells[1] = sc.oracle.mc_cells(sc.X, sc.Y, sc.Z, occ)
+        return self.cells[1]
+
+    def mc_mesh_held(self):
+        """arvx_mc_mesh_download[_faces]: before any arvx_mc_mesh the mesh has no triangle."""
+        if self.mesh is None:
+            return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.uint32)
+        return self.mesh
+
+    def welded_held(self):
+        w = self.welded
+        if w is None:
+            raise Refused("no welded mesh")
+        return w["verts"], w["faces"], w["face_rgb"], w["vrgb"]
+
+    def smooth_held(self):
+        if self.smoothed is None:
+            raise Refused("no smoothed mesh")
+        return self.smoothed
+
+    def decimate_held(self):
+        if self.decimated is None:
+            raise Refused("no decimated mesh")
+        return self.decimated
+
+    def refined_held(self):
+        if self.refined is None:
+            raise Refused("no refined mesh")
+        return self.refined[:5]
+
+    def render_held(self):
+        if self.rendered is None:
+            raise Refused("no render")
+        return tuple(self.rendered)
+
+    def _visible(self):
+        # the colour list of an arvx_color_visible: gone with the list, and after a plain
+        # arvx_color or arvx_colors_upload filled it anew
+        if self.colors is None or self.visible is None or self.visible[0] is not self.colors:
+            raise Refused("no visible colour result")
+        return self.visible
+
+    def surface_visible(self):
+        return self._visible()[1]
+
+    def view_depth(self, view):
+        return self._visible()[2][view]
 
 
 class HostModel:
