@@ -1185,6 +1185,12 @@ static int fills_without_colours(Ctx *ctx) {
                                     "new views or images since): upload the state and its colours again");
     return ARVX_OK;
 }
+// A closure's list holds the fills of one apply_unseen: calls that read it under the other are refused.
+static int closure_of_other_unseen(const Ctx *ctx, int apply_unseen) {
+    if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
+        return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d", ctx->closure_unseen);
+    return ARVX_OK;
+}
 
 // Bytes of local planes [zl0, zl0 + nz), already in the staging buffer, into the records
 // (+ bit2 into the paint plane).  Ends with a host synchronisation.
@@ -2883,9 +2889,7 @@ int arvx_export_model(arvx_ctx *ctx, float *rgba, int apply_unseen) {
     if (!rgba) return fail(ARVX_ERR_INVALID, "null rgba");
     arvx::CarveParams g = record_params(ctx);
     const int zown = ctx->z0 - ctx->ze0;
-    if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
-        return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d",
-                    ctx->closure_unseen);
+    if (int crc = closure_of_other_unseen(ctx, apply_unseen)) return crc;
     const size_t chunk = (size_t)1 << 24;  // voxels per chunk: 256 MiB of float4
     const size_t nchunk = std::min(chunk, ctx->nvox);
     float4 *d_out = nullptr;
@@ -3314,6 +3318,8 @@ int arvx_closure_download(arvx_ctx *ctx, int64_t *index, float *rgba) {
 
 // ---- marching-cubes hand-off ----------------------------------------------------------
 
+inline Ctx::Plane *Ctx::dec_bits() const { return (Plane *)(dec_rank() + dec_words); }
+
 // The cell list, launched without a synchronisation: up to `cap` cells into the context's buffer,
 // the list's true length in device word *d_total (and the count word kCells after the next sync).
 static int mc_cells_launch(Ctx *ctx, long long cap, const long long **d_total) {
@@ -3352,17 +3358,35 @@ static long long mc_cells_cap(const Ctx *ctx) {
     return list_cap(ctx->pool_mc_cells, sizeof(int4), first_list_cap(v, v + 1e6));
 }
 
-// what the two meshes' kernels read of the state and its colours
-static arvx::McMeshParams mesh_params(const Ctx *ctx, int apply_unseen) {
+// The start of every mesh's attempt: the cell list at room `cap`, what the kernels read of the state and its
+// colours, the cells' triangle offsets (in a pool of their own: the scratch buffer holds mc_cells_launch's arrays).
+struct MeshCells {
     arvx::McMeshParams mp;
-    mp.g = record_params(ctx);
-    mp.paint = paint_plane(ctx);
-    mp.apply_unseen = apply_unseen ? 1 : 0;
-    mp.col = colour_list(ctx);
-    mp.col_rgba = ctx->d_surf_rgba;
-    mp.clo = closure_list(ctx);
-    mp.clo_rgba = (const float4 *)ctx->d_clo_rgba;
-    return mp;
+    const int4 *cells;
+    long long cap;
+    const long long *d_ncells;
+    int *d_off;
+};
+static int mesh_cells_launch(Ctx *ctx, int apply_unseen, long long cap, MeshCells *m) {
+    if (int rc = mc_cells_launch(ctx, cap, &m->d_ncells)) return rc;
+    m->mp.g = record_params(ctx);
+    m->mp.paint = paint_plane(ctx);
+    m->mp.apply_unseen = apply_unseen ? 1 : 0;
+    m->mp.col = colour_list(ctx);
+    m->mp.col_rgba = ctx->d_surf_rgba;
+    m->mp.clo = closure_list(ctx);
+    m->mp.clo_rgba = (const float4 *)ctx->d_clo_rgba;
+    m->cells = (const int4 *)ctx->d_mc_cells;
+    m->cap = cap;
+    ARVX_HIP(ctx->pool_mesh_off.reserve((size_t)(cap + 1) * sizeof(int)));
+    m->d_off = ctx->pool_mesh_off.data();
+    return scan_counts(ctx, nullptr, m->cells, cap, m->d_ncells, m->d_off, Ctx::kTris, nullptr);
+}
+
+// n entries of `entry` bytes to the host, where there are any and the caller wants them
+static int download(Ctx *ctx, void *dst, const void *src, size_t n, size_t entry) {
+    if (n > 0 && dst) ARVX_HIP(hipMemcpyAsync(dst, src, n * entry, hipMemcpyDeviceToHost, ctx->stream));
+    return ARVX_OK;
 }
 
 int arvx_mc_cells(arvx_ctx *ctx, int64_t *count) {
@@ -3373,11 +3397,8 @@ int arvx_mc_cells(arvx_ctx *ctx, int64_t *count) {
     ctx->free_mc();
     ListRoom lists[] = {{Ctx::kCells, mc_cells_cap(ctx), 0}};
     if (int rc = run_lists(ctx, lists, [&] { return mc_cells_launch(ctx, lists[0].cap, nullptr); })) return rc;
-    const long long total = lists[0].total;
-    if (total == 0) ctx->d_mc_cells = nullptr;
-    ctx->mc_count = total;
-    ctx->mc_ready = true;
-    *count = total;
+    ctx->cells_built(lists[0].total);
+    *count = lists[0].total;
     return ARVX_OK;
 }
 
@@ -3399,9 +3420,7 @@ int arvx_mc_mesh(arvx_ctx *ctx, int apply_unseen, int64_t *triangles) {
     if (!triangles) return fail(ARVX_ERR_INVALID, "null argument");
     if (ctx->stripe_world > 1)
         return fail(ARVX_ERR_STATE, "arvx_mc_mesh needs contiguous slabs (neighbour planes)");
-    if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
-        return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d",
-                    ctx->closure_unseen);
+    if (int crc = closure_of_other_unseen(ctx, apply_unseen)) return crc;
     {
         // a slab lists the cells whose upper plane it owns: their corners lie in planes
         // z0 - 1 .. z1 - 1, and plane z0 - 1 (a halo plane) must carry whatever the owned
@@ -3425,44 +3444,32 @@ int arvx_mc_mesh(arvx_ctx *ctx, int apply_unseen, int64_t *triangles) {
     *triangles = 0;
     const long long cells = mc_cells_cap(ctx);
     ListRoom lists[] = {{Ctx::kCells, cells, 0},
-                        {Ctx::kTris, list_cap(ctx->pool_mesh_verts, 9 * sizeof(float), 2 * cells), 0}};
+                        {Ctx::kTris, list_cap(ctx->pool_mesh_verts, 3 * Ctx::kVertexBytes, 2 * cells), 0}};
     const long long &ccap = lists[0].cap, &tcap = lists[1].cap;
     auto attempt = [&]() -> int {
-        const long long *d_ncells = nullptr;
-        if (int rc = mc_cells_launch(ctx, ccap, &d_ncells)) return rc;
-        ARVX_HIP(ctx->pool_mesh_verts.reserve((size_t)tcap * 9 * sizeof(float)));
-        ARVX_HIP(ctx->pool_mesh_rgb.reserve((size_t)tcap * 6 * sizeof(unsigned)));  // face records
-        const arvx::McMeshParams mp = mesh_params(ctx, apply_unseen);
-        // (the scratch buffer holds mc_cells_launch's arrays: the triangle offsets get their own)
-        ARVX_HIP(ctx->pool_mesh_off.reserve((size_t)(ccap + 1) * sizeof(int)));
-        int *d_off = (int *)ctx->pool_mesh_off.p;
-        const long long *d_ntris = nullptr;
-        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, Ctx::kTris, &d_ntris))
-            return rc;
-        return launch(ctx, arvx::mc_mesh_kernel, blocks_for(ccap), 256, mp, (const int4 *)ctx->d_mc_cells, ccap,
-                      d_ncells, tcap, d_off, (float *)ctx->pool_mesh_verts.p,
-                      (unsigned *)ctx->pool_mesh_rgb.p);
+        ARVX_HIP(ctx->pool_mesh_verts.reserve((size_t)tcap * 3 * Ctx::kVertexBytes));
+        ARVX_HIP(ctx->pool_mesh_rgb.reserve((size_t)tcap * Ctx::kFaceBytes));
+        MeshCells mc;
+        if (int rc = mesh_cells_launch(ctx, apply_unseen, ccap, &mc)) return rc;
+        return launch(ctx, arvx::mc_mesh_kernel, blocks_for(ccap), 256, mc.mp, mc.cells, ccap, mc.d_ncells, tcap,
+                      mc.d_off, ctx->pool_mesh_verts.data(), ctx->pool_mesh_rgb.data());
     };
-    if (int rc = run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }))
-        return rc;
-    const long long ncells = lists[0].total, total = lists[1].total;
-    if (ncells == 0) ctx->d_mc_cells = nullptr;
-    ctx->mc_count = ncells;
-    ctx->mc_ready = true;
-    ctx->mesh_tris = total;
-    *triangles = total;
+    ARVX_TRY(run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }));
+    ctx->cells_built(lists[0].total);
+    *triangles = ctx->mesh_tris = lists[1].total;
     return ARVX_OK;
 }
 
 int arvx_mc_mesh_download(arvx_ctx *ctx, float *verts, uint32_t *face_rgb) {
     ARVX_CHECK_CTX(ctx);
     if (!verts || !face_rgb) return fail(ARVX_ERR_INVALID, "null argument");
-    if (ctx->mesh_tris > 0) {
-        ARVX_HIP(hipMemcpyAsync(verts, ctx->pool_mesh_verts.p, (size_t)ctx->mesh_tris * 36,
-                                hipMemcpyDeviceToHost, ctx->stream));
-        // r, g, b of the 24-byte face records
-        ARVX_HIP(hipMemcpy2DAsync(face_rgb, 12, (const uint8_t *)ctx->pool_mesh_rgb.p + 12, 24, 12,
-                                  (size_t)ctx->mesh_tris, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t T = (size_t)ctx->mesh_tris;
+    if (T > 0) {
+        ARVX_TRY(download(ctx, verts, ctx->pool_mesh_verts.data(), T, 3 * Ctx::kVertexBytes));
+        // r, g, b of the face records
+        const size_t rgb = Ctx::kFaceBytes - Ctx::kFaceColour;
+        ARVX_HIP(hipMemcpy2DAsync(face_rgb, rgb, (const uint8_t *)ctx->pool_mesh_rgb.data() + Ctx::kFaceColour,
+                                  Ctx::kFaceBytes, rgb, T, hipMemcpyDeviceToHost, ctx->stream));
         ARVX_SYNC(ctx);
     }
     return ARVX_OK;
@@ -3471,19 +3478,66 @@ int arvx_mc_mesh_download(arvx_ctx *ctx, float *verts, uint32_t *face_rgb) {
 int arvx_mc_mesh_download_faces(arvx_ctx *ctx, float *verts, uint32_t *faces) {
     ARVX_CHECK_CTX(ctx);
     if (!verts || !faces) return fail(ARVX_ERR_INVALID, "null argument");
-    if (ctx->mesh_tris > 0) {
-        ARVX_HIP(hipMemcpyAsync(verts, ctx->pool_mesh_verts.p, (size_t)ctx->mesh_tris * 36,
-                                hipMemcpyDeviceToHost, ctx->stream));
-        ARVX_HIP(hipMemcpyAsync(faces, ctx->pool_mesh_rgb.p, (size_t)ctx->mesh_tris * 24,
-                                hipMemcpyDeviceToHost, ctx->stream));
-        ARVX_SYNC(ctx);
-    }
+    const size_t T = (size_t)ctx->mesh_tris;
+    ARVX_TRY(download(ctx, verts, ctx->pool_mesh_verts.data(), T, 3 * Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, faces, ctx->pool_mesh_rgb.data(), T, Ctx::kFaceBytes));
+    if (T > 0) ARVX_SYNC(ctx);
     return ARVX_OK;
 }
 
-// The welded mesh (mc_weld_kernels.h): vertex plane, cells, triangles and vertices, all launched
-// before the call's ONE synchronisation, as in arvx_mc_mesh; the three lists' lengths come back
-// together, and a mesh that outgrew its buffers is built once more with room for all of it.
+// The frame of the two indexed meshes -- welded: a vertex per surface voxel; refined: a vertex per cut
+// edge.  Occupancy plane -> vertex plane with its chunk counts -> vertex list; cells -> triangles; the
+// vertices: all launched before the call's ONE synchronisation, as in arvx_mc_mesh; the three lists'
+// lengths come back together, and a mesh that outgrew its buffers is built once more with room for all
+// of it.  What differs between the two is in here, and in two callbacks: plane(d_counts) launches the
+// vertex plane's kernel, build(mc, tcap, vcap, d_nverts) the triangle and the vertex kernels.
+struct IndexedMesh {
+    Ctx::Plane *occ, *vtx;  // the grid's occupancy plane; the vertex plane, of grid `vg` (both reserved)
+    arvx::BitGrid vg;
+    arvx::DevArray<arvx::SparseWord> &rank;  // the vertex plane's ranks
+    arvx::DevArray<int> &index;              // the vertex list
+    arvx::DevArray<float> &verts, &rgb;
+    arvx::DevArray<unsigned> &faces;
+    Ctx::Word word;           // the vertex list's count word
+    int per_cell;             // its first room, in cells
+    arvx::DevPool *more;      // a further array of `more_entry` bytes per vertex (null: none)
+    size_t more_entry;
+    long long nverts, ntris;  // out: the lists' lengths
+};
+extern "C++" template <class PlaneKernel, class Build>  // (the entry points' block has C linkage)
+static int indexed_mesh(Ctx *ctx, int apply_unseen, IndexedMesh &m, PlaneKernel plane, Build build) {
+    // the occupancy the cell walk reads (the records: closure fills included), then the vertex plane
+    const size_t nvw = bit_words(m.vg);
+    ARVX_HIP(m.rank.reserve(nvw * sizeof(arvx::SparseWord)));
+    if (int rc = launch_bit_pack(ctx, bit_grid(ctx), 0, 0, m.occ, nullptr)) return rc;
+    int *d_counts = nullptr;
+    if (int rc = chunk_counts(ctx, nvw, &d_counts)) return rc;
+    ARVX_TRY(plane(d_counts));
+    // room: what the last mesh of this kind needed, or a surface's share of the voxels
+    const long long cells = mc_cells_cap(ctx);
+    ListRoom lists[] = {{Ctx::kCells, cells, 0},
+                        {Ctx::kTris, list_cap(m.faces, Ctx::kFaceBytes, 2 * cells), 0},
+                        {m.word, list_cap(m.index, sizeof(int), m.per_cell * cells), 0}};
+    const long long &ccap = lists[0].cap, &tcap = lists[1].cap, &vcap = lists[2].cap;
+    auto attempt = [&]() -> int {
+        ARVX_HIP(m.index.reserve((size_t)vcap * sizeof(int)));
+        ARVX_HIP(m.verts.reserve((size_t)vcap * Ctx::kVertexBytes));
+        ARVX_HIP(m.rgb.reserve((size_t)vcap * Ctx::kVertexBytes));
+        if (m.more) ARVX_HIP(m.more->reserve((size_t)vcap * m.more_entry));
+        ARVX_HIP(m.faces.reserve((size_t)tcap * Ctx::kFaceBytes));
+        const long long *d_nverts = nullptr;
+        ARVX_TRY(bit_compact(ctx, m.vtx, nvw, m.vg, vcap, m.index.data(), m.rank.data(), m.word, &d_nverts));
+        MeshCells mc;
+        if (int rc = mesh_cells_launch(ctx, apply_unseen, ccap, &mc)) return rc;
+        return build(mc, tcap, vcap, d_nverts);
+    };
+    ARVX_TRY(run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }));
+    ctx->cells_built(lists[0].total);
+    m.ntris = lists[1].total, m.nverts = lists[2].total;
+    return ARVX_OK;
+}
+
+// The welded mesh (mc_weld_kernels.h).
 int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int64_t *triangles) {
     ARVX_CHECK_CTX(ctx);
     if (int frc = fills_without_colours(ctx)) return frc;
@@ -3491,9 +3545,7 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     if (!whole_grid(ctx))
         return fail(ARVX_ERR_STATE, "arvx_mc_mesh_welded needs a whole-grid context (vertex indices "
                                     "are ranks in the whole grid)");
-    if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
-        return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d",
-                    ctx->closure_unseen);
+    if (int crc = closure_of_other_unseen(ctx, apply_unseen)) return crc;
     ctx->free_mc();
     ctx->weld_ready = false;
     ctx->smooth_ready = ctx->smooth_csr_ready = false;  // (a new mesh: new CSRs)
@@ -3501,77 +3553,38 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     ctx->render_ready = false;                           // (... and the old one's render goes)
     ctx->weld_verts = ctx->weld_tris = 0;
     *vertices = *triangles = 0;
-    // the vertex plane: occupied voxels with an empty 6-neighbour, in the occupancy the cell walk
-    // reads (the records: closure fills included); its chunk counts come with it
     const arvx::BitGrid g = bit_grid(ctx);
-    const size_t nw = bit_words(g);
-    ARVX_HIP(ctx->pool_weld_planes.reserve(2 * nw * sizeof(unsigned long long)));
-    ARVX_HIP(ctx->pool_weld_rank.reserve(nw * sizeof(arvx::SparseWord)));
-    unsigned long long *d_occ = (unsigned long long *)ctx->pool_weld_planes.p, *d_vtx = d_occ + nw;
-    arvx::SparseWord *d_rank = (arvx::SparseWord *)ctx->pool_weld_rank.p;
-    if (int rc = launch_bit_pack(ctx, g, 0, 0, d_occ, nullptr)) return rc;
-    int *d_counts = nullptr;
-    if (int rc = chunk_counts(ctx, nw, &d_counts)) return rc;
-    ARVX_TRY(launch(ctx, arvx::bit_surface_count_kernel, blocks_for(nw), 256, d_occ, g, 0, ctx->Z, d_vtx,
-                    d_counts));
-    // room: what the last welded mesh needed, or a surface's share of the voxels
-    const long long cells = mc_cells_cap(ctx);
-    ListRoom lists[] = {{Ctx::kCells, cells, 0},
-                        {Ctx::kTris, list_cap(ctx->pool_weld_faces, 6 * sizeof(unsigned), 2 * cells), 0},
-                        {Ctx::kVerts, list_cap(ctx->pool_weld_index, sizeof(int), cells), 0}};
-    const long long &ccap = lists[0].cap, &tcap = lists[1].cap, &vcap = lists[2].cap;
-    auto attempt = [&]() -> int {
-        ARVX_HIP(ctx->pool_weld_index.reserve((size_t)vcap * sizeof(int)));
-        ARVX_HIP(ctx->pool_weld_verts.reserve((size_t)vcap * 3 * sizeof(float)));
-        ARVX_HIP(ctx->pool_weld_rgb.reserve((size_t)vcap * 3 * sizeof(float)));
-        ARVX_HIP(ctx->pool_weld_faces.reserve((size_t)tcap * 6 * sizeof(unsigned)));
-        const long long *d_nverts = nullptr;
-        if (int rc = bit_compact(ctx, d_vtx, nw, g, vcap, (int *)ctx->pool_weld_index.p, d_rank,
-                                 Ctx::kVerts, &d_nverts))
-            return rc;
-        const long long *d_ncells = nullptr;
-        if (int rc = mc_cells_launch(ctx, ccap, &d_ncells)) return rc;
-        const arvx::McMeshParams mp = mesh_params(ctx, apply_unseen);
-        ARVX_HIP(ctx->pool_mesh_off.reserve((size_t)(ccap + 1) * sizeof(int)));
-        int *d_off = (int *)ctx->pool_mesh_off.p;
-        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, Ctx::kTris, nullptr))
-            return rc;
-        ARVX_TRY(launch(ctx, arvx::mc_weld_tri_kernel, blocks_for(ccap), 256, mp, arvx::SparseList{d_rank},
-                        (const int4 *)ctx->d_mc_cells, ccap, d_ncells, tcap, d_off,
-                        (unsigned *)ctx->pool_weld_faces.p));
-        return launch(ctx, arvx::mc_weld_vertex_kernel, blocks_for(vcap), 256, mp,
-                      (const int *)ctx->pool_weld_index.p, vcap, d_nverts, (float *)ctx->pool_weld_verts.p,
-                      (float *)ctx->pool_weld_rgb.p);
+    ctx->weld_words = bit_words(g);
+    ARVX_HIP(ctx->pool_weld_planes.reserve(2 * ctx->weld_words * sizeof(Ctx::Plane)));
+    IndexedMesh m{ctx->weld_occ(), ctx->weld_vtx(), g, ctx->pool_weld_rank, ctx->pool_weld_index,
+                  ctx->pool_weld_verts, ctx->pool_weld_rgb, ctx->pool_weld_faces, Ctx::kVerts, 1, nullptr, 0, 0, 0};
+    // the vertex plane: occupied voxels with an empty 6-neighbour
+    auto plane = [&](int *d_counts) {
+        return launch(ctx, arvx::bit_surface_count_kernel, blocks_for(ctx->weld_words), 256, m.occ, g, 0, ctx->Z,
+                      m.vtx, d_counts);
     };
-    if (int rc = run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }))
-        return rc;
-    const long long ncells = lists[0].total, ntris = lists[1].total, nverts = lists[2].total;
-    if (ncells == 0) ctx->d_mc_cells = nullptr;
-    ctx->mc_count = ncells;
-    ctx->mc_ready = true;
-    ctx->weld_verts = nverts;
-    ctx->weld_tris = ntris;
+    auto build = [&](const MeshCells &mc, long long tcap, long long vcap, const long long *d_nverts) -> int {
+        ARVX_TRY(launch(ctx, arvx::mc_weld_tri_kernel, blocks_for(mc.cap), 256, mc.mp,
+                        arvx::SparseList{m.rank.data()}, mc.cells, mc.cap, mc.d_ncells, tcap, mc.d_off,
+                        m.faces.data()));
+        return launch(ctx, arvx::mc_weld_vertex_kernel, blocks_for(vcap), 256, mc.mp, m.index.data(), vcap,
+                      d_nverts, m.verts.data(), m.rgb.data());
+    };
+    if (int rc = indexed_mesh(ctx, apply_unseen, m, plane, build)) return rc;
+    *vertices = ctx->weld_verts = m.nverts;
+    *triangles = ctx->weld_tris = m.ntris;
     ctx->weld_ready = true;
-    *vertices = nverts;
-    *triangles = ntris;
     return ARVX_OK;
 }
 
 int arvx_mc_mesh_welded_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb) {
     ARVX_CHECK_CTX(ctx);
     if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
-    if ((ctx->weld_verts > 0 && !verts) || (ctx->weld_tris > 0 && !faces))
-        return fail(ARVX_ERR_INVALID, "null argument");
-    if (ctx->weld_verts > 0) {
-        ARVX_HIP(hipMemcpyAsync(verts, ctx->pool_weld_verts.p, (size_t)ctx->weld_verts * 12,
-                                hipMemcpyDeviceToHost, ctx->stream));
-        if (vertex_rgb)
-            ARVX_HIP(hipMemcpyAsync(vertex_rgb, ctx->pool_weld_rgb.p, (size_t)ctx->weld_verts * 12,
-                                    hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (ctx->weld_tris > 0)
-        ARVX_HIP(hipMemcpyAsync(faces, ctx->pool_weld_faces.p, (size_t)ctx->weld_tris * 24,
-                                hipMemcpyDeviceToHost, ctx->stream));
+    const size_t V = (size_t)ctx->weld_verts, T = (size_t)ctx->weld_tris;
+    if ((V > 0 && !verts) || (T > 0 && !faces)) return fail(ARVX_ERR_INVALID, "null argument");
+    ARVX_TRY(download(ctx, verts, ctx->pool_weld_verts.data(), V, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, vertex_rgb, ctx->pool_weld_rgb.data(), V, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, faces, ctx->pool_weld_faces.data(), T, Ctx::kFaceBytes));
     ARVX_SYNC(ctx);
     return ARVX_OK;
 }
@@ -3585,30 +3598,28 @@ static int smooth_csr(Ctx *ctx) {
     const long long V = ctx->weld_verts, T = ctx->weld_tris;
     const long long ncap = std::min(26 * V, 6 * T), icap = 3 * T;
     const unsigned blocks_v = blocks_for(V + 1), blocks_t = blocks_for(T);
-    // masks (V) | incidence counts (V + 1) | neighbour counts (V + 1) | their two offsets (V + 1 each)
-    ARVX_HIP(ctx->pool_smooth_csr.reserve((size_t)(5 * V + 4) * sizeof(int)));
+    ARVX_HIP(ctx->pool_smooth_csr.reserve(ctx->smooth_csr_bytes()));
     ARVX_HIP(ctx->pool_smooth_nbr.reserve((size_t)std::max(ncap, 1ll) * sizeof(unsigned)));
     ARVX_HIP(ctx->pool_smooth_inc.reserve((size_t)std::max(icap, 1ll) * sizeof(unsigned)));
-    unsigned *masks = (unsigned *)ctx->pool_smooth_csr.p;
-    int *icount = (int *)(masks + V), *ncount = icount + V + 1, *noff = ncount + V + 1, *ioff = noff + V + 1;
-    unsigned *nbr = (unsigned *)ctx->pool_smooth_nbr.p, *inc = (unsigned *)ctx->pool_smooth_inc.p;
-    const unsigned *faces = (const unsigned *)ctx->pool_weld_faces.p;
-    const int *index = (const int *)ctx->pool_weld_index.p;
-    ARVX_HIP(hipMemsetAsync(masks, 0, (size_t)(2 * V + 1) * sizeof(int), ctx->stream));  // masks, icount
-    if (T > 0) {
+    unsigned *masks = ctx->smooth_masks();
+    int *icount = ctx->smooth_icount(), *ncount = ctx->smooth_ncount(), *noff = ctx->smooth_noff(),
+        *ioff = ctx->smooth_ioff();
+    unsigned *nbr = ctx->pool_smooth_nbr.data(), *inc = ctx->pool_smooth_inc.data(), *faces = ctx->pool_weld_faces.data();
+    const int *index = ctx->pool_weld_index.data();
+    // (the masks and the incidence counts: all that lies before the neighbour counts)
+    ARVX_HIP(hipMemsetAsync(masks, 0, (size_t)(ncount - (int *)masks) * sizeof(int), ctx->stream));
+    if (T > 0)
         ARVX_TRY(launch(ctx, arvx::mc_smooth_adjacency_kernel, blocks_t, 256, faces, T, V, index, ctx->X,
                         ctx->Y, masks, icount));
-    }
     ARVX_TRY(launch(ctx, arvx::mc_smooth_degree_kernel, blocks_v, 256, masks, V, ncount));
     // (a total no call reads)
     if (int rc = scan_counts(ctx, ncount, nullptr, V + 1, nullptr, noff, Ctx::kSmoothScan, nullptr)) return rc;
     if (int rc = scan_counts(ctx, icount, nullptr, V + 1, nullptr, ioff, Ctx::kSmoothScan, nullptr)) return rc;
     ARVX_TRY(launch(ctx, arvx::mc_smooth_neighbours_kernel, blocks_v, 256, masks, V, index, ctx->X, ctx->Y,
-                    arvx::SparseList{(const arvx::SparseWord *)ctx->pool_weld_rank.p}, noff, ncap, nbr));
-    if (T > 0) {
+                    arvx::SparseList{ctx->pool_weld_rank.data()}, noff, ncap, nbr));
+    if (T > 0)
         ARVX_TRY(launch(ctx, arvx::mc_smooth_incidence_kernel, blocks_t, 256, faces, T, V, icount, ioff, icap,
                         inc));
-    }
     ARVX_TRY(launch(ctx, arvx::mc_smooth_sort_kernel, blocks_v, 256, ioff, V, icap, inc));
     ctx->smooth_csr_ready = true;
     return ARVX_OK;
@@ -3629,30 +3640,24 @@ int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu) {
     if (!ctx->smooth_csr_ready)
         if (int rc = smooth_csr(ctx)) return rc;
     const long long ncap = std::min(26 * V, 6 * T), icap = 3 * T;
-    const unsigned *faces = (const unsigned *)ctx->pool_weld_faces.p;
-    int *noff = (int *)ctx->pool_smooth_csr.p + V + 2 * (V + 1), *ioff = noff + V + 1;
     const unsigned blocks_v = blocks_for(V), blocks_t = blocks_for(T);
     // the steps: welded positions -> buffer 1 -> buffer 2 -> buffer 1 ...
-    ARVX_HIP(ctx->pool_smooth_verts.reserve((size_t)6 * V * sizeof(float)));
-    float *buf[3] = {(float *)ctx->pool_weld_verts.p, (float *)ctx->pool_smooth_verts.p,
-                     (float *)ctx->pool_smooth_verts.p + 3 * V};
+    ARVX_HIP(ctx->pool_smooth_verts.reserve((size_t)2 * V * Ctx::kVertexBytes));
     int q = 0;
     for (int s = 0; s < 2 * iterations; ++s) {
         const int next = q == 1 ? 2 : 1;
-        ARVX_TRY(launch(ctx, arvx::mc_smooth_step_kernel, blocks_v, 256, buf[q], V, noff, ncap,
-                        (const unsigned *)ctx->pool_smooth_nbr.p, (s & 1) ? mu : lambda, buf[next]));
+        ARVX_TRY(launch(ctx, arvx::mc_smooth_step_kernel, blocks_v, 256, ctx->smooth_xyz(q), V, ctx->smooth_noff(),
+                        ncap, ctx->pool_smooth_nbr.data(), (s & 1) ? mu : lambda, ctx->smooth_xyz(next)));
         q = next;
     }
     // the normals of the final positions
     ARVX_HIP(ctx->pool_smooth_cross.reserve((size_t)std::max(3 * T, 1ll) * sizeof(float)));
-    ARVX_HIP(ctx->pool_smooth_normals.reserve((size_t)3 * V * sizeof(float)));
-    if (T > 0) {
-        ARVX_TRY(launch(ctx, arvx::mc_smooth_cross_kernel, blocks_t, 256, faces, T, buf[q], V,
-                        (float *)ctx->pool_smooth_cross.p));
-    }
-    ARVX_TRY(launch(ctx, arvx::mc_smooth_normal_kernel, blocks_v, 256, ioff, V, icap,
-                    (const unsigned *)ctx->pool_smooth_inc.p, (const float *)ctx->pool_smooth_cross.p, T,
-                    (float *)ctx->pool_smooth_normals.p));
+    ARVX_HIP(ctx->pool_smooth_normals.reserve((size_t)V * Ctx::kVertexBytes));
+    if (T > 0)
+        ARVX_TRY(launch(ctx, arvx::mc_smooth_cross_kernel, blocks_t, 256, ctx->pool_weld_faces.data(), T,
+                        ctx->smooth_xyz(q), V, ctx->pool_smooth_cross.data()));
+    ARVX_TRY(launch(ctx, arvx::mc_smooth_normal_kernel, blocks_v, 256, ctx->smooth_ioff(), V, icap,
+                    ctx->pool_smooth_inc.data(), ctx->pool_smooth_cross.data(), T, ctx->pool_smooth_normals.data()));
     ctx->smooth_q = q;
     ctx->smooth_ready = true;
     return ARVX_OK;
@@ -3661,15 +3666,9 @@ int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu) {
 int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals) {
     ARVX_CHECK_CTX(ctx);
     if (!ctx->smooth_ready) return fail(ARVX_ERR_STATE, "no smoothed mesh (call arvx_mc_mesh_smooth)");
-    const long long V = ctx->weld_verts;
-    if (V > 0 && verts) {
-        const float *q = ctx->smooth_q == 0 ? (const float *)ctx->pool_weld_verts.p
-                                            : (const float *)ctx->pool_smooth_verts.p + (ctx->smooth_q - 1) * 3 * V;
-        ARVX_HIP(hipMemcpyAsync(verts, q, (size_t)V * 12, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    if (V > 0 && normals)
-        ARVX_HIP(hipMemcpyAsync(normals, ctx->pool_smooth_normals.p, (size_t)V * 12, hipMemcpyDeviceToHost,
-                                ctx->stream));
+    const size_t V = (size_t)ctx->weld_verts;
+    ARVX_TRY(download(ctx, verts, ctx->smooth_xyz(ctx->smooth_q), V, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, normals, ctx->pool_smooth_normals.data(), V, Ctx::kVertexBytes));
     ARVX_HIP(hipStreamSynchronize(ctx->stream));
     if (int rc = check_fault(ctx)) {  // (a scan gave up: the CSRs are built again)
         ctx->smooth_ready = ctx->smooth_csr_ready = false;
@@ -3704,7 +3703,7 @@ int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices
     d.CX = (ctx->X + cell - 1) / cell, d.CY = (ctx->Y + cell - 1) / cell, d.CZ = (ctx->Z + cell - 1) / cell;
     d.CXW = (d.CX + 63) / 64;
     const arvx::BitGrid cg{d.CX, d.CY, d.CZ, d.CXW};
-    const size_t nw = (size_t)d.XW * ctx->Y * ctx->Z, ncw = (size_t)d.CXW * d.CY * d.CZ;
+    const size_t ncw = ctx->dec_words = bit_words(cg);
     const long long vcap = std::min<long long>(V, (long long)d.CX * d.CY * d.CZ);
     // the cluster plane, then its ranks (16-byte entries first)
     ARVX_HIP(ctx->pool_dec_planes.reserve(ncw * (sizeof(arvx::SparseWord) + sizeof(unsigned long long))));
@@ -3713,33 +3712,30 @@ int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices
     ARVX_HIP(ctx->pool_dec_rgb.reserve((size_t)vcap * 3 * sizeof(float)));
     ARVX_HIP(ctx->pool_dec_members.reserve((size_t)vcap * sizeof(int)));
     ARVX_HIP(ctx->pool_dec_map.reserve((size_t)V * sizeof(int)));
-    arvx::SparseWord *d_crank = (arvx::SparseWord *)ctx->pool_dec_planes.p;
-    unsigned long long *d_cbits = (unsigned long long *)(d_crank + ncw);
-    int *d_cidx = (int *)ctx->pool_dec_index.p, *d_map = (int *)ctx->pool_dec_map.p;
-    const unsigned long long *d_vtx = (const unsigned long long *)ctx->pool_weld_planes.p + nw;
-    const arvx::SparseList vtx{(const arvx::SparseWord *)ctx->pool_weld_rank.p};
-    const float *q = (source == ARVX_DECIMATE_LATTICE || ctx->smooth_q == 0)
-                         ? (const float *)ctx->pool_weld_verts.p
-                         : (const float *)ctx->pool_smooth_verts.p + (ctx->smooth_q - 1) * 3 * V;
+    arvx::SparseWord *d_crank = ctx->dec_rank();
+    Ctx::Plane *d_cbits = ctx->dec_bits();
+    int *d_cidx = ctx->pool_dec_index.data(), *d_map = ctx->pool_dec_map.data();
+    const arvx::SparseList vtx{ctx->pool_weld_rank.data()};
+    const float *q = ctx->smooth_xyz(source == ARVX_DECIMATE_LATTICE ? 0 : ctx->smooth_q);
     // (the control block holds both totals: it must not move between the compaction and the scan)
     if (int rc = compact_control(ctx, (size_t)((T + arvx::kScanChunk - 1) / arvx::kScanChunk), nullptr)) return rc;
     int *d_counts = nullptr;
     if (int rc = chunk_counts(ctx, ncw, &d_counts)) return rc;
-    ARVX_TRY(launch(ctx, arvx::mc_decimate_plane_kernel, blocks_for(ncw), 256, d_vtx, d, d_cbits, d_counts));
+    ARVX_TRY(launch(ctx, arvx::mc_decimate_plane_kernel, blocks_for(ncw), 256, ctx->weld_vtx(), d, d_cbits, d_counts));
     const long long *d_nverts = nullptr;
     if (int rc = bit_compact(ctx, d_cbits, ncw, cg, vcap, d_cidx, d_crank, Ctx::kDecVerts, &d_nverts)) return rc;
     ARVX_TRY(launch(ctx, arvx::mc_decimate_vertex_kernel, blocks_for(vcap), 256, d_cidx, vcap, d_nverts, d, vtx,
-                    V, q, (const float *)ctx->pool_weld_rgb.p, (float *)ctx->pool_dec_verts.p,
-                    (float *)ctx->pool_dec_rgb.p, (int *)ctx->pool_dec_members.p));
-    ARVX_TRY(launch(ctx, arvx::mc_decimate_map_kernel, blocks_for(V), 256, (const int *)ctx->pool_weld_index.p, V,
-                    d, arvx::SparseList{d_crank}, d_map));
+                    V, q, ctx->pool_weld_rgb.data(), ctx->pool_dec_verts.data(), ctx->pool_dec_rgb.data(),
+                    ctx->pool_dec_members.data()));
+    ARVX_TRY(launch(ctx, arvx::mc_decimate_map_kernel, blocks_for(V), 256, ctx->pool_weld_index.data(), V, d,
+                    arvx::SparseList{d_crank}, d_map));
     if (T > 0) {
-        ARVX_HIP(ctx->pool_dec_faces.reserve((size_t)T * 6 * sizeof(unsigned)));
+        ARVX_HIP(ctx->pool_dec_faces.reserve((size_t)T * Ctx::kFaceBytes));
         ARVX_HIP(ctx->pool_dec_flags.reserve((size_t)T * 2 * sizeof(int)));
         ARVX_HIP(ctx->pool_dec_slots.reserve((size_t)vcap * arvx::kDecSlots * sizeof(unsigned)));
-        const unsigned *faces = (const unsigned *)ctx->pool_weld_faces.p;
-        unsigned *d_slots = (unsigned *)ctx->pool_dec_slots.p;
-        int *d_flags = (int *)ctx->pool_dec_flags.p, *d_off = d_flags + T;
+        const unsigned *faces = ctx->pool_weld_faces.data();
+        unsigned *d_slots = ctx->pool_dec_slots.data();
+        int *d_flags = ctx->dec_flags(), *d_off = ctx->dec_off();
         const unsigned blocks_t = blocks_for(T);
         ARVX_HIP(hipMemsetAsync(d_slots, 0xff, (size_t)vcap * arvx::kDecSlots * sizeof(unsigned), ctx->stream));
         ARVX_TRY(launch(ctx, arvx::mc_decimate_claim_kernel, blocks_t, 256, faces, T, V, d_map, d_cidx, vcap,
@@ -3748,7 +3744,7 @@ int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices
                         d_nverts, d, d_slots, d_flags));
         if (int rc = scan_counts(ctx, d_flags, nullptr, T, nullptr, d_off, Ctx::kDecTris, nullptr)) return rc;
         ARVX_TRY(launch(ctx, arvx::mc_decimate_write_kernel, blocks_t, 256, faces, T, V, d_map, d_flags,
-                        d_off, T, (unsigned *)ctx->pool_dec_faces.p));
+                        d_off, T, ctx->pool_dec_faces.data()));
     }
     ARVX_SYNC(ctx);
     const long long nverts = host_total(ctx, Ctx::kDecVerts), ntris = T > 0 ? host_total(ctx, Ctx::kDecTris) : 0;
@@ -3767,24 +3763,17 @@ int arvx_mc_mesh_decimate_download(arvx_ctx *ctx, float *verts, uint32_t *faces,
     ARVX_CHECK_CTX(ctx);
     if (!ctx->dec_ready) return fail(ARVX_ERR_STATE, "no decimated mesh (call arvx_mc_mesh_decimate)");
     const size_t Vd = (size_t)ctx->dec_verts, Td = (size_t)ctx->dec_tris, V = (size_t)ctx->weld_verts;
-    if (Vd > 0 && verts)
-        ARVX_HIP(hipMemcpyAsync(verts, ctx->pool_dec_verts.p, Vd * 12, hipMemcpyDeviceToHost, ctx->stream));
-    if (Td > 0 && faces)
-        ARVX_HIP(hipMemcpyAsync(faces, ctx->pool_dec_faces.p, Td * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (Vd > 0 && vertex_rgb)
-        ARVX_HIP(hipMemcpyAsync(vertex_rgb, ctx->pool_dec_rgb.p, Vd * 12, hipMemcpyDeviceToHost, ctx->stream));
-    if (Vd > 0 && members)
-        ARVX_HIP(hipMemcpyAsync(members, ctx->pool_dec_members.p, Vd * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (V > 0 && map)
-        ARVX_HIP(hipMemcpyAsync(map, ctx->pool_dec_map.p, V * 4, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_TRY(download(ctx, verts, ctx->pool_dec_verts.data(), Vd, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, faces, ctx->pool_dec_faces.data(), Td, Ctx::kFaceBytes));
+    ARVX_TRY(download(ctx, vertex_rgb, ctx->pool_dec_rgb.data(), Vd, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, members, ctx->pool_dec_members.data(), Vd, sizeof(int)));
+    ARVX_TRY(download(ctx, map, ctx->pool_dec_map.data(), V, sizeof(int)));
     ARVX_SYNC(ctx);
     return ARVX_OK;
 }
 
-// The refined mesh (mc_refine_kernels.h): occupancy plane, edge plane, cells, triangles and the
-// bisection, all launched before the call's ONE synchronisation, as in arvx_mc_mesh_welded; the three
-// lists' lengths come back together, and a mesh that outgrew its buffers is built once more with room
-// for all of it.  Its buffers are its own: the welded mesh and what was made of it stay as they were.
+// The refined mesh (mc_refine_kernels.h): the welded mesh's frame over the edge plane, the bisection in its
+// vertex kernel.  Its buffers are its own: the welded mesh and what was made of it stay as they were.
 int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_t *vertices,
                          int64_t *triangles) {
     ARVX_CHECK_CTX(ctx);
@@ -3801,74 +3790,40 @@ int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_
     if (bisections > 0 && !ctx->views_ready)
         return fail(ARVX_ERR_STATE, "the bisection needs views with masks (arvx_set_views)");
     if (int frc = fills_without_colours(ctx)) return frc;
-    if (ctx->closure_ready && (apply_unseen != 0) != (ctx->closure_unseen != 0))
-        return fail(ARVX_ERR_STATE, "arvx_closure was computed with apply_unseen=%d", ctx->closure_unseen);
+    if (int crc = closure_of_other_unseen(ctx, apply_unseen)) return crc;
     ctx->free_mc();
     ctx->ref_ready = false;
     ctx->ref_verts = ctx->ref_tris = 0;
     *vertices = *triangles = 0;
-    // the occupancy the cell walk reads (the records: closure fills included), then the edge plane
-    // with its chunk counts
     const arvx::BitGrid g = bit_grid(ctx);
-    const size_t nw = bit_words(g), new_ = bit_words(eg);
-    ARVX_HIP(ctx->pool_ref_planes.reserve((nw + new_) * sizeof(unsigned long long)));
-    ARVX_HIP(ctx->pool_ref_rank.reserve(new_ * sizeof(arvx::SparseWord)));
-    unsigned long long *d_occ = (unsigned long long *)ctx->pool_ref_planes.p, *d_edge = d_occ + nw;
-    arvx::SparseWord *d_rank = (arvx::SparseWord *)ctx->pool_ref_rank.p;
-    if (int rc = launch_bit_pack(ctx, g, 0, 0, d_occ, nullptr)) return rc;
-    int *d_counts = nullptr;
-    if (int rc = chunk_counts(ctx, new_, &d_counts)) return rc;
-    ARVX_TRY(launch(ctx, arvx::mc_refine_plane_kernel, blocks_for(new_), 256, d_occ, g, eg, d_edge, d_counts));
+    ctx->ref_words = bit_words(g);
+    ARVX_HIP(ctx->pool_ref_planes.reserve((ctx->ref_words + bit_words(eg)) * sizeof(Ctx::Plane)));
+    // (three cut edges per surface voxel, about)
+    IndexedMesh m{ctx->ref_occ(), ctx->ref_edge_plane(), eg, ctx->pool_ref_rank, ctx->pool_ref_index,
+                  ctx->pool_ref_verts, ctx->pool_ref_rgb, ctx->pool_ref_faces, Ctx::kRefVerts, 3,
+                  &ctx->pool_ref_edges, (Ctx::kRefEdgeInts + 1) * sizeof(int), 0, 0};
+    auto plane = [&](int *d_counts) {
+        return launch(ctx, arvx::mc_refine_plane_kernel, blocks_for(bit_words(eg)), 256, m.occ, g, eg, m.vtx,
+                      d_counts);
+    };
     arvx::RefineViews vw{};
     if (ctx->views_ready)  // (without masks only bisections == 0 gets here: every cut is the midpoint)
         vw = arvx::RefineViews{ctx->M(), ctx->bg(), ctx->V, ctx->W, ctx->H, ctx->bgWords, ctx->s};
-    // room: what the last refined mesh needed, or a surface's share of the voxels (three cut edges
-    // per surface voxel, about)
-    const long long cells = mc_cells_cap(ctx);
-    ListRoom lists[] = {{Ctx::kCells, cells, 0},
-                        {Ctx::kTris, list_cap(ctx->pool_ref_faces, 6 * sizeof(unsigned), 2 * cells), 0},
-                        {Ctx::kRefVerts, list_cap(ctx->pool_ref_index, sizeof(int), 3 * cells), 0}};
-    const long long &ccap = lists[0].cap, &tcap = lists[1].cap, &vcap = lists[2].cap;
-    auto attempt = [&]() -> int {
-        ARVX_HIP(ctx->pool_ref_index.reserve((size_t)vcap * sizeof(int)));
-        ARVX_HIP(ctx->pool_ref_verts.reserve((size_t)vcap * 3 * sizeof(float)));
-        ARVX_HIP(ctx->pool_ref_rgb.reserve((size_t)vcap * 3 * sizeof(float)));
-        ARVX_HIP(ctx->pool_ref_edges.reserve((size_t)vcap * 5 * sizeof(int)));  // 4 ints of edge, then n
-        ARVX_HIP(ctx->pool_ref_faces.reserve((size_t)tcap * 6 * sizeof(unsigned)));
-        const long long *d_nverts = nullptr;
-        if (int rc = bit_compact(ctx, d_edge, new_, eg, vcap, (int *)ctx->pool_ref_index.p, d_rank,
-                                 Ctx::kRefVerts, &d_nverts))
-            return rc;
-        const long long *d_ncells = nullptr;
-        if (int rc = mc_cells_launch(ctx, ccap, &d_ncells)) return rc;
-        const arvx::McMeshParams mp = mesh_params(ctx, apply_unseen);
-        ARVX_HIP(ctx->pool_mesh_off.reserve((size_t)(ccap + 1) * sizeof(int)));
-        int *d_off = (int *)ctx->pool_mesh_off.p;
-        if (int rc = scan_counts(ctx, nullptr, (const int4 *)ctx->d_mc_cells, ccap, d_ncells, d_off, Ctx::kTris, nullptr))
-            return rc;
-        ARVX_TRY(launch(ctx, arvx::mc_refine_tri_kernel, blocks_for(ccap), 256, mp, arvx::SparseList{d_rank}, eg,
-                        (const int4 *)ctx->d_mc_cells, ccap, d_ncells, tcap, d_off,
-                        (unsigned *)ctx->pool_ref_faces.p));
-        int *d_edges = (int *)ctx->pool_ref_edges.p;
+    auto build = [&](const MeshCells &mc, long long tcap, long long vcap, const long long *d_nverts) -> int {
+        ARVX_TRY(launch(ctx, arvx::mc_refine_tri_kernel, blocks_for(mc.cap), 256, mc.mp,
+                        arvx::SparseList{m.rank.data()}, eg, mc.cells, mc.cap, mc.d_ncells, tcap, mc.d_off,
+                        m.faces.data()));
+        ctx->ref_cap = vcap;  // (where the cut numerators start)
         return by_assoc(ctx, [&](auto left) {
-            return launch(ctx, arvx::mc_refine_vertex_kernel<decltype(left)::value>, blocks_for(vcap), 256, mp, vw,
-                          d_occ, g, (const int *)ctx->pool_ref_index.p, vcap, d_nverts, bisections,
-                          (float *)ctx->pool_ref_verts.p, (float *)ctx->pool_ref_rgb.p, d_edges,
-                          d_edges + 4 * vcap);
+            return launch(ctx, arvx::mc_refine_vertex_kernel<decltype(left)::value>, blocks_for(vcap), 256, mc.mp,
+                          vw, m.occ, g, m.index.data(), vcap, d_nverts, bisections, m.verts.data(), m.rgb.data(),
+                          ctx->ref_edges(), ctx->ref_cut());
         });
     };
-    if (int rc = run_lists(ctx, lists, attempt, [&] { return room_for_missing_cells(lists[0], lists[1]); }))
-        return rc;
-    const long long ncells = lists[0].total, ntris = lists[1].total, nverts = lists[2].total;
-    if (ncells == 0) ctx->d_mc_cells = nullptr;
-    ctx->mc_count = ncells;
-    ctx->mc_ready = true;
-    ctx->ref_verts = nverts;
-    ctx->ref_tris = ntris;
-    ctx->ref_cap = vcap;
+    if (int rc = indexed_mesh(ctx, apply_unseen, m, plane, build)) return rc;
+    *vertices = ctx->ref_verts = m.nverts;
+    *triangles = ctx->ref_tris = m.ntris;
     ctx->ref_ready = true;
-    *vertices = nverts;
-    *triangles = ntris;
     return ARVX_OK;
 }
 
@@ -3877,18 +3832,11 @@ int arvx_mc_mesh_refined_download(arvx_ctx *ctx, float *verts, uint32_t *faces, 
     ARVX_CHECK_CTX(ctx);
     if (!ctx->ref_ready) return fail(ARVX_ERR_STATE, "no refined mesh (call arvx_mc_mesh_refined)");
     const size_t Vr = (size_t)ctx->ref_verts, T = (size_t)ctx->ref_tris;
-    const int *d_edges = (const int *)ctx->pool_ref_edges.p;
-    if (Vr > 0 && verts)
-        ARVX_HIP(hipMemcpyAsync(verts, ctx->pool_ref_verts.p, Vr * 12, hipMemcpyDeviceToHost, ctx->stream));
-    if (T > 0 && faces)
-        ARVX_HIP(hipMemcpyAsync(faces, ctx->pool_ref_faces.p, T * 24, hipMemcpyDeviceToHost, ctx->stream));
-    if (Vr > 0 && vertex_rgb)
-        ARVX_HIP(hipMemcpyAsync(vertex_rgb, ctx->pool_ref_rgb.p, Vr * 12, hipMemcpyDeviceToHost, ctx->stream));
-    if (Vr > 0 && edges)
-        ARVX_HIP(hipMemcpyAsync(edges, d_edges, Vr * 16, hipMemcpyDeviceToHost, ctx->stream));
-    if (Vr > 0 && cut)
-        ARVX_HIP(hipMemcpyAsync(cut, d_edges + 4 * (size_t)ctx->ref_cap, Vr * 4, hipMemcpyDeviceToHost,
-                                ctx->stream));
+    ARVX_TRY(download(ctx, verts, ctx->pool_ref_verts.data(), Vr, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, faces, ctx->pool_ref_faces.data(), T, Ctx::kFaceBytes));
+    ARVX_TRY(download(ctx, vertex_rgb, ctx->pool_ref_rgb.data(), Vr, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, edges, ctx->ref_edges(), Vr, Ctx::kRefEdgeInts * sizeof(int)));
+    ARVX_TRY(download(ctx, cut, ctx->ref_cut(), Vr, sizeof(int)));
     ARVX_SYNC(ctx);
     return ARVX_OK;
 }
@@ -3957,7 +3905,7 @@ static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *
     }
     if (n > 0) {
         arvx::RenderSplatParams sp;
-        sp.index = (const int *)ctx->pool_weld_index.p;
+        sp.index = ctx->pool_weld_index.data();
         sp.n = n;
         sp.X = ctx->X;
         sp.Y = ctx->Y;
@@ -3978,7 +3926,7 @@ static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *
                         large_cap, keys, W, ctx->word_dev(Ctx::kRenderNeed)));
     }
     ARVX_TRY(launch(ctx, arvx::render_resolve_kernel, blocks_for(npix), 256, keys, npix,
-                    (const float *)ctx->pool_weld_rgb.p, render_id(ctx), render_depth(ctx), render_bgr(ctx)));
+                    ctx->pool_weld_rgb.data(), render_id(ctx), render_depth(ctx), render_bgr(ctx)));
     ctx->render_ready = true;
     return ARVX_OK;
 }
@@ -4008,10 +3956,9 @@ int arvx_render_download(arvx_ctx *ctx, uint8_t *bgr, float *depth, int32_t *id)
     ARVX_CHECK_CTX(ctx);
     if (!ctx->render_ready) return fail(ARVX_ERR_STATE, "no render (call arvx_render)");
     const size_t npix = (size_t)ctx->render_W * ctx->render_H;
-    if (bgr) ARVX_HIP(hipMemcpyAsync(bgr, render_bgr(ctx), npix * 3, hipMemcpyDeviceToHost, ctx->stream));
-    if (depth)
-        ARVX_HIP(hipMemcpyAsync(depth, render_depth(ctx), npix * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (id) ARVX_HIP(hipMemcpyAsync(id, render_id(ctx), npix * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_TRY(download(ctx, bgr, render_bgr(ctx), npix, 3));
+    ARVX_TRY(download(ctx, depth, render_depth(ctx), npix, sizeof(float)));
+    ARVX_TRY(download(ctx, id, render_id(ctx), npix, sizeof(int32_t)));
     ARVX_SYNC(ctx);
     ctx->render_need = std::max(ctx->word(Ctx::kRenderNeed), 0ll);
     return ARVX_OK;

@@ -46,6 +46,12 @@ struct DevPool {
         cap = 0;
     }
 };
+// A pool that holds one array: of what is said here, once.
+template <class T>
+struct DevArray : DevPool {
+    T *data() const { return (T *)p; }
+};
+struct SparseWord;  // bitplane_kernels.h
 
 struct Ctx {
     int device = 0;
@@ -389,36 +395,75 @@ struct Ctx {
     bool mc_ready = false;
     // storage behind the d_surf_* / d_clo_* / d_mc_cells views
     DevPool pool_surf_index, pool_surf_rgb, pool_surf_depth, pool_surf_has, pool_clo_index,
-        pool_clo_rgba, pool_mc_cells, pool_raw_masks, pool_mesh_verts, pool_mesh_rgb, pool_mesh_off;
+        pool_clo_rgba, pool_mc_cells, pool_raw_masks;
+
+    // ---- the meshes: where an array lies in a pool is said once, by the pool's type where it holds one
+    // array and by the accessors under it where it holds several; the sizes such a layout depends on are
+    // kept from the call that built the mesh (V and T of the welded mesh: weld_verts, weld_tris) ----
+    using Plane = unsigned long long;  // a word of a bit plane (bitplane_kernels.h)
+    // a face record: three vertex indices, then r, g, b; a position or a vertex colour: three floats
+    static constexpr size_t kFaceBytes = 24, kFaceColour = 12, kVertexBytes = 12;
+    // arvx_mc_mesh: three positions and a face record per triangle; every mesh's triangle offsets per cell
+    DevArray<float> pool_mesh_verts;
+    DevArray<unsigned> pool_mesh_rgb;
+    DevArray<int> pool_mesh_off;
     int64_t mesh_tris = 0;  // triangles of the last arvx_mc_mesh
-    // arvx_mc_mesh_welded: the occupancy and vertex planes, the vertex plane's ranks and list, and
-    // the welded mesh (positions, vertex colours, face records)
-    DevPool pool_weld_planes, pool_weld_rank, pool_weld_index, pool_weld_verts, pool_weld_rgb,
-        pool_weld_faces;
+    // arvx_mc_mesh_welded: the occupancy plane and the vertex plane (weld_words words each), the vertex
+    // plane's ranks and list, and the welded mesh (positions, vertex colours, face records)
+    DevArray<Plane> pool_weld_planes;
+    DevArray<SparseWord> pool_weld_rank;
+    DevArray<int> pool_weld_index;
+    DevArray<float> pool_weld_verts, pool_weld_rgb;
+    DevArray<unsigned> pool_weld_faces;
+    size_t weld_words = 0;
     int64_t weld_verts = 0, weld_tris = 0;
     bool weld_ready = false;
-    // arvx_mc_mesh_smooth: the welded mesh's CSRs -- masks, counts and offsets; neighbour list;
-    // incidence list -- (built once per welded mesh), the two position buffers, the faces' cross
-    // products and the normals
-    DevPool pool_smooth_csr, pool_smooth_nbr, pool_smooth_inc, pool_smooth_verts, pool_smooth_cross,
-        pool_smooth_normals;
+    Plane *weld_occ() const { return pool_weld_planes.data(); }
+    Plane *weld_vtx() const { return weld_occ() + weld_words; }
+    // arvx_mc_mesh_smooth: the welded mesh's CSRs, built once per welded mesh -- V masks, then counts and
+    // offsets (V + 1 each); neighbour list; incidence list --, two position buffers, cross products, normals
+    DevArray<int> pool_smooth_csr;
+    DevArray<unsigned> pool_smooth_nbr, pool_smooth_inc;
+    DevArray<float> pool_smooth_verts, pool_smooth_cross, pool_smooth_normals;
     bool smooth_csr_ready = false, smooth_ready = false;
-    int smooth_q = 0;  // where the smoothed positions are: 0 the welded mesh's, 1 / 2 a buffer
-    // arvx_mc_mesh_decimate: the cluster plane and its ranks, the cluster list, the decimated mesh
-    // (positions, colours, member counts, face records), the welded vertices' map, the faces' flags
-    // and offsets, and the slot table (mc_decimate_kernels.h), sized at first use and kept
-    DevPool pool_dec_planes, pool_dec_index, pool_dec_verts, pool_dec_rgb, pool_dec_members, pool_dec_map,
-        pool_dec_faces, pool_dec_flags, pool_dec_slots;
+    int smooth_q = 0;  // the smoothed positions are smooth_xyz(smooth_q)
+    size_t smooth_csr_bytes() const { return (size_t)(5 * weld_verts + 4) * sizeof(int); }
+    unsigned *smooth_masks() const { return (unsigned *)pool_smooth_csr.data(); }
+    int *smooth_icount() const { return pool_smooth_csr.data() + weld_verts; }
+    int *smooth_ncount() const { return smooth_icount() + weld_verts + 1; }
+    int *smooth_noff() const { return smooth_ncount() + weld_verts + 1; }
+    int *smooth_ioff() const { return smooth_noff() + weld_verts + 1; }
+    float *smooth_xyz(int q) const {  // 0: the welded mesh's own positions, 1 / 2: a buffer
+        return q == 0 ? pool_weld_verts.data() : pool_smooth_verts.data() + (q - 1) * 3 * weld_verts;
+    }
+    // arvx_mc_mesh_decimate: the cluster plane behind its dec_words ranks, the cluster list, the decimated
+    // mesh, the welded vertices' map, the welded faces' flags and offsets (T each), the slot table
+    DevArray<SparseWord> pool_dec_planes;
+    DevArray<int> pool_dec_index, pool_dec_members, pool_dec_map, pool_dec_flags;
+    DevArray<float> pool_dec_verts, pool_dec_rgb;
+    DevArray<unsigned> pool_dec_faces, pool_dec_slots;
+    size_t dec_words = 0;
     int64_t dec_verts = 0, dec_tris = 0;
     bool dec_ready = false;
-    // arvx_mc_mesh_refined: the occupancy plane and the edge plane behind it, the edge plane's ranks
-    // and list (the keys), and the refined mesh (positions, vertex colours, face records; per vertex
-    // 4 ints of edge description, then -- ref_cap entries in -- the cut numerators), sized by the
-    // list protocol and kept
-    DevPool pool_ref_planes, pool_ref_rank, pool_ref_index, pool_ref_verts, pool_ref_rgb, pool_ref_faces,
-        pool_ref_edges;
+    SparseWord *dec_rank() const { return pool_dec_planes.data(); }
+    inline Plane *dec_bits() const;  // (arvx_capi.hip: it takes the size of a SparseWord)
+    int *dec_flags() const { return pool_dec_flags.data(); }
+    int *dec_off() const { return dec_flags() + weld_tris; }
+    // arvx_mc_mesh_refined: the occupancy plane (ref_words words) and the edge plane, its ranks and list (the
+    // keys), the refined mesh; per vertex kRefEdgeInts ints of edge, then -- ref_cap entries in -- the cuts
+    DevArray<Plane> pool_ref_planes;
+    DevArray<SparseWord> pool_ref_rank;
+    DevArray<int> pool_ref_index, pool_ref_edges;
+    DevArray<float> pool_ref_verts, pool_ref_rgb;
+    DevArray<unsigned> pool_ref_faces;
+    static constexpr int kRefEdgeInts = 4;
+    size_t ref_words = 0;
     int64_t ref_verts = 0, ref_tris = 0, ref_cap = 0;
     bool ref_ready = false;
+    Plane *ref_occ() const { return pool_ref_planes.data(); }
+    Plane *ref_edge_plane() const { return ref_occ() + ref_words; }
+    int *ref_edges() const { return pool_ref_edges.data(); }
+    int *ref_cut() const { return ref_edges() + kRefEdgeInts * ref_cap; }
 
     // arvx_render: the W x H keys, the images (id | depth | bgr), the large-footprint list behind
     // its header (render_kernels.h), all sized at first use and kept.  Count words: kRenderNeed, then
@@ -446,6 +491,11 @@ struct Ctx {
         d_mc_cells = nullptr;
         mc_count = 0;
         mc_ready = false;
+    }
+    void cells_built(long long n) {  // the cell list a call leaves (no buffer where it is empty)
+        if (n == 0) d_mc_cells = nullptr;
+        mc_count = n;
+        mc_ready = true;
     }
     void free_views() {
         pool_M.release();

@@ -1,12 +1,13 @@
 """Inputs of the list-retry tests (test_list_retry_cpu.py, test_list_retry_gpu.py): a grid of noise
-whose every list -- surface voxels, closure fills, marching-cubes cells, triangles, welded vertices --
-is longer than the room a fresh context gives it (first-capacity rule), so that the first
-call of each list stage on a fresh context has to run its second attempt."""
+whose every list -- surface voxels, closure fills, marching-cubes cells, triangles, welded vertices, the
+refined mesh's cut edges -- is longer than the room a fresh context gives it (first-capacity
+rule), so that the first call of each list stage on a fresh context has to run its second attempt."""
 from collections import namedtuple
 
 import numpy as np
 
 from ar_voxel_project_amd import synthetic as syn
+from tests import mesh_refine as mr
 from tests import mesh_weld as mw
 from tests import np_restate as npr
 from tests import photo_carve as pc
@@ -20,6 +21,7 @@ S = np.float32(EXTENT / X)
 MODE = 1                  # ARVX_COLOR_AVERAGE
 TOL = np.float32(3) * S   # visibility tolerance: 3 voxel edges
 PHOTO = dict(max_std=48.0, min_views=2, iterations=2)
+BISECTIONS = 2            # of the refined mesh
 
 Scene = namedtuple("Scene", "state occ M campos masks images")
 
@@ -30,11 +32,12 @@ def first_capacity(v, most=None):
 
 
 def first_capacities():
-    """Room on a fresh whole-grid context of this grid: surface, fills, cells, triangles, vertices."""
+    """Room on a fresh whole-grid context of this grid: surface, fills, cells, triangles, vertices,
+    and the refined mesh's vertices (its cut edges)."""
     v = X * Y * Z
     cells = first_capacity(v, v + 1e6)
     return dict(surface=first_capacity(v), fills=first_capacity(v), cells=cells, triangles=2 * cells,
-                vertices=cells)
+                vertices=cells, cut_edges=3 * cells)
 
 
 def scene():
@@ -46,14 +49,16 @@ def scene():
 
 
 Want = namedtuple("Want", "coloured closed cells mesh welded cells_closed mesh_closed welded_closed "
-                          "visible photo")
+                          "visible photo refined")
 
 
 def references(oracle, sc):
     """What the suite compares each stage with: the oracle's colour pass, closure, cell list and mesh
     (test_pipeline_gpu.py), the weld of the unwelded mesh (test_mc_weld_gpu.py), the numpy visible
     colour pass and photo carve (test_color_visible_gpu.py, test_photo_carve_gpu.py).  cells / mesh /
-    welded: of the coloured model; *_closed: of the model after closure(3, no unseen)."""
+    welded: of the coloured model; *_closed: of the model after closure(3, no unseen).  refined: the
+    numpy restatement (test_mc_refine_gpu.py, check_refined) on the scene's occupancy and the coloured
+    model's colours, left grouping."""
     fresh = oracle.model_from_state(sc.state)
     coloured = oracle.color(X, Y, Z, S, sc.M, sc.campos, sc.images, MODE, fresh)
     closed = oracle.closure(X, Y, Z, coloured)
@@ -62,11 +67,13 @@ def references(oracle, sc):
                 oracle.mc_cells(X, Y, Z, closed), mesh_closed, mw.weld(*mesh_closed),
                 vis.color_visible(X, Y, Z, S, sc.M, sc.campos, sc.images, MODE, fresh, TOL),
                 pc.photo_carve(X, Y, Z, S, sc.M, sc.images, sc.state, PHOTO["max_std"], PHOTO["min_views"],
-                               TOL, PHOTO["iterations"]))
+                               TOL, PHOTO["iterations"]),
+                mr.refine(sc.occ, S, sc.M, sc.masks, BISECTIONS, True, coloured[:, :3].reshape(Z, Y, X, 3)))
 
 
 def lengths(sc, want):
     """The scene's list lengths, counted on the CPU."""
     return dict(surface=int(npr.surface_mask(sc.occ).sum()),
                 fills=int(((want.closed[:, 3] != 0) & (want.coloured[:, 3] == 0)).sum()),
-                cells=len(want.cells), triangles=len(want.mesh[1]), vertices=len(want.welded[0]))
+                cells=len(want.cells), triangles=len(want.mesh[1]), vertices=len(want.welded[0]),
+                cut_edges=len(mr.cut_edges(sc.occ)[0]))

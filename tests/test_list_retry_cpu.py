@@ -19,12 +19,13 @@ def counted(want):
 
 def test_first_capacity_rule():
     caps = lr.first_capacities()
-    assert caps == dict(surface=17099, fills=17099, cells=17099, triangles=34198, vertices=17099)
+    assert caps == dict(surface=17099, fills=17099, cells=17099, triangles=34198, vertices=17099,
+                        cut_edges=51297)
     # the bound on the minimum only matters for tiny grids: 8 voxels have room for 8, cells for more
     assert lr.first_capacity(8) == 8 and lr.first_capacity(8, 8 + 1e6) == 4128
 
 
-@pytest.mark.parametrize("name", ["surface", "fills", "cells", "triangles", "vertices"])
+@pytest.mark.parametrize("name", ["surface", "fills", "cells", "triangles", "vertices", "cut_edges"])
 def test_every_list_outgrows_a_fresh_context(counted, name):
     cap = lr.first_capacities()[name]
     print(f"{name}: {counted[name]} entries, room for {cap}")

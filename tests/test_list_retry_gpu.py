@@ -6,9 +6,10 @@ suite compares that stage with everywhere else.  The second run on the same cont
 room for all -- the single-attempt path -- and must give the same arrays.
 
 A list stage runs its second attempt only where its own pools are fresh: the cell list's pool is
-shared by arvx_mc_cells, arvx_mc_mesh and arvx_mc_mesh_welded, the surface list's by arvx_color,
-arvx_color_visible and arvx_photo_carve, and the closure fills the noise almost solid (few cells).  So
-each of those entry points also gets a context of its own, next to the sequence on one context."""
+shared by arvx_mc_cells, arvx_mc_mesh, arvx_mc_mesh_welded and arvx_mc_mesh_refined, the surface list's
+by arvx_color, arvx_color_visible and arvx_photo_carve, and the closure fills the noise almost solid
+(few cells).  So each of those entry points also gets a context of its own, next to the sequence on one
+context."""
 import numpy as np
 import pytest
 
@@ -28,6 +29,10 @@ def sc():
 @pytest.fixture(scope="module")
 def want(oracle, sc):
     return lr.references(oracle, sc)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def check_mesh(got, mesh):
@@ -90,6 +95,22 @@ def stage_welded(ctx, arvx, want):
     return out + [*welded]
 
 
+def stage_refined(ctx, arvx, want):
+    """As check_refined of tests/test_mc_refine_gpu.py, against the restatement of the state and the
+    colours the context holds: positions and colours bit for bit, edges, cuts and faces equal."""
+    out = coloured(ctx, arvx, want)
+    assert ctx.assoc == arvx.ASSOC_LEFT
+    assert np.array_equal(ctx.download_state().reshape(-1) & 1, want.coloured[:, 3] != 0)
+    verts, faces, frgb, vrgb, edges, cut = ctx.mc_mesh_refined(lr.BISECTIONS, False, vertex_colors=True,
+                                                               details=True)
+    w = want.refined
+    assert verts.shape == w["verts"].shape and faces.shape == w["faces"].shape
+    assert np.array_equal(edges, w["edges"]) and np.array_equal(cut, w["cut"])
+    assert np.array_equal(bits(verts), bits(w["verts"])) and np.array_equal(bits(vrgb), bits(w["vertex_rgb"]))
+    assert np.array_equal(faces, w["faces"]) and np.array_equal(frgb, w["face_rgb"])
+    return out + [verts, faces, frgb, vrgb, edges, cut]
+
+
 def stage_visible(ctx, arvx, want):
     """As tests/test_color_visible_gpu.py: coloured voxels, colours, visible-view counts, depth buffers."""
     ctx.color_visible(lr.MODE, lr.TOL)
@@ -112,8 +133,8 @@ def stage_photo(ctx, arvx, want):
     return [np.array([it, removed]), state]
 
 
-@pytest.mark.parametrize("stage", [stage_sequence, stage_cells, stage_mesh, stage_welded, stage_visible,
-                                   stage_photo], ids=lambda f: f.__name__[6:])
+@pytest.mark.parametrize("stage", [stage_sequence, stage_cells, stage_mesh, stage_welded, stage_refined,
+                                   stage_visible, stage_photo], ids=lambda f: f.__name__[6:])
 def test_second_attempt_then_single_attempt(arvx, sc, want, stage):
     with arvx.Context(X, Y, Z, lr.S) as ctx:  # fresh: no pool has a size
         ctx.set_views(sc.M, sc.masks, campos=sc.campos)
