@@ -50,6 +50,10 @@ MORPH_OPEN = 2
 MORPH_CLOSE = 3
 DECIMATE_LATTICE = 0
 DECIMATE_SMOOTHED = 1
+MESH_WELDED = 0
+MESH_SMOOTHED = 1
+MESH_DECIMATED = 2
+MESH_REFINED = 3
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
 # whole test module with the streaming carve forced on every fresh model (the library itself reads
 # no environment variable)
@@ -87,6 +91,8 @@ SYMBOLS = [
     "arvx_mc_mesh_decimate", "arvx_mc_mesh_decimate_download",
     "arvx_mc_mesh_refined", "arvx_mc_mesh_refined_download",
     "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
+    "arvx_render_mesh", "arvx_render_mesh_view", "arvx_render_mesh_agreement", "arvx_render_triangles",
+    "arvx_render_mesh_stats", "arvx_selftest_render_mesh_list",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
     "arvx_export_model", "arvx_get_stats", "arvx_last_carve_path", "arvx_last_fast_carve_path",
@@ -263,6 +269,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.arvx_render_view.argtypes = [p, C.c_int]
         lib.arvx_render_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.arvx_render_agreement.argtypes = [p, C.c_int, C.POINTER(C.c_int64)]
+    if hasattr(lib, "arvx_render_mesh") or not ab_build:
+        lib.arvx_render_mesh.argtypes = [p, C.c_int, f32p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.arvx_render_mesh_view.argtypes = [p, C.c_int, C.c_int, C.c_void_p]
+        lib.arvx_render_mesh_agreement.argtypes = [p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        lib.arvx_render_triangles.argtypes = [p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, f32p,
+                                              C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.arvx_render_mesh_stats.argtypes = [p, C.POINTER(C.c_int64)]
+        lib.arvx_selftest_render_mesh_list.argtypes = [p, C.c_int64]
     for name in SYMBOLS:
         if ab_build and not hasattr(lib, name):
             continue
@@ -301,6 +315,14 @@ def compose_projection(K, Rt) -> np.ndarray:
     M = np.empty(12, np.float32)
     _check(load_library().arvx_compose_projection(_fp(K), _fp(Rt), _fp(M)))
     return M.reshape(3, 4)
+
+
+def headlight(M) -> np.ndarray:
+    """The viewing direction of the camera M (3 x 4, world -> pixel) along the voxel axes x, y, z, for the
+    `light` of render_mesh: (m21, m20, -m22), the third row of M reordered, because world = (y * s, x * s,
+    -z * s)."""
+    M = _f32(M).reshape(3, 4)
+    return np.array([M[2, 1], M[2, 0], -M[2, 2]], np.float32)
 
 
 def view_window_host(X: int, Y: int, Z: int, voxel_size: float, M, W: int, H: int) -> Tuple[int, int, int, int]:
@@ -995,6 +1017,75 @@ class Context:
         self._ck(self._lib.arvx_render_agreement(self._h, int(view), counts))
         self._render_wh = (self.W, self.H)
         return int(counts[0]), int(counts[1]), int(counts[2])
+
+    @staticmethod
+    def _background(background, W: int, H: int):
+        if background is None:
+            return None, 0
+        bg = np.asarray(background)
+        assert bg.dtype == np.uint8 and bg.shape == (H, W, 3) and bg.strides[1:] == (3, 1)
+        return bg, bg.strides[0]
+
+    def render_mesh(self, source: int, M, W: int, H: int, background=None, light=None, download: bool = True):
+        """arvx_render_mesh: the triangles of the context's mesh `source` (MESH_WELDED, MESH_SMOOTHED,
+        MESH_DECIMATED, MESH_REFINED) drawn with a depth buffer into the camera M (3 x 4, world -> pixel)
+        on a W x H image, over `background` or black, flat-shaded by `light` (3 floats along the voxel
+        axes, e.g. headlight(M); None: unshaded): (bgr, depth, id) as render() returns them, id the
+        index into the source's face list.  download=False: the call only."""
+        M = _f32(M).reshape(12)
+        bg, stride = self._background(background, W, H)
+        lt = None if light is None else _f32(light).reshape(3)
+        self._ck(self._lib.arvx_render_mesh(self._h, int(source), _fp(M), int(W), int(H),
+                                            bg.ctypes.data if bg is not None else None, stride,
+                                            lt.ctypes.data if lt is not None else None))
+        self._render_wh = (int(W), int(H))
+        return self.render_download() if download else None
+
+    def render_mesh_view(self, source: int, view: int, light=None, download: bool = True):
+        """arvx_render_mesh_view: render_mesh() with the camera and image size of the context's view
+        `view` and no background."""
+        lt = None if light is None else _f32(light).reshape(3)
+        self._ck(self._lib.arvx_render_mesh_view(self._h, int(source), int(view),
+                                                 lt.ctypes.data if lt is not None else None))
+        self._render_wh = (self.W, self.H)
+        return self.render_download() if download else None
+
+    def render_mesh_agreement(self, source: int, view: int) -> Tuple[int, int, int]:
+        """arvx_render_mesh_agreement: render_agreement() of the mesh's triangles."""
+        counts = (C.c_int64 * 3)()
+        self._ck(self._lib.arvx_render_mesh_agreement(self._h, int(source), int(view), counts))
+        self._render_wh = (self.W, self.H)
+        return int(counts[0]), int(counts[1]), int(counts[2])
+
+    def render_triangles(self, verts, vertex_rgb, faces, M, W: int, H: int, background=None, light=None,
+                         download: bool = True):
+        """arvx_render_triangles: render_mesh() of a caller's mesh -- verts (V, 3) float32 in voxel units,
+        vertex_rgb (V, 3) float32, faces (T, 3) vertex indices or (T, 6) face records."""
+        v, c = _f32(verts).reshape(-1, 3), _f32(vertex_rgb).reshape(-1, 3)
+        assert len(v) == len(c)
+        f = np.asarray(faces)
+        rec = np.zeros((len(f), 6), np.uint32)
+        if len(f):
+            rec[:, :f.shape[1]] = f
+        M = _f32(M).reshape(12)
+        bg, stride = self._background(background, W, H)
+        lt = None if light is None else _f32(light).reshape(3)
+        self._ck(self._lib.arvx_render_triangles(self._h, len(v), v.ctypes.data, c.ctypes.data, len(rec),
+                                                 rec.ctypes.data, _fp(M), int(W), int(H),
+                                                 bg.ctypes.data if bg is not None else None, stride,
+                                                 lt.ctypes.data if lt is not None else None))
+        self._render_wh = (int(W), int(H))
+        return self.render_download() if download else None
+
+    def render_mesh_stats(self) -> Tuple[int, int, int, int]:
+        """arvx_render_mesh_stats: (drawn, empty, flat, refused) triangles of the current triangle render."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.arvx_render_mesh_stats(self._h, out))
+        return tuple(int(n) for n in out)
+
+    def selftest_render_mesh_list(self, cap: int) -> None:
+        """Room of the triangle render's list of large pixel boxes from the next render on (-1: default)."""
+        self._ck(self._lib.arvx_selftest_render_mesh_list(self._h, int(cap)))
 
     def mc_mesh_count(self, apply_unseen: bool = False) -> int:
         """arvx_mc_mesh without the download: the triangles stay on the device."""

@@ -44,6 +44,7 @@
 #include "distance_kernels.h"
 #include "vote_kernels.h"
 #include "render_kernels.h"
+#include "render_mesh_kernels.h"
 #include "exchange_kernels.h"
 #include <algorithm>
 
@@ -3863,25 +3864,20 @@ static int render_refusals(const Ctx *ctx, const float *M, int W, int H) {
     return ARVX_OK;
 }
 
-// Clear, background, splat, large footprints, resolve: launches only.  The caller has refused what
-// is to be refused; a failure in here leaves no render.
-static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *background, size_t bg_stride) {
+// What every render starts with: the pools, the keys cleared (with the list's header and the agreement
+// counters: large_bytes of pool_render_large, 64 at least), the background in place.  A failure in
+// here leaves no render.
+static int render_begin(Ctx *ctx, int W, int H, const uint8_t *background, size_t bg_stride, size_t large_bytes) {
     ctx->render_ready = false;
+    ctx->render_tris = false;
     const size_t npix = (size_t)W * H;
-    const long long n = ctx->weld_verts;
     ARVX_HIP(ctx->pool_render_keys.reserve(npix * sizeof(unsigned long long)));
     ARVX_HIP(ctx->pool_render_img.reserve(npix * 11));
-    // large footprints (large_list_cap): never more than there are vertices.
-    // render_need is the count word as it stood at the last synchronisation of a render call
-    // (arvx_render_download, arvx_render_agreement): renders launched back to back without one all
-    // use the same capacity, whatever the device has finished by then.
-    const unsigned large_cap = large_list_cap(n, ctx->render_need, n);
-    ARVX_HIP(ctx->pool_render_large.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
+    ARVX_HIP(ctx->pool_render_large.reserve(large_bytes));
     ctx->render_W = W;
     ctx->render_H = H;
     unsigned long long *keys = (unsigned long long *)ctx->pool_render_keys.p;
     arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
-    arvx::SplatRect *large = (arvx::SplatRect *)((uint8_t *)ctx->pool_render_large.p + 64);
     const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
     ARVX_TRY(launch(ctx, arvx::render_clear_kernel, (unsigned)std::min<size_t>((npix + 255) / 256, 8 * ncu),
                     256, keys, npix, head));
@@ -3903,6 +3899,24 @@ static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *
     } else {
         ARVX_HIP(hipMemsetAsync(render_bgr(ctx), 0, npix * 3, ctx->stream));
     }
+    return ARVX_OK;
+}
+
+// Clear, background, splat, large footprints, resolve: launches only.  The caller has refused what
+// is to be refused; a failure in here leaves no render.
+static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *background, size_t bg_stride) {
+    const size_t npix = (size_t)W * H;
+    const long long n = ctx->weld_verts;
+    // large footprints (large_list_cap): never more than there are vertices.
+    // render_need is the count word as it stood at the last synchronisation of a render call
+    // (arvx_render_download, arvx_render_agreement): renders launched back to back without one all
+    // use the same capacity, whatever the device has finished by then.
+    const unsigned large_cap = large_list_cap(n, ctx->render_need, n);
+    ARVX_TRY(render_begin(ctx, W, H, background, bg_stride, 64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
+    unsigned long long *keys = (unsigned long long *)ctx->pool_render_keys.p;
+    arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
+    arvx::SplatRect *large = (arvx::SplatRect *)((uint8_t *)ctx->pool_render_large.p + 64);
+    const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
     if (n > 0) {
         arvx::RenderSplatParams sp;
         sp.index = ctx->pool_weld_index.data();
@@ -3961,6 +3975,7 @@ int arvx_render_download(arvx_ctx *ctx, uint8_t *bgr, float *depth, int32_t *id)
     ARVX_TRY(download(ctx, id, render_id(ctx), npix, sizeof(int32_t)));
     ARVX_SYNC(ctx);
     ctx->render_need = std::max(ctx->word(Ctx::kRenderNeed), 0ll);
+    ctx->render_mesh_need = std::max(ctx->word(Ctx::kRenderMeshNeed), 0ll);
     return ARVX_OK;
 }
 
@@ -3982,6 +3997,204 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]) {
         if (ctx->word(Ctx::kRenderAgree + k) < 0) return fail(ARVX_ERR_HIP, "the agreement left no count");
         counts[k] = ctx->word(Ctx::kRenderAgree + k);
     }
+    return ARVX_OK;
+}
+
+// ---- triangle render (render_mesh_kernels.h) ------------------------------------------------
+
+// A mesh as the rasteriser reads it: where its arrays lie and how long they are.
+struct MeshSource {
+    const float *verts, *rgb;
+    const unsigned *faces;
+    long long V, T;
+};
+
+// The context's mesh `source`, or the refusal: an unknown source, or a mesh that does not exist
+// (slab and striped contexts never build one).
+static int mesh_source(const Ctx *ctx, int source, MeshSource &m) {
+    switch (source) {
+    case ARVX_MESH_WELDED:
+    case ARVX_MESH_SMOOTHED:
+        if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
+        if (source == ARVX_MESH_SMOOTHED && !ctx->smooth_ready)
+            return fail(ARVX_ERR_STATE, "no smoothed mesh (call arvx_mc_mesh_smooth)");
+        m = MeshSource{ctx->smooth_xyz(source == ARVX_MESH_WELDED ? 0 : ctx->smooth_q), ctx->pool_weld_rgb.data(),
+                       ctx->pool_weld_faces.data(), ctx->weld_verts, ctx->weld_tris};
+        return ARVX_OK;
+    case ARVX_MESH_DECIMATED:
+        if (!ctx->dec_ready) return fail(ARVX_ERR_STATE, "no decimated mesh (call arvx_mc_mesh_decimate)");
+        m = MeshSource{ctx->pool_dec_verts.data(), ctx->pool_dec_rgb.data(), ctx->pool_dec_faces.data(),
+                       ctx->dec_verts, ctx->dec_tris};
+        return ARVX_OK;
+    case ARVX_MESH_REFINED:
+        if (!ctx->ref_ready) return fail(ARVX_ERR_STATE, "no refined mesh (call arvx_mc_mesh_refined)");
+        m = MeshSource{ctx->pool_ref_verts.data(), ctx->pool_ref_rgb.data(), ctx->pool_ref_faces.data(),
+                       ctx->ref_verts, ctx->ref_tris};
+        return ARVX_OK;
+    }
+    return fail(ARVX_ERR_INVALID, "unknown mesh source %d", source);
+}
+
+// the refusals of a camera, an image size, a background and a light
+static int render_mesh_refusals(const float *M, int W, int H, const uint8_t *background, size_t bg_stride,
+                                const float *light) {
+    if (!M) return fail(ARVX_ERR_INVALID, "null M");
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(M[k])) return fail(ARVX_ERR_INVALID, "M[%d] is not finite", k);
+    if (W < 1 || H < 1 || W > arvx::kMaxImageDim || H > arvx::kMaxImageDim)
+        return fail(ARVX_ERR_INVALID, "image size %dx%d out of range", W, H);
+    if (background && bg_stride < (size_t)W * 3) return fail(ARVX_ERR_INVALID, "bg_stride %zu < 3 * W", bg_stride);
+    for (int k = 0; light && k < 3; ++k)
+        if (!std::isfinite(light[k])) return fail(ARVX_ERR_INVALID, "light[%d] is not finite", k);
+    return ARVX_OK;
+}
+
+// Clear, background, projection, raster, large boxes, resolve: launches only.  The caller has refused
+// what is to be refused; a failure in here leaves no render.
+static int render_mesh_launch(Ctx *ctx, const MeshSource &m, const float *M, int W, int H,
+                              const uint8_t *background, size_t bg_stride, const float *light) {
+    ARVX_TRY(render_begin(ctx, W, H, background, bg_stride, 64));
+    const size_t npix = (size_t)W * H;
+    // large pixel boxes (large_list_cap): never more than there are triangles.  render_mesh_need is
+    // the count word as it stood at the last synchronisation of a render call.
+    const unsigned large_cap =
+        ctx->render_mesh_list_cap >= 0
+            ? (unsigned)std::min<long long>({ctx->render_mesh_list_cap, m.T, (long long)UINT32_MAX})
+            : large_list_cap(m.T, ctx->render_mesh_need, m.T);
+    ARVX_HIP(ctx->pool_render_tris.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
+    arvx::RenderMeshParams p{};
+    p.verts = m.verts, p.rgb = m.rgb, p.faces = m.faces;
+    p.V = m.V, p.T = m.T;
+    p.s = ctx->s;
+    p.W = W, p.H = H;
+    memcpy(p.M.m, M, 12 * sizeof(float));
+    p.keys = (unsigned long long *)ctx->pool_render_keys.p;
+    p.head = (arvx::RenderMeshHeader *)ctx->pool_render_tris.p;
+    p.large = (arvx::SplatRect *)((uint8_t *)ctx->pool_render_tris.p + 64);
+    p.large_cap = large_cap;
+    p.lit = light ? 1 : 0;
+    for (int k = 0; k < 3; ++k) p.light[k] = light ? light[k] : 0.f;
+    static_assert(sizeof(arvx::RenderMeshHeader) <= 64, "the header ends before the list");
+    ARVX_HIP(hipMemsetAsync(p.head, 0, 64, ctx->stream));
+    if (m.T > 0 && m.V > 0) {
+        ARVX_HIP(ctx->pool_render_proj.reserve((size_t)m.V * sizeof(arvx::MeshVertex)));
+        p.proj = (arvx::MeshVertex *)ctx->pool_render_proj.p;
+        const int ncu = ctx->ncu > 0 ? ctx->ncu : 256;
+        ARVX_TRY(by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::render_mesh_project_kernel<decltype(left)::value>, blocks_for(m.V), 256, p);
+        }));
+        // (the grid strides over the faces)
+        ARVX_TRY(launch(ctx, arvx::render_mesh_raster_kernel,
+                        (unsigned)std::min<long long>((m.T + 255) / 256, 8 * ncu), 256, p));
+        ARVX_TRY(launch(ctx, arvx::render_mesh_large_kernel, (unsigned)(4 * ncu), 256, p,
+                        ctx->word_dev(Ctx::kRenderMeshNeed)));
+    } else {
+        p.T = 0;  // (faces without vertices cannot be: every index is below V)
+    }
+    ARVX_TRY(launch(ctx, arvx::render_mesh_resolve_kernel, blocks_for(npix), 256, p, npix, render_id(ctx),
+                    render_depth(ctx), render_bgr(ctx)));
+    ctx->render_ready = true;
+    ctx->render_tris = true;
+    return ARVX_OK;
+}
+
+int arvx_render_mesh(arvx_ctx *ctx, int source, const float M[12], int W, int H, const uint8_t *background,
+                     size_t bg_stride, const float *light) {
+    ARVX_CHECK_CTX(ctx);
+    MeshSource m;
+    if (int rc = mesh_source(ctx, source, m)) return rc;
+    if (int rc = render_mesh_refusals(M, W, H, background, bg_stride, light)) return rc;
+    return render_mesh_launch(ctx, m, M, W, H, background, bg_stride, light);
+}
+
+// arvx_render_mesh_view's refusals (arvx_render_mesh_agreement adds its own after them)
+static int render_mesh_view_refusals(const Ctx *ctx, int source, int view, const float *light, MeshSource &m) {
+    if (int rc = mesh_source(ctx, source, m)) return rc;
+    if (!ctx->cameras_ready) return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
+    if (view < 0 || view >= ctx->V) return fail(ARVX_ERR_INVALID, "view %d outside [0,%d)", view, ctx->V);
+    return render_mesh_refusals(ctx->h_M.data() + 12 * (size_t)view, ctx->W, ctx->H, nullptr, 0, light);
+}
+
+int arvx_render_mesh_view(arvx_ctx *ctx, int source, int view, const float *light) {
+    ARVX_CHECK_CTX(ctx);
+    MeshSource m;
+    if (int rc = render_mesh_view_refusals(ctx, source, view, light, m)) return rc;
+    return render_mesh_launch(ctx, m, ctx->h_M.data() + 12 * (size_t)view, ctx->W, ctx->H, nullptr, 0, light);
+}
+
+int arvx_render_mesh_agreement(arvx_ctx *ctx, int source, int view, int64_t counts[3]) {
+    ARVX_CHECK_CTX(ctx);
+    MeshSource m;
+    if (int rc = render_mesh_view_refusals(ctx, source, view, nullptr, m)) return rc;
+    if (!ctx->views_ready) return fail(ARVX_ERR_STATE, "arvx_set_views was given no masks");
+    if (!counts) return fail(ARVX_ERR_INVALID, "null counts");
+    ARVX_TRY(render_mesh_launch(ctx, m, ctx->h_M.data() + 12 * (size_t)view, ctx->W, ctx->H, nullptr, 0, nullptr));
+    const size_t npix = (size_t)ctx->W * ctx->H;
+    arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
+    for (int k = 0; k < 3; ++k) ctx->word(Ctx::kRenderAgree + k) = -1;
+    ARVX_TRY(launch(ctx, arvx::render_agreement_kernel, blocks_for(npix), 256, render_id(ctx), npix,
+                    ctx->bg() + (size_t)view * ctx->bgWords, head->counts));
+    ARVX_TRY(launch(ctx, arvx::render_counts_out_kernel, 1, 64, head->counts, ctx->word_dev(Ctx::kRenderAgree)));
+    ARVX_SYNC(ctx);
+    ctx->render_mesh_need = std::max(ctx->word(Ctx::kRenderMeshNeed), 0ll);
+    for (int k = 0; k < 3; ++k) {
+        if (ctx->word(Ctx::kRenderAgree + k) < 0) return fail(ARVX_ERR_HIP, "the agreement left no count");
+        counts[k] = ctx->word(Ctx::kRenderAgree + k);
+    }
+    return ARVX_OK;
+}
+
+int arvx_render_triangles(arvx_ctx *ctx, int64_t nv, const float *verts, const float *vertex_rgb, int64_t nt,
+                          const uint32_t *faces, const float M[12], int W, int H, const uint8_t *background,
+                          size_t bg_stride, const float *light) {
+    ARVX_CHECK_CTX(ctx);
+    if (!whole_grid(ctx)) return fail(ARVX_ERR_STATE, "the render needs a whole-grid context");
+    if (nv < 0 || nt < 0) return fail(ARVX_ERR_INVALID, "a negative count");
+    if ((nv > 0 && (!verts || !vertex_rgb)) || (nt > 0 && !faces)) return fail(ARVX_ERR_INVALID, "null mesh array");
+    if (nv > (int64_t)UINT32_MAX || nt > (int64_t)UINT32_MAX) return fail(ARVX_ERR_INVALID, "the mesh is too long");
+    if (int rc = render_mesh_refusals(M, W, H, background, bg_stride, light)) return rc;
+    for (int64_t t = 0; t < nt; ++t)
+        for (int k = 0; k < 3; ++k)
+            if ((int64_t)faces[6 * t + k] >= nv)
+                return fail(ARVX_ERR_INVALID, "face %lld: index %u >= nv", (long long)t, faces[6 * t + k]);
+    // (the pools may hold the mesh of a triangle render still in flight: the stream orders the copies
+    // after it.  The caller's arrays are free when the call returns.)
+    if (nv > 0) {
+        ARVX_HIP(ctx->pool_tri_verts.reserve((size_t)nv * Ctx::kVertexBytes));
+        ARVX_HIP(ctx->pool_tri_rgb.reserve((size_t)nv * Ctx::kVertexBytes));
+        ARVX_HIP(hipMemcpyAsync(ctx->pool_tri_verts.p, verts, (size_t)nv * Ctx::kVertexBytes, hipMemcpyHostToDevice,
+                                ctx->stream));
+        ARVX_HIP(hipMemcpyAsync(ctx->pool_tri_rgb.p, vertex_rgb, (size_t)nv * Ctx::kVertexBytes,
+                                hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (nt > 0) {
+        ARVX_HIP(ctx->pool_tri_faces.reserve((size_t)nt * Ctx::kFaceBytes));
+        ARVX_HIP(hipMemcpyAsync(ctx->pool_tri_faces.p, faces, (size_t)nt * Ctx::kFaceBytes, hipMemcpyHostToDevice,
+                                ctx->stream));
+    }
+    if (nv > 0 || nt > 0) ARVX_SYNC(ctx);
+    const MeshSource m{ctx->pool_tri_verts.data(), ctx->pool_tri_rgb.data(), ctx->pool_tri_faces.data(), nv, nt};
+    return render_mesh_launch(ctx, m, M, W, H, background, bg_stride, light);
+}
+
+int arvx_render_mesh_stats(arvx_ctx *ctx, int64_t out[4]) {
+    ARVX_CHECK_CTX(ctx);
+    if (!out) return fail(ARVX_ERR_INVALID, "null out");
+    if (!ctx->render_ready || !ctx->render_tris)
+        return fail(ARVX_ERR_STATE, "the current render is no triangle render (call arvx_render_mesh)");
+    unsigned long long classes[arvx::kMeshClasses];
+    const arvx::RenderMeshHeader *head = (const arvx::RenderMeshHeader *)ctx->pool_render_tris.p;
+    ARVX_HIP(hipMemcpyAsync(classes, head->classes, sizeof classes, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    ctx->render_mesh_need = std::max(ctx->word(Ctx::kRenderMeshNeed), 0ll);
+    for (int k = 0; k < arvx::kMeshClasses; ++k) out[k] = (int64_t)classes[k];
+    return ARVX_OK;
+}
+
+int arvx_selftest_render_mesh_list(arvx_ctx *ctx, int64_t cap) {
+    ARVX_CHECK_CTX(ctx);
+    if (cap < -1) return fail(ARVX_ERR_INVALID, "cap %lld (-1: the default room)", (long long)cap);
+    ctx->render_mesh_list_cap = cap;
     return ARVX_OK;
 }
 

@@ -91,6 +91,7 @@ struct Ctx {
         kRenderNeed, kRenderAgree,      // the render's large footprints; three agreement counts in a row
         kRectMiss = kRenderAgree + 3,   // a block's rectangle did not fit its table entry (rect_cache_kernels.h)
         kMorphChanged,                  // arvx_morph: voxels that left or joined the model
+        kRenderMeshNeed,                // the triangle render's large pixel boxes
         kWords
     };
     static constexpr size_t kHostBlockBytes = 192;
@@ -480,6 +481,17 @@ struct Ctx {
     uint8_t *h_render_bg = nullptr;
     size_t render_bg_cap = 0;
     hipEvent_t render_bg_done = nullptr;
+    // arvx_render_mesh / arvx_render_triangles (render_mesh_kernels.h): a triangle render is the current
+    // render -- the keys, the images and render_ready above -- with render_tris set.  Its own: the
+    // projected vertices (16 bytes each), the list of large pixel boxes behind its header with the class
+    // counts, sized from kRenderMeshNeed as the voxel render's list is from kRenderNeed (or by
+    // arvx_selftest_render_mesh_list: render_mesh_list_cap >= 0), and a caller's mesh (positions, colours,
+    // face records).
+    DevPool pool_render_proj, pool_render_tris{DevPool::Exact};
+    DevArray<float> pool_tri_verts, pool_tri_rgb;
+    DevArray<unsigned> pool_tri_faces;
+    bool render_tris = false;
+    long long render_mesh_need = 0, render_mesh_list_cap = -1;
 
     // (the device buffers are freed by their DevPool members, after this)
     ~Ctx() {

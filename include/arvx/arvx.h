@@ -828,8 +828,8 @@ int arvx_mc_mesh_decimate_download(arvx_ctx *ctx, float *verts, uint32_t *faces,
  * The refined mesh lives until the next arvx_mc_mesh_refined.  It is a snapshot of the state and the
  * views at the call and touches no other product -- the unwelded, welded, smoothed and decimated
  * meshes and a render stay as they were; like arvx_mc_mesh_welded it runs arvx_mc_cells itself.
- * Out of scope: smoothing, decimating or rendering this mesh; normals; slabs and multi-GPU; colour
- * interpolation along the edge. */
+ * Out of scope: smoothing or decimating this mesh (arvx_render_mesh draws it); normals; slabs and
+ * multi-GPU; colour interpolation along the edge. */
 int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_t *vertices,
                          int64_t *triangles);
 int arvx_mc_mesh_refined_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb,
@@ -889,6 +889,89 @@ int arvx_render(arvx_ctx *ctx, const float M[12], int W, int H, const uint8_t *b
 int arvx_render_view(arvx_ctx *ctx, int view);
 int arvx_render_download(arvx_ctx *ctx, uint8_t *bgr, float *depth, int32_t *id);
 int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]);
+
+/* ---- triangle render (extension beyond the reference) -----------------------------------------
+ * Draws a mesh's triangles into a camera view with a depth buffer: any mesh the context holds, or a
+ * caller's.  Definition, bit for bit and without a thread order in it; the library is built with
+ * -ffp-contract=off, so every operation below is rounded on its own, and '/' is IEEE.  Inputs: V
+ * positions p (fp32 voxel coordinates x, y, z), V vertex colours col (fp32 r, g, b), T faces (i0, i1,
+ * i2), the camera M with W x H as for arvx_render, the context's voxel size s and row-sum grouping.
+ *  1. Vertex.  (a0, a1, a2) is the refined mesh's projection of a point: world = (py * s, px * s,
+ *     (-pz) * s, 1) in fp32, the rows' fp64 products summed in the context's grouping and rounded to
+ *     fp32.  qu = a0 / a2, qv = a1 / a2.  The vertex is VALID iff a2 >= FLT_MIN (normal, positive), qu
+ *     and qv are finite, |qu| <= 32768 and |qv| <= 32768.  Its fixed-point position is
+ *     fx = (int)std::round(qu * 16.0f), fy = (int)std::round(qv * 16.0f): the products are exact and
+ *     |fx|, |fy| <= 2^19.  Pixel (c, r) is the point (16 c, 16 r): pixel centres are the integers, as
+ *     everywhere in this library.
+ *  2. Triangle.  REFUSED if a corner is not VALID (no near-plane clipping).  With corners (x0, y0),
+ *     (x1, y1), (x2, y2): A = (x1 - x0)(y2 - y0) - (x2 - x0)(y1 - y0) in int64; FLAT if A == 0.  Both
+ *     windings are drawn.
+ *  3. Coverage.  For P = (px, py) = (16 c, 16 r): E0 = (x1 - px)(y2 - py) - (x2 - px)(y1 - py),
+ *     E1 = (x2 - px)(y0 - py) - (x0 - px)(y2 - py), E2 = (x0 - px)(y1 - py) - (x1 - px)(y0 - py), int64
+ *     and exact (|E| < 2^42; E0 + E1 + E2 = A).  If A < 0, all four are negated.  The pixel is COVERED
+ *     iff E0, E1, E2 >= 0: edges are inclusive on every side, so two faces that share an edge both
+ *     cover its pixels and step 4 decides.  Only pixels with 0 <= c < W, 0 <= r < H,
+ *     ceil(min fx / 16) <= c <= floor(max fx / 16) and the same in r can be covered (floor and ceil
+ *     towards -inf and +inf).  A valid triangle with an area that covers no pixel is EMPTY, every
+ *     other one DRAWN: each triangle is in exactly one of the four classes.
+ *  4. Depth and winner.  iz_i = 1.0 / (double)a2_i of corner i; t_i = (double)E_i * iz_i;
+ *     S = (t0 + t1) + t2; depth = (float)((double)A / S): perspective-correct, positive.  The winner of
+ *     a pixel is the minimum of bits(depth) << 32 | t over the triangles t that cover it: the nearest,
+ *     among equally near ones the least t, whatever the order in which triangles arrive.
+ *  5. Colour of the winner, per channel: n = (t0 * col[i0] + t1 * col[i1]) + t2 * col[i2] in fp64,
+ *     v = (float)(n / S).  With a light L (3 finite floats along the voxel axes x, y, z): c = a x b
+ *     with a = p[i2] - p[i0], b = p[i1] - p[i0] (the smoothing block's face normal, fp32);
+ *     l = sqrtf((c.x * c.x + c.y * c.y) + c.z * c.z), m the same expression over L;
+ *     d = (c.x * L.x + c.y * L.y) + c.z * L.z; f = (l == 0 || m == 0) ? 1 : fminf(fabsf(d) / (l * m), 1);
+ *     v = (0.25f + 0.75f * f) * v.  The pixel's channel is arvx_render's
+ *     (uint8_t)roundf(fminf(fmaxf(v, 0.f), 255.f)), stored B, G, R.
+ *  6. Images, as arvx_render's: id = the winner's t, an index into the source's face list (-1 where
+ *     there is none), depth (+inf where there is none), bgr (the background or zeros where there is
+ *     none).
+ * Sources: ARVX_MESH_WELDED -- the mesh of arvx_mc_mesh_welded, lattice positions --,
+ * ARVX_MESH_SMOOTHED -- the same faces and colours with the positions of the last arvx_mc_mesh_smooth
+ * --, ARVX_MESH_DECIMATED -- arvx_mc_mesh_decimate's --, ARVX_MESH_REFINED -- arvx_mc_mesh_refined's.
+ * arvx_render_triangles draws a caller's mesh instead: nv positions and colours (3 floats each), nt
+ * face records {i0, i1, i2, r, g, b} as the mesh downloads return them (r, g, b are not read); the
+ * arrays are copied before the call returns, into buffers of their own.
+ * arvx_render_mesh takes the camera, an optional background and an optional light (NULL: unshaded) as
+ * arvx_render does; arvx_render_mesh_view takes M_v, W, H of the context's view.  Neither
+ * synchronises.  The result is the context's current render: arvx_render_download returns it, and it
+ * lives and ends exactly as a render of arvx_render does (its lifetime paragraph; the next render of
+ * either kind replaces it).  The images are resolved inside the call: a later change of the source
+ * mesh does not touch them.  arvx_render_mesh_agreement renders view `view` unshaded, leaves that
+ * render as the current one and counts as arvx_render_agreement does, with ONE host synchronisation.
+ * arvx_render_mesh_stats returns the class counts of the current render, {DRAWN, EMPTY, FLAT,
+ * REFUSED}; they sum to T; it synchronises.  An empty mesh renders the background.
+ * Refusals.  ARVX_ERR_STATE: the source mesh does not exist (slab and striped contexts never have
+ * one); the _view and _agreement forms without views, or the agreement form when the views were set
+ * with masks == NULL; arvx_render_mesh_stats when the current render is no triangle render;
+ * arvx_render_triangles on a slab or a striped context.  ARVX_ERR_INVALID: an unknown source; a null
+ * M or a non-finite entry of it, W or H out of range, bg_stride < 3 W, a view outside [0, V), a
+ * non-finite light, null counts; for arvx_render_triangles a negative count, a null array with a
+ * non-zero count, or a face index >= nv (checked on the host before anything is enqueued).  A refused
+ * call leaves the previous render as it was.
+ * Device memory beside the render's, sized at first use and kept: 16 bytes per vertex of projected
+ * positions and the list of triangles whose pixel box exceeds 64 pixels (16 bytes each), swept by a
+ * wave each; what does not fit the list is swept by the wave that found it.
+ * Out of scope: near-plane and guard-band clipping, anti-aliasing, per-vertex normals, textures,
+ * slabs and multi-GPU. */
+#define ARVX_MESH_WELDED 0
+#define ARVX_MESH_SMOOTHED 1
+#define ARVX_MESH_DECIMATED 2
+#define ARVX_MESH_REFINED 3
+int arvx_render_mesh(arvx_ctx *ctx, int source, const float M[12], int W, int H, const uint8_t *background,
+                     size_t bg_stride, const float *light);
+int arvx_render_mesh_view(arvx_ctx *ctx, int source, int view, const float *light);
+int arvx_render_mesh_agreement(arvx_ctx *ctx, int source, int view, int64_t counts[3]);
+int arvx_render_triangles(arvx_ctx *ctx, int64_t nv, const float *verts, const float *vertex_rgb, int64_t nt,
+                          const uint32_t *faces, const float M[12], int W, int H, const uint8_t *background,
+                          size_t bg_stride, const float *light);
+int arvx_render_mesh_stats(arvx_ctx *ctx, int64_t out[4]);
+/* Self-test hook: room of the triangle render's list of large pixel boxes from the next render on
+ * (0: everything large is swept in place; -1: the default sizing).  The room changes the time, never
+ * the images. */
+int arvx_selftest_render_mesh_list(arvx_ctx *ctx, int64_t cap);
 
 /* Model::voxels as the reference would hold it after carve [+ colour]
  * [+ handleUnseen]: n*4 floats (RGBA), n = slab voxels. */

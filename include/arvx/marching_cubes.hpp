@@ -692,6 +692,80 @@ inline bool marchingCubesRefined(const Intrinsics &intr, Model *model, const std
                                         });
 }
 
+// ---- triangle render (an extension beyond the reference) -----------------------------------------
+//
+// A mesh's triangles drawn into a camera view on the device with a depth buffer (arvx_render_mesh,
+// defined in include/arvx/arvx.h): M, W, H and background as for renderWelded; light, if given, is 3
+// floats along the voxel axes that shade every face by the angle between its normal and the light
+// ({M[9], M[8], -M[10]}: a light at the camera).  id holds indices into the mesh's triangle list.
+namespace detail {
+inline RenderedView rendered_view(arvx_ctx *ctx, int W, int H) {
+    RenderedView out;
+    out.W = W;
+    out.H = H;
+    out.bgr.resize((size_t)W * H * 3);
+    out.depth.resize((size_t)W * H);
+    out.id.resize((size_t)W * H);
+    check(arvx_render_download(ctx, out.bgr.data(), out.depth.data(), out.id.data()), "arvx_render_download");
+    return out;
+}
+}  // namespace detail
+
+// Draws the mesh `source` (ARVX_MESH_WELDED, _SMOOTHED, _DECIMATED, _REFINED) that the model's context
+// holds: the one the last marchingCubesMeshWelded / Smoothed / Decimated / Refined of this model built
+// on the device, also after the model has moved on (renderWelded's note).  Only a missing welded mesh
+// is built here, as renderWelded builds it; any other source that the context does not hold throws.
+inline RenderedView renderMesh(Model *model, int source, const float M[12], int W, int H,
+                               const uint8_t *background = nullptr, const float *light = nullptr) {
+    arvx_ctx *ctx = model->device_for_reading();
+    const size_t stride = (size_t)(W > 0 ? W : 0) * 3;
+    int rc = arvx_render_mesh(ctx, source, M, W, H, background, stride, light);
+    if (rc == ARVX_ERR_STATE && source == ARVX_MESH_WELDED) {  // no welded mesh yet
+        bool on_device = false;
+        (void)model->inside_state(0.5f, on_device);
+        if (on_device) {
+            int apply_unseen = 0;
+            ctx = detail::mesh_context(model, apply_unseen);
+            int64_t nv = 0, nt = 0;
+            detail::check(arvx_mc_mesh_welded(ctx, apply_unseen, &nv, &nt), "arvx_mc_mesh_welded");
+            rc = arvx_render_mesh(ctx, source, M, W, H, background, stride, light);
+        }
+    }
+    detail::check(rc, "arvx_render_mesh");
+    return detail::rendered_view(ctx, W, H);
+}
+
+// Draws a mesh of the caller's on the model's context (arvx_render_triangles): its vertices in voxel
+// units, as the marchingCubesMesh* calls return them.  vertex_rgb: 3 floats per vertex; null: every
+// vertex takes the colour of the first triangle that contains it (black where there is none).
+inline RenderedView renderMesh(Model *model, const SimpleMesh &mesh, const float M[12], int W, int H,
+                               const uint8_t *background = nullptr, const float *light = nullptr,
+                               const float *vertex_rgb = nullptr) {
+    arvx_ctx *ctx = model->device_for_reading();
+    const HostVector<Vec3f> &mv = mesh.GetVertices();
+    const HostVector<Triangle> &mt = mesh.GetTriangles();
+    std::vector<float> rgb;
+    if (!vertex_rgb) {
+        rgb.assign(3 * mv.size(), 0.f);
+        for (size_t t = mt.size(); t-- > 0;) {  // (descending: the first triangle writes last)
+            const unsigned corner[3] = {mt[t].idx0, mt[t].idx1, mt[t].idx2};
+            for (unsigned i : corner) {
+                if (i >= mv.size()) continue;  // (the call refuses the mesh)
+                rgb[3 * (size_t)i] = (float)mt[t].r;
+                rgb[3 * (size_t)i + 1] = (float)mt[t].g;
+                rgb[3 * (size_t)i + 2] = (float)mt[t].b;
+            }
+        }
+        vertex_rgb = rgb.data();
+    }
+    static_assert(sizeof(Triangle) == 24, "a face record: three indices, then r, g, b");
+    detail::check(arvx_render_triangles(ctx, (int64_t)mv.size(), mv.empty() ? nullptr : mv[0].data(), vertex_rgb, (int64_t)mt.size(),
+                                        mt.empty() ? nullptr : &mt[0].idx0, M, W, H, background,
+                                        (size_t)(W > 0 ? W : 0) * 3, light),
+                  "arvx_render_triangles");
+    return detail::rendered_view(ctx, W, H);
+}
+
 namespace detail {
 // carve(..., intermediateMeshes = true) without a caller-supplied hook writes what the
 // reference writes after every view (src/VoxelCarving.cpp:65-68): the model so far, moved

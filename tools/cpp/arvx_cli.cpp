@@ -166,8 +166,10 @@ bool load_poses(const std::string &path, std::vector<arvx::View> &views) {
     return true;
 }
 
-// -render=DIR: DIR/render%04d.ppm per view, and one line per view with the agreement counts
-bool render_views(const std::string &dir, const Inputs &in, arvx::Model &model) {
+// -render=DIR: DIR/render%04d.ppm per view, and one line per view with the agreement counts.
+// mesh_source < 0: the welded mesh's vertex voxels (arvx_render); else, -renderMesh=true: the triangles
+// of that mesh of the context (ARVX_MESH_*), shaded by a light at the camera (arvx_render_mesh).
+bool render_views(const std::string &dir, const Inputs &in, arvx::Model &model, int mesh_source) {
     fs::create_directories(dir);
     const int V = (int)in.views.size();
     std::vector<uint8_t> bg, rgb;
@@ -186,7 +188,10 @@ bool render_views(const std::string &dir, const Inputs &in, arvx::Model &model) 
             for (int r = 0; r < H; ++r)
                 std::memcpy(bg.data() + (size_t)r * W * 3, im.data + (size_t)r * im.stride, (size_t)W * 3);
         }
-        const arvx::RenderedView out = arvx::renderWelded(&model, M, W, H, over ? bg.data() : nullptr);
+        const float light[3] = {M[9], M[8], -M[10]};  // the viewing direction along the voxel axes
+        const arvx::RenderedView out =
+            mesh_source < 0 ? arvx::renderWelded(&model, M, W, H, over ? bg.data() : nullptr)
+                            : arvx::renderMesh(&model, mesh_source, M, W, H, over ? bg.data() : nullptr, light);
         rgb.resize(out.bgr.size());
         for (size_t p = 0; p < out.bgr.size(); p += 3) {
             rgb[p] = out.bgr[p + 2];
@@ -208,8 +213,11 @@ bool render_views(const std::string &dir, const Inputs &in, arvx::Model &model) 
     model.set_colors_on_device(false);
     for (int i = 0; i < V; ++i) {
         int64_t n[3];
-        arvx::detail::check(arvx_render_agreement(ctx, i, n), "arvx_render_agreement");
-        std::cout << "LOG - RENDER: view " << i << " both " << n[0] << " model_only " << n[1] << " mask_only "
+        if (mesh_source < 0)
+            arvx::detail::check(arvx_render_agreement(ctx, i, n), "arvx_render_agreement");
+        else
+            arvx::detail::check(arvx_render_mesh_agreement(ctx, mesh_source, i, n), "arvx_render_mesh_agreement");
+        std::cout << (mesh_source < 0 ? "LOG - RENDER: view " : "LOG - RENDER MESH: view ") << i << " both " << n[0] << " model_only " << n[1] << " mask_only "
                   << n[2] << std::endl;
     }
     return true;
@@ -229,7 +237,7 @@ int main(int argc, char *argv[]) {
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
         {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"},
-        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}};
+        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"renderMesh", "false"}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -260,7 +268,10 @@ int main(int argc, char *argv[]) {
                      "    ball of radius R voxels, R >= 0 a float; at most one of them; an opening removes\n"
                      "    what is thinner than the ball, and -largest=true then drops what it cut loose),\n"
                      "  -render=DIR (after the mesh: the welded model drawn over every input image,\n"
-                     "    DIR/renderNNNN.ppm, and its agreement with every mask)\n";
+                     "    DIR/renderNNNN.ppm, and its agreement with every mask),\n"
+                     "  -renderMesh=true (with -render: the triangles of the mesh the run wrote -- refined,\n"
+                     "    decimated, smoothed, else welded -- with a depth buffer and a light at the camera,\n"
+                     "    in place of the welded model's voxels)\n";
         return 0;
     }
     const int choose = parser.i("c");
@@ -504,7 +515,13 @@ int main(int argc, char *argv[]) {
             arvx::marchingCubes(&model, parser.f("scale"), modelTranslation, 0.5f, parser.str("outFile"));
         // -render=DIR (an extension beyond the reference): the welded mesh's vertex voxels drawn
         // into every view over its input image, then each render's agreement with the view's mask
-        if (!parser.str("render").empty() && !render_views(parser.str("render"), in, model)) return 1;
+        // -renderMesh=true: the triangles of the mesh written above instead, with a headlight
+        const int mesh_source = !parser.b("renderMesh")          ? -1
+                                : !parser.str("refine").empty() ? ARVX_MESH_REFINED
+                                : parser.i("decimate") > 0      ? ARVX_MESH_DECIMATED
+                                : parser.i("smooth") > 0        ? ARVX_MESH_SMOOTHED
+                                                                : ARVX_MESH_WELDED;
+        if (!parser.str("render").empty() && !render_views(parser.str("render"), in, model, mesh_source)) return 1;
     } catch (const arvx::Error &e) {
         return 3;  // (already logged)
     }
