@@ -54,6 +54,8 @@ MESH_WELDED = 0
 MESH_SMOOTHED = 1
 MESH_DECIMATED = 2
 MESH_REFINED = 3
+MESH_IMAGE_COLORS = 0x100  # OR-ed into `source` of the render_mesh family: draw mesh_color()'s colours
+MESH_COLOR_FOREGROUND = 1  # flags of mesh_color
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
 # whole test module with the streaming carve forced on every fresh model (the library itself reads
 # no environment variable)
@@ -93,6 +95,8 @@ SYMBOLS = [
     "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
     "arvx_render_mesh", "arvx_render_mesh_view", "arvx_render_mesh_agreement", "arvx_render_triangles",
     "arvx_render_mesh_stats", "arvx_selftest_render_mesh_list",
+    "arvx_mesh_color", "arvx_mesh_color_count", "arvx_mesh_color_download", "arvx_mesh_color_depth_download",
+    "arvx_selftest_mesh_color_batch",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
     "arvx_export_model", "arvx_get_stats", "arvx_last_carve_path", "arvx_last_fast_carve_path",
@@ -277,6 +281,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                               C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.arvx_render_mesh_stats.argtypes = [p, C.POINTER(C.c_int64)]
         lib.arvx_selftest_render_mesh_list.argtypes = [p, C.c_int64]
+    if hasattr(lib, "arvx_mesh_color") or not ab_build:
+        lib.arvx_mesh_color.argtypes = [p, C.c_int, C.c_int, C.c_float, C.c_uint, C.POINTER(C.c_int64)]
+        lib.arvx_mesh_color_count.argtypes = [p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.arvx_mesh_color_download.argtypes = [p, C.c_void_p, C.c_void_p]
+        lib.arvx_mesh_color_depth_download.argtypes = [p, C.c_int, C.c_void_p]
+        lib.arvx_selftest_mesh_color_batch.argtypes = [p, C.c_int]
     for name in SYMBOLS:
         if ab_build and not hasattr(lib, name):
             continue
@@ -1086,6 +1096,44 @@ class Context:
     def selftest_render_mesh_list(self, cap: int) -> None:
         """Room of the triangle render's list of large pixel boxes from the next render on (-1: default)."""
         self._ck(self._lib.arvx_selftest_render_mesh_list(self._h, int(cap)))
+
+    def mesh_color(self, source: int, mode: int, tolerance: float, flags: int = 0, download: bool = True):
+        """arvx_mesh_color: the vertices of the context's mesh `source` coloured from the images -- per
+        view the depth buffer of the mesh's own triangles, per vertex a vote (COLOR_CLOSEST or
+        COLOR_AVERAGE) over the views that see it within `tolerance`, sampled bilinearly;
+        MESH_COLOR_FOREGROUND drops the views whose mask has the vertex's pixel as background.
+        -> (rgb (Vn, 3) float32, views (Vn,) int32: the views that see each vertex, coloured: the
+        vertices some view sees).  render_mesh(source | MESH_IMAGE_COLORS, ...) draws them.
+        download=False: the call only, -> coloured."""
+        n = C.c_int64()
+        self._ck(self._lib.arvx_mesh_color(self._h, int(source), int(mode), float(tolerance), int(flags),
+                                           C.byref(n)))
+        self._mesh_color_wh = (self.W, self.H)  # (the product keeps the image size of its call)
+        if not download:
+            return int(n.value)
+        return self.mesh_color_download() + (int(n.value),)
+
+    def mesh_color_download(self):
+        """arvx_mesh_color_download: (rgb, views) of the product of the last mesh_color()."""
+        nv = C.c_int64()
+        self._ck(self._lib.arvx_mesh_color_count(self._h, C.byref(nv), None))
+        rgb = np.empty((nv.value, 3), np.float32)
+        views = np.empty(nv.value, np.int32)
+        self._ck(self._lib.arvx_mesh_color_download(self._h, rgb.ctypes.data, views.ctypes.data))
+        return rgb, views
+
+    def mesh_color_depth(self, view: int) -> np.ndarray:
+        """arvx_mesh_color_depth_download: the depth buffer of view `view` that mesh_color() voted with,
+        (H, W) float32, +inf where no triangle covers the pixel."""
+        self._ck(self._lib.arvx_mesh_color_count(self._h, None, None))  # (no product: refused before any buffer)
+        W, H = self._mesh_color_wh
+        d = np.empty((H, W), np.float32)
+        self._ck(self._lib.arvx_mesh_color_depth_download(self._h, int(view), d.ctypes.data))
+        return d
+
+    def selftest_mesh_color_batch(self, views_per_batch: int) -> None:
+        """Views per batch of mesh_color()'s depth pass from the next call on (0: the default bound)."""
+        self._ck(self._lib.arvx_selftest_mesh_color_batch(self._h, int(views_per_batch)))
 
     def mc_mesh_count(self, apply_unseen: bool = False) -> int:
         """arvx_mc_mesh without the download: the triangles stay on the device."""

@@ -45,6 +45,7 @@
 #include "vote_kernels.h"
 #include "render_kernels.h"
 #include "render_mesh_kernels.h"
+#include "mesh_color_kernels.h"
 #include "exchange_kernels.h"
 #include <algorithm>
 
@@ -3552,6 +3553,8 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     ctx->smooth_ready = ctx->smooth_csr_ready = false;  // (a new mesh: new CSRs)
     ctx->dec_ready = false;                              // (... and the old one's decimation goes)
     ctx->render_ready = false;                           // (... and the old one's render goes)
+    for (int src : {ARVX_MESH_WELDED, ARVX_MESH_SMOOTHED, ARVX_MESH_DECIMATED})
+        ctx->mesh_color_ended(src);                      // (... and the image colours of the three)
     ctx->weld_verts = ctx->weld_tris = 0;
     *vertices = *triangles = 0;
     const arvx::BitGrid g = bit_grid(ctx);
@@ -3632,6 +3635,7 @@ int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu) {
         return fail(ARVX_ERR_INVALID, "iterations must be >= 0 and the factors finite");
     if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
     ctx->smooth_ready = false;
+    ctx->mesh_color_ended(ARVX_MESH_SMOOTHED);
     const long long V = ctx->weld_verts, T = ctx->weld_tris;
     if (V == 0) {
         ctx->smooth_q = 0;
@@ -3673,6 +3677,7 @@ int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals) {
     ARVX_HIP(hipStreamSynchronize(ctx->stream));
     if (int rc = check_fault(ctx)) {  // (a scan gave up: the CSRs are built again)
         ctx->smooth_ready = ctx->smooth_csr_ready = false;
+        ctx->mesh_color_ended(ARVX_MESH_SMOOTHED);
         return rc;
     }
     return ARVX_OK;
@@ -3691,6 +3696,7 @@ int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices
     if (source == ARVX_DECIMATE_SMOOTHED && !ctx->smooth_ready)
         return fail(ARVX_ERR_STATE, "no smoothed mesh on this welded mesh (call arvx_mc_mesh_smooth)");
     ctx->dec_ready = false;
+    ctx->mesh_color_ended(ARVX_MESH_DECIMATED);
     ctx->dec_verts = ctx->dec_tris = 0;
     const long long V = ctx->weld_verts, T = ctx->weld_tris;
     if (V == 0) {
@@ -3794,6 +3800,7 @@ int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_
     if (int crc = closure_of_other_unseen(ctx, apply_unseen)) return crc;
     ctx->free_mc();
     ctx->ref_ready = false;
+    ctx->mesh_color_ended(ARVX_MESH_REFINED);
     ctx->ref_verts = ctx->ref_tris = 0;
     *vertices = *triangles = 0;
     const arvx::BitGrid g = bit_grid(ctx);
@@ -4010,29 +4017,38 @@ struct MeshSource {
 };
 
 // The context's mesh `source`, or the refusal: an unknown source, or a mesh that does not exist
-// (slab and striped contexts never build one).
-static int mesh_source(const Ctx *ctx, int source, MeshSource &m) {
-    switch (source) {
+// (slab and striped contexts never build one).  With ARVX_MESH_IMAGE_COLORS (where the caller allows
+// it) the colours are arvx_mesh_color's of that source.
+static int mesh_source(const Ctx *ctx, int source, MeshSource &m, bool image_colours_allowed = true) {
+    const int base = image_colours_allowed ? source & ~ARVX_MESH_IMAGE_COLORS : source;
+    switch (base) {
     case ARVX_MESH_WELDED:
     case ARVX_MESH_SMOOTHED:
         if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
-        if (source == ARVX_MESH_SMOOTHED && !ctx->smooth_ready)
+        if (base == ARVX_MESH_SMOOTHED && !ctx->smooth_ready)
             return fail(ARVX_ERR_STATE, "no smoothed mesh (call arvx_mc_mesh_smooth)");
-        m = MeshSource{ctx->smooth_xyz(source == ARVX_MESH_WELDED ? 0 : ctx->smooth_q), ctx->pool_weld_rgb.data(),
+        m = MeshSource{ctx->smooth_xyz(base == ARVX_MESH_WELDED ? 0 : ctx->smooth_q), ctx->pool_weld_rgb.data(),
                        ctx->pool_weld_faces.data(), ctx->weld_verts, ctx->weld_tris};
-        return ARVX_OK;
+        break;
     case ARVX_MESH_DECIMATED:
         if (!ctx->dec_ready) return fail(ARVX_ERR_STATE, "no decimated mesh (call arvx_mc_mesh_decimate)");
         m = MeshSource{ctx->pool_dec_verts.data(), ctx->pool_dec_rgb.data(), ctx->pool_dec_faces.data(),
                        ctx->dec_verts, ctx->dec_tris};
-        return ARVX_OK;
+        break;
     case ARVX_MESH_REFINED:
         if (!ctx->ref_ready) return fail(ARVX_ERR_STATE, "no refined mesh (call arvx_mc_mesh_refined)");
         m = MeshSource{ctx->pool_ref_verts.data(), ctx->pool_ref_rgb.data(), ctx->pool_ref_faces.data(),
                        ctx->ref_verts, ctx->ref_tris};
-        return ARVX_OK;
+        break;
+    default:
+        return fail(ARVX_ERR_INVALID, "unknown mesh source %d", source);
     }
-    return fail(ARVX_ERR_INVALID, "unknown mesh source %d", source);
+    if (base != source) {
+        if (!ctx->mesh_color_ready || ctx->mesh_color_source != base)
+            return fail(ARVX_ERR_STATE, "no image colours of mesh source %d (call arvx_mesh_color)", base);
+        m.rgb = ctx->pool_mcol_rgb.data();  // (as many as the source has vertices: the product ends with them)
+    }
+    return ARVX_OK;
 }
 
 // the refusals of a camera, an image size, a background and a light
@@ -4195,6 +4211,152 @@ int arvx_selftest_render_mesh_list(arvx_ctx *ctx, int64_t cap) {
     ARVX_CHECK_CTX(ctx);
     if (cap < -1) return fail(ARVX_ERR_INVALID, "cap %lld (-1: the default room)", (long long)cap);
     ctx->render_mesh_list_cap = cap;
+    return ARVX_OK;
+}
+
+// ---- mesh colours from the images (mesh_color_kernels.h) -------------------------------------
+
+// the projected vertices of one batch of views: never more than this, or one view's
+static constexpr size_t kMeshColorProjBytes = (size_t)64 << 20;
+
+int arvx_mesh_color(arvx_ctx *ctx, int source, int mode, float tolerance, unsigned flags, int64_t *coloured) {
+    ARVX_CHECK_CTX(ctx);
+    if (!whole_grid(ctx)) return fail(ARVX_ERR_STATE, "arvx_mesh_color needs a whole-grid context");
+    MeshSource m;
+    if (int rc = mesh_source(ctx, source, m, false)) return rc;
+    if (mode != ARVX_COLOR_CLOSEST && mode != ARVX_COLOR_AVERAGE) return fail(ARVX_ERR_INVALID, "colour mode %d", mode);
+    if (flags & ~ARVX_MESH_COLOR_FOREGROUND) return fail(ARVX_ERR_INVALID, "unknown flag bits %#x", flags);
+    if (std::isnan(tolerance) || tolerance < 0.f)
+        return fail(ARVX_ERR_INVALID, "tolerance %g: must be >= 0 (finite or +inf)", (double)tolerance);
+    if (!coloured) return fail(ARVX_ERR_INVALID, "null coloured");
+    if (!ctx->cameras_ready) return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
+    if (!ctx->images_ready) return fail(ARVX_ERR_STATE, "arvx_set_images has not been called");
+    if ((flags & ARVX_MESH_COLOR_FOREGROUND) && !ctx->views_ready)
+        return fail(ARVX_ERR_STATE, "ARVX_MESH_COLOR_FOREGROUND: arvx_set_views was given no masks");
+    if (m.T > (long long)UINT32_MAX) return fail(ARVX_ERR_STATE, "the mesh is too long");
+    ctx->mesh_color_ready = false;
+    const int V = ctx->V, W = ctx->W, H = ctx->H;
+    const size_t npix = (size_t)W * H;
+    const bool faces = m.T > 0 && m.V > 0;
+    // views per batch: what the bound on the projected vertices holds (one view at least)
+    long long batch = std::max<long long>(1, (long long)(kMeshColorProjBytes / sizeof(arvx::MeshVertex)) / std::max(m.V, 1ll));
+    if (ctx->mesh_color_batch > 0) batch = ctx->mesh_color_batch;
+    batch = std::min<long long>({batch, V, 65535});
+    // large pixel boxes of a batch (large_list_cap): never more than its (triangle, view) pairs
+    const long long pairs = faces ? m.T * batch : 0;
+    const unsigned large_cap =
+        ctx->render_mesh_list_cap >= 0
+            ? (unsigned)std::min<long long>({ctx->render_mesh_list_cap, pairs, (long long)UINT32_MAX})
+            : large_list_cap(pairs, ctx->mesh_color_need, pairs);
+    ARVX_HIP(ctx->pool_mcol_keys.reserve((size_t)V * npix * sizeof(unsigned long long)));
+    ARVX_HIP(ctx->pool_mcol_rgb.reserve((size_t)m.V * Ctx::kVertexBytes));
+    ARVX_HIP(ctx->pool_mcol_views.reserve((size_t)m.V * sizeof(int)));
+    ARVX_HIP(ctx->pool_mcol_large.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
+    static_assert(sizeof(arvx::MeshColorHeader) <= 64, "the header ends before the list");
+    arvx::MeshColorHeader *head = (arvx::MeshColorHeader *)ctx->pool_mcol_large.p;
+    unsigned long long *keys = (unsigned long long *)ctx->pool_mcol_keys.p;
+    ARVX_HIP(hipMemsetAsync(keys, 0xFF, (size_t)V * npix * sizeof(unsigned long long), ctx->stream));  // (kRenderEmpty)
+    ARVX_HIP(hipMemsetAsync(head, 0, 64, ctx->stream));
+    const int ncu = compute_units(ctx);
+    if (faces) {
+        ARVX_HIP(ctx->pool_mcol_proj.reserve((size_t)batch * (size_t)m.V * sizeof(arvx::MeshVertex)));
+        arvx::MeshColorParams p{};
+        p.mesh.verts = m.verts, p.mesh.faces = m.faces;
+        p.mesh.V = m.V, p.mesh.T = m.T;
+        p.mesh.s = ctx->s;
+        p.mesh.W = W, p.mesh.H = H;
+        p.mesh.proj = (arvx::MeshVertex *)ctx->pool_mcol_proj.p;
+        p.mesh.large = (arvx::SplatRect *)((uint8_t *)ctx->pool_mcol_large.p + 64);
+        p.mesh.large_cap = large_cap;
+        p.M = (const arvx::SelftestMatrix *)ctx->M();
+        p.head = head;
+        // (the grid strides over the faces: as many workgroups in all as the render's raster has)
+        const unsigned tblocks = (unsigned)std::max<long long>(
+            1, std::min<long long>((m.T + 255) / 256, (8ll * ncu + batch - 1) / batch));
+        for (int v0 = 0; v0 < V; v0 += (int)batch) {
+            p.view0 = v0;
+            p.nviews = (int)std::min<long long>(batch, V - v0);
+            p.mesh.keys = keys + (size_t)v0 * npix;
+            if (v0 > 0) ARVX_HIP(hipMemsetAsync(&head->n_large, 0, sizeof head->n_large, ctx->stream));
+            ARVX_TRY(by_assoc(ctx, [&](auto left) {
+                return launch(ctx, arvx::mesh_color_project_kernel<decltype(left)::value>,
+                              dim3(blocks_for(m.V), p.nviews), 256, p);
+            }));
+            ARVX_TRY(launch(ctx, arvx::mesh_color_raster_kernel, dim3(tblocks, p.nviews), 256, p));
+            ARVX_TRY(launch(ctx, arvx::mesh_color_large_kernel, (unsigned)(4 * ncu), 256, p,
+                            ctx->word_dev(Ctx::kMeshColorNeed)));
+        }
+    }
+    unsigned long long n_coloured = 0;
+    if (m.V > 0) {
+        arvx::MeshVoteParams vp{};
+        vp.verts = m.verts, vp.col = m.rgb;
+        vp.Vn = m.V;
+        vp.s = ctx->s;
+        vp.V = V, vp.W = W, vp.H = H;
+        vp.M = (const arvx::SelftestMatrix *)ctx->M();
+        vp.keys = keys;
+        vp.bg = (flags & ARVX_MESH_COLOR_FOREGROUND) ? ctx->bg() : nullptr;
+        vp.bgWords = ctx->bgWords;
+        vp.images = ctx->images();
+        vp.average = mode == ARVX_COLOR_AVERAGE;
+        vp.tol = tolerance;
+        vp.rgb = ctx->pool_mcol_rgb.data();
+        vp.views = ctx->pool_mcol_views.data();
+        vp.coloured = &head->coloured;
+        ARVX_TRY(by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::mesh_color_vote_kernel<decltype(left)::value>, blocks_for(m.V), 256, vp);
+        }));
+        ARVX_HIP(hipMemcpyAsync(&n_coloured, &head->coloured, sizeof n_coloured, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    ARVX_SYNC(ctx);
+    if (faces) ctx->mesh_color_need = std::max(ctx->word(Ctx::kMeshColorNeed), 0ll);
+    ctx->mesh_color_source = source;
+    ctx->mesh_color_V = V, ctx->mesh_color_W = W, ctx->mesh_color_H = H;
+    ctx->mesh_color_verts = m.V;
+    *coloured = ctx->mesh_color_coloured = (int64_t)n_coloured;
+    ctx->mesh_color_ready = true;
+    return ARVX_OK;
+}
+
+int arvx_mesh_color_count(arvx_ctx *ctx, int64_t *vertices, int64_t *coloured) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->mesh_color_ready) return fail(ARVX_ERR_STATE, "no image colours (call arvx_mesh_color)");
+    if (vertices) *vertices = ctx->mesh_color_verts;
+    if (coloured) *coloured = ctx->mesh_color_coloured;
+    return ARVX_OK;
+}
+
+int arvx_mesh_color_download(arvx_ctx *ctx, float *vertex_rgb, int32_t *views) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->mesh_color_ready) return fail(ARVX_ERR_STATE, "no image colours (call arvx_mesh_color)");
+    const size_t Vn = (size_t)ctx->mesh_color_verts;
+    ARVX_TRY(download(ctx, vertex_rgb, ctx->pool_mcol_rgb.data(), Vn, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, views, ctx->pool_mcol_views.data(), Vn, sizeof(int32_t)));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+int arvx_mesh_color_depth_download(arvx_ctx *ctx, int view, float *depth) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->mesh_color_ready) return fail(ARVX_ERR_STATE, "no image colours (call arvx_mesh_color)");
+    if (view < 0 || view >= ctx->mesh_color_V)
+        return fail(ARVX_ERR_INVALID, "view %d outside [0,%d)", view, ctx->mesh_color_V);
+    if (!depth) return fail(ARVX_ERR_INVALID, "null depth");
+    const size_t npix = (size_t)ctx->mesh_color_W * ctx->mesh_color_H;
+    ARVX_HIP(ctx->pool_mcol_depth.reserve(npix * sizeof(float)));
+    ARVX_TRY(launch(ctx, arvx::mesh_color_depth_kernel, blocks_for(npix), 256,
+                    (const unsigned long long *)ctx->pool_mcol_keys.p + (size_t)view * npix, npix,
+                    ctx->pool_mcol_depth.data()));
+    ARVX_TRY(download(ctx, depth, ctx->pool_mcol_depth.data(), npix, sizeof(float)));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+int arvx_selftest_mesh_color_batch(arvx_ctx *ctx, int views_per_batch) {
+    ARVX_CHECK_CTX(ctx);
+    if (views_per_batch < 0) return fail(ARVX_ERR_INVALID, "views_per_batch %d (0: the default bound)", views_per_batch);
+    ctx->mesh_color_batch = views_per_batch;
     return ARVX_OK;
 }
 

@@ -92,9 +92,10 @@ struct Ctx {
         kRectMiss = kRenderAgree + 3,   // a block's rectangle did not fit its table entry (rect_cache_kernels.h)
         kMorphChanged,                  // arvx_morph: voxels that left or joined the model
         kRenderMeshNeed,                // the triangle render's large pixel boxes
+        kMeshColorNeed,                 // arvx_mesh_color: the large pixel boxes of its fullest batch
         kWords
     };
-    static constexpr size_t kHostBlockBytes = 192;
+    static constexpr size_t kHostBlockBytes = 256;
     static_assert(8 + 8 * (size_t)kWords <= kHostBlockBytes, "the count words fit the block");
     long long &word(int w) const { return ((long long *)(h_fault + 2))[w]; }      // host value
     long long *word_dev(int w) const { return (long long *)(d_fault + 2) + w; }  // device address
@@ -492,6 +493,23 @@ struct Ctx {
     DevArray<unsigned> pool_tri_faces;
     bool render_tris = false;
     long long render_mesh_need = 0, render_mesh_list_cap = -1;
+    // arvx_mesh_color (mesh_color_kernels.h): the product -- per vertex r, g, b and the number of views
+    // that see it, the V x H x W depth keys, tagged with its source (read only while mesh_color_ready is
+    // set) -- and its workspace: the projected vertices of one batch of views, the list of large pixel
+    // boxes behind its header (sized from kMeshColorNeed, or by arvx_selftest_render_mesh_list), the
+    // depth image a download converts a view's keys into.  None of them is the render's: a call leaves
+    // the current render as it is.  mesh_color_ended(source) is called where a mesh stage replaces or
+    // drops the arrays of `source`.
+    DevArray<float> pool_mcol_rgb, pool_mcol_depth;
+    DevArray<int> pool_mcol_views;
+    DevPool pool_mcol_keys{DevPool::Exact}, pool_mcol_proj, pool_mcol_large{DevPool::Exact};
+    bool mesh_color_ready = false;
+    int mesh_color_source = 0, mesh_color_V = 0, mesh_color_W = 0, mesh_color_H = 0;
+    int64_t mesh_color_verts = 0, mesh_color_coloured = 0;
+    long long mesh_color_need = 0, mesh_color_batch = 0;  // (batch: arvx_selftest_mesh_color_batch; 0: the bound)
+    void mesh_color_ended(int source) {
+        if (mesh_color_source == source) mesh_color_ready = false;
+    }
 
     // (the device buffers are freed by their DevPool members, after this)
     ~Ctx() {

@@ -62,17 +62,16 @@ struct RenderMeshParams {
     int lit;
 };
 
+// Step 1 of the definition for the point (px, py, pz) under camera M: the one place it is computed
+// (the mesh colours' kernels, mesh_color_kernels.h, project with it too).
 template <bool LEFT>
-__global__ __launch_bounds__(256) void render_mesh_project_kernel(const RenderMeshParams p) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= p.V) return;
-    const float px = p.verts[3 * i], py = p.verts[3 * i + 1], pz = p.verts[3 * i + 2];
-    const double w0 = (double)(py * p.s), w1 = (double)(px * p.s), w2 = (double)((-pz) * p.s);
+__device__ __forceinline__ MeshVertex mesh_project(const SelftestMatrix &M, float s, float px, float py, float pz) {
+    const double w0 = (double)(py * s), w1 = (double)(px * s), w2 = (double)((-pz) * s);
     float a[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
-        a[r] = row_sum<LEFT>((double)p.M.m[4 * r] * w0, (double)p.M.m[4 * r + 1] * w1,
-                             (double)p.M.m[4 * r + 2] * w2, (double)p.M.m[4 * r + 3]);
+        a[r] = row_sum<LEFT>((double)M.m[4 * r] * w0, (double)M.m[4 * r + 1] * w1, (double)M.m[4 * r + 2] * w2,
+                             (double)M.m[4 * r + 3]);
     const float qu = a[0] / a[2], qv = a[1] / a[2];
     const bool valid = a[2] >= FLT_MIN && isfinite(qu) && isfinite(qv) && fabsf(qu) <= kMeshMaxPixel &&
                        fabsf(qv) <= kMeshMaxPixel;
@@ -81,7 +80,19 @@ __global__ __launch_bounds__(256) void render_mesh_project_kernel(const RenderMe
         out.fx = (int)roundf(qu * 16.0f);
         out.fy = (int)roundf(qv * 16.0f);
     }
-    *reinterpret_cast<int4 *>(p.proj + i) = make_int4(out.fx, out.fy, (int)out.a2, out.valid);
+    return out;
+}
+
+__device__ __forceinline__ void mesh_vertex_store(MeshVertex *__restrict__ proj, size_t i, const MeshVertex &v) {
+    *reinterpret_cast<int4 *>(proj + i) = make_int4(v.fx, v.fy, (int)v.a2, v.valid);
+}
+
+template <bool LEFT>
+__global__ __launch_bounds__(256) void render_mesh_project_kernel(const RenderMeshParams p) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.V) return;
+    mesh_vertex_store(p.proj, (size_t)i,
+                      mesh_project<LEFT>(p.M, p.s, p.verts[3 * i], p.verts[3 * i + 1], p.verts[3 * i + 2]));
 }
 
 // What a triangle's sweep and its resolve need: the corners, the doubled area's sign, 1 / a2 per

@@ -829,7 +829,8 @@ int arvx_mc_mesh_decimate_download(arvx_ctx *ctx, float *verts, uint32_t *faces,
  * views at the call and touches no other product -- the unwelded, welded, smoothed and decimated
  * meshes and a render stay as they were; like arvx_mc_mesh_welded it runs arvx_mc_cells itself.
  * Out of scope: smoothing or decimating this mesh (arvx_render_mesh draws it); normals; slabs and
- * multi-GPU; colour interpolation along the edge. */
+ * multi-GPU; colour interpolation along the edge (arvx_mesh_color samples the photographs at the
+ * vertex itself instead). */
 int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_t *vertices,
                          int64_t *triangles);
 int arvx_mc_mesh_refined_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb,
@@ -972,6 +973,75 @@ int arvx_render_mesh_stats(arvx_ctx *ctx, int64_t out[4]);
  * (0: everything large is swept in place; -1: the default sizing).  The room changes the time, never
  * the images. */
 int arvx_selftest_render_mesh_list(arvx_ctx *ctx, int64_t cap);
+
+/* ---- mesh colours from the images (extension beyond the reference) -----------------------------
+ * Colours the vertices of a held mesh from the photographs: per view the depth buffer of the mesh's
+ * own triangles, per vertex a vote over the views that really see it, sampled bilinearly.  Definition,
+ * bit for bit and without a thread order in it.  Inputs: a whole-grid context; its V views (M_v, W, H)
+ * and its images (arvx_set_images, BGR u8, I_v[r, c] per channel); a source mesh among ARVX_MESH_WELDED,
+ * _SMOOTHED, _DECIMATED, _REFINED with its Vn positions p, vertex colours col and T faces -- exactly
+ * the arrays arvx_render_mesh would draw --; mode ARVX_COLOR_CLOSEST or ARVX_COLOR_AVERAGE; tol >= 0,
+ * finite or +inf, in the units of a2.
+ *  1. Projection.  For vertex i and view v, step 1 of the triangle render with M_v: a2, VALID, fx, fy
+ *     (the same code, the same bits).
+ *  2. Depth buffer.  D_v is the depth image arvx_render_mesh_view(source, v, NULL) defines: steps 2-4
+ *     of the triangle render over all T faces, +inf where no triangle covers the pixel.
+ *  3. Candidate.  Vertex i is IN IMAGE in v iff it is VALID, 0 <= fx <= 16 (W - 1) and
+ *     0 <= fy <= 16 (H - 1).  Its nearest pixel is cn = (fx + 8) >> 4, rn = (fy + 8) >> 4.  It is
+ *     VISIBLE in v iff it is in image and a2 <= D_v[rn, cn] + tol (one fp32 addition) and -- with
+ *     ARVX_MESH_COLOR_FOREGROUND only -- pixel (cn, rn) is foreground in the view's background bit
+ *     plane (the one arvx_selftest_view_tables returns).  A vertex on the hull's rim is, in the view
+ *     whose silhouette it lies on, a grazing sample next to the photograph's background: the flag
+ *     drops that view.
+ *  4. Sample, in integers.  c0 = fx >> 4, r0 = fy >> 4, wx = fx & 15, wy = fy & 15,
+ *     c1 = min(c0 + 1, W - 1), r1 = min(r0 + 1, H - 1) (the clamp only ever meets a weight of 0).  Per
+ *     channel S = (16 - wx)(16 - wy) I[r0, c0] + wx (16 - wy) I[r0, c1] + (16 - wx) wy I[r1, c0]
+ *     + wx wy I[r1, c1]: an integer in [0, 255 * 256]; the sample is S / 256.
+ *  5. Vote over the visible views, n of them.  CLOSEST: the visible view with the least a2, compared
+ *     as fp32 with strict < in ascending view order (the first view wins ties: arvx_color's rule);
+ *     rgb_c = (float)S_c / 256.0f, exact.  AVERAGE: Sum_c the integer sum of S_c over the visible views
+ *     (64 bits: no order matters); rgb_c = (float)((double)Sum_c / (double)(256 n)).  n == 0:
+ *     rgb = col[i], the source's own vertex colour.
+ *  6. Product: vertex_rgb, 3 Vn floats r, g, b; views, Vn int32, the value n; *coloured, the number of
+ *     vertices with n > 0.  An empty mesh gives 0 and empty arrays.
+ * Consequence: arvx_mesh_color_depth_download(v) equals, bit for bit, the depth arvx_render_download
+ * returns after arvx_render_mesh_view(source, v, NULL).
+ * arvx_mesh_color takes ONE host synchronisation, for *coloured; nothing falls back to the host.
+ * arvx_mesh_color_count returns Vn and the count again (host bookkeeping; either pointer may be
+ * null); arvx_mesh_color_download copies vertex_rgb and views (either may be null);
+ * arvx_mesh_color_depth_download copies D_v, H x W floats.
+ * Drawing: in arvx_render_mesh, _view and _agreement, source | ARVX_MESH_IMAGE_COLORS draws the same
+ * mesh with the product's vertex_rgb in place of col; nothing else of that definition changes.
+ * Refusals.  ARVX_ERR_STATE: a slab or a striped context; the source mesh does not exist; no views, or
+ * no images; ARVX_MESH_COLOR_FOREGROUND when the views were set with masks == NULL; the count or
+ * either download before a product; ARVX_MESH_IMAGE_COLORS in a render when the product does not exist or was computed
+ * for another source.  ARVX_ERR_INVALID: an unknown source, an unknown mode, unknown flag bits, a NaN
+ * or negative tolerance, a null `coloured`, a null `depth`, a view outside [0, V).  A refused call
+ * leaves the previous product as it was.
+ * Lifetime.  One product per context, tagged with its source: a snapshot of the mesh, the views and the
+ * images at the call.  Later arvx_set_views, arvx_set_images, colour calls, carves and renders keep it.
+ * It ends at the next successful arvx_mesh_color, and at any call that replaces or drops the
+ * positions, faces or colours of its source: arvx_mc_mesh_welded for WELDED, SMOOTHED and DECIMATED,
+ * arvx_mc_mesh_smooth for SMOOTHED, arvx_mc_mesh_decimate for DECIMATED, arvx_mc_mesh_refined for
+ * REFINED.  It never ends the context's current render: its buffers are its own.
+ * Device memory.  Kept with the product: 16 Vn bytes of colours and counts and the depth keys,
+ * V * W * H * 8 bytes.  Workspace: the views are processed in batches, and the projected vertices of a
+ * batch (16 bytes per vertex and view) take at most max(64 MiB, 16 Vn) bytes -- a batch is
+ * floor(64 MiB / 16 Vn) views, one at least --; the list of a batch's (triangle, view) pairs whose pixel
+ * box exceeds 64 pixels (16 bytes each; what does not fit is swept by the wave that found it, and
+ * arvx_selftest_render_mesh_list bounds this list too); W * H * 4 bytes for a depth download.
+ * Out of scope: texture atlases and per-face textures, view weighting by surface normal, blending
+ * across seams, a caller's mesh (arvx_render_triangles), near-plane clipping, slabs and multi-GPU,
+ * writing the colours back into the meshes' own vertex_rgb or the voxel colour list. */
+#define ARVX_MESH_COLOR_FOREGROUND 1u /* flags of arvx_mesh_color */
+#define ARVX_MESH_IMAGE_COLORS 0x100  /* OR-ed into `source` of the arvx_render_mesh family */
+int arvx_mesh_color(arvx_ctx *ctx, int source, int mode, float tolerance, unsigned flags, int64_t *coloured);
+int arvx_mesh_color_count(arvx_ctx *ctx, int64_t *vertices, int64_t *coloured);
+int arvx_mesh_color_download(arvx_ctx *ctx, float *vertex_rgb, int32_t *views);
+int arvx_mesh_color_depth_download(arvx_ctx *ctx, int view, float *depth);
+/* Self-test hook: views per batch of arvx_mesh_color's depth pass from the next call on (0: the bound
+ * above).  The batches change the workspace and the launches, never the product. */
+int arvx_selftest_mesh_color_batch(arvx_ctx *ctx, int views_per_batch);
 
 /* Model::voxels as the reference would hold it after carve [+ colour]
  * [+ handleUnseen]: n*4 floats (RGBA), n = slab voxels. */

@@ -715,6 +715,8 @@ inline RenderedView rendered_view(arvx_ctx *ctx, int W, int H) {
 // holds: the one the last marchingCubesMeshWelded / Smoothed / Decimated / Refined of this model built
 // on the device, also after the model has moved on (renderWelded's note).  Only a missing welded mesh
 // is built here, as renderWelded builds it; any other source that the context does not hold throws.
+// source | ARVX_MESH_IMAGE_COLORS draws the mesh with the colours of the last colorMesh of that source
+// (below); without them the call throws.
 inline RenderedView renderMesh(Model *model, int source, const float M[12], int W, int H,
                                const uint8_t *background = nullptr, const float *light = nullptr) {
     arvx_ctx *ctx = model->device_for_reading();
@@ -733,6 +735,56 @@ inline RenderedView renderMesh(Model *model, int source, const float M[12], int 
     }
     detail::check(rc, "arvx_render_mesh");
     return detail::rendered_view(ctx, W, H);
+}
+
+// ---- mesh colours from the images (an extension beyond the reference) -----------------------------
+//
+// The vertices of the mesh `source` that the model's context holds, coloured from the views' images
+// (arvx_mesh_color, defined in include/arvx/arvx.h): per view the depth buffer of the mesh's own
+// triangles, per vertex a vote -- mode ARVX_COLOR_CLOSEST or ARVX_COLOR_AVERAGE -- over the views that
+// see it within `tolerance` (world units), sampled bilinearly; ARVX_MESH_COLOR_FOREGROUND in `flags`
+// drops the views whose mask has the vertex's pixel as background.  The views are bound with their
+// masks and their images.  renderMesh(model, source | ARVX_MESH_IMAGE_COLORS, ...) then draws the mesh
+// with these colours, until the source mesh is built again.
+struct MeshColors {
+    std::vector<float> rgb;      // r, g, b per vertex
+    std::vector<int32_t> views;  // the views that see each vertex
+    int64_t coloured = 0;        // vertices some view sees
+};
+
+inline MeshColors colorMesh(const Intrinsics &intr, Model *model, const std::vector<View> &views, int source,
+                            int mode, float tolerance, unsigned flags = 0) {
+    arvx_ctx *ctx = detail::bind_views(intr, *model, views, false);
+    model->set_colors_on_device(false);  // (arvx_set_views drops the context's colour list)
+    std::vector<const uint8_t *> imgs(views.size());
+    for (size_t i = 0; i < views.size(); ++i) {
+        const Image &im = views[i].image;
+        if (!im.data || im.channels != 3 || im.width != views[0].mask.width || im.height != views[0].mask.height ||
+            im.stride != views[0].image.stride)
+            throw Error(ARVX_ERR_INVALID, "colorMesh: colour images must be BGR u8 with the masks' size");
+        imgs[i] = im.data;
+    }
+    detail::check(arvx_set_images(ctx, imgs.data(), views[0].image.stride), "arvx_set_images");
+    MeshColors out;
+    int rc = arvx_mesh_color(ctx, source, mode, tolerance, flags, &out.coloured);
+    if (rc == ARVX_ERR_STATE && source == ARVX_MESH_WELDED) {  // no welded mesh yet: built as renderMesh builds it
+        bool on_device = false;
+        (void)model->inside_state(0.5f, on_device);
+        if (on_device) {
+            int apply_unseen = 0;
+            ctx = detail::mesh_context(model, apply_unseen);
+            int64_t nv = 0, nt = 0;
+            detail::check(arvx_mc_mesh_welded(ctx, apply_unseen, &nv, &nt), "arvx_mc_mesh_welded");
+            rc = arvx_mesh_color(ctx, source, mode, tolerance, flags, &out.coloured);
+        }
+    }
+    detail::check(rc, "arvx_mesh_color");
+    int64_t vertices = 0;
+    detail::check(arvx_mesh_color_count(ctx, &vertices, nullptr), "arvx_mesh_color_count");
+    out.rgb.resize(3 * (size_t)vertices);
+    out.views.resize((size_t)vertices);
+    detail::check(arvx_mesh_color_download(ctx, out.rgb.data(), out.views.data()), "arvx_mesh_color_download");
+    return out;
 }
 
 // Draws a mesh of the caller's on the model's context (arvx_render_triangles): its vertices in voxel

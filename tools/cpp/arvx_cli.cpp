@@ -237,7 +237,8 @@ int main(int argc, char *argv[]) {
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
         {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"},
-        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"renderMesh", "false"}};
+        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"renderMesh", "false"},
+        {"meshColor", ""}, {"meshForeground", "false"}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -271,7 +272,13 @@ int main(int argc, char *argv[]) {
                      "    DIR/renderNNNN.ppm, and its agreement with every mask),\n"
                      "  -renderMesh=true (with -render: the triangles of the mesh the run wrote -- refined,\n"
                      "    decimated, smoothed, else welded -- with a depth buffer and a light at the camera,\n"
-                     "    in place of the welded model's voxels)\n";
+                     "    in place of the welded model's voxels),\n"
+                     "  -meshColor=closest|average (with -render and -renderMesh=true: the mesh's vertices\n"
+                     "    coloured from the input images -- per view the depth buffer of the mesh itself, per\n"
+                     "    vertex a vote over the views that see it within -visibleTol voxel edges, sampled\n"
+                     "    bilinearly -- and the renders drawn with those colours),\n"
+                     "  -meshForeground=true (with -meshColor: a view votes only where its mask has the\n"
+                     "    vertex's pixel as foreground)\n";
         return 0;
     }
     const int choose = parser.i("c");
@@ -521,7 +528,26 @@ int main(int argc, char *argv[]) {
                                 : parser.i("decimate") > 0      ? ARVX_MESH_DECIMATED
                                 : parser.i("smooth") > 0        ? ARVX_MESH_SMOOTHED
                                                                 : ARVX_MESH_WELDED;
-        if (!parser.str("render").empty() && !render_views(parser.str("render"), in, model, mesh_source)) return 1;
+        // -meshColor=closest|average: that mesh's vertices coloured from the images first, and drawn so
+        int drawn = mesh_source;
+        const std::string meshColor = parser.str("meshColor");
+        if (!meshColor.empty()) {
+            if (meshColor != "closest" && meshColor != "average") {
+                std::cerr << "-meshColor takes closest or average" << std::endl;
+                return 1;
+            }
+            if (mesh_source < 0 || parser.str("render").empty()) {
+                std::cerr << "-meshColor needs -render=DIR and -renderMesh=true" << std::endl;
+                return 1;
+            }
+            const arvx::MeshColors col = arvx::colorMesh(
+                in.intr, &model, in.views, mesh_source, meshColor == "closest" ? ARVX_COLOR_CLOSEST : ARVX_COLOR_AVERAGE,
+                tol * model.getSize(), parser.b("meshForeground") ? ARVX_MESH_COLOR_FOREGROUND : 0u);
+            std::cout << "LOG - MESH COLOR: " << col.coloured << " of " << col.views.size()
+                      << " vertices coloured from the images" << std::endl;
+            drawn = mesh_source | ARVX_MESH_IMAGE_COLORS;
+        }
+        if (!parser.str("render").empty() && !render_views(parser.str("render"), in, model, drawn)) return 1;
     } catch (const arvx::Error &e) {
         return 3;  // (already logged)
     }
