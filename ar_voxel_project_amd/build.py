@@ -58,6 +58,7 @@ def build_host_tests() -> str:
     build_refine_host_test()
     build_render_mesh_host_test()
     build_mesh_color_host_test()
+    build_mesh_texture_host_test()
     return os.path.join(ROOT, "tests", "cpp", "test_host")
 
 
@@ -103,6 +104,14 @@ def build_mesh_color_host_test() -> str:
     """g++ -> tests/cpp/test_mesh_color_host: arvx::colorMesh (include/arvx/marching_cubes.hpp) on a
     scene from a file, built as build_weld_host_test builds its test."""
     return _build_host_test("test_mesh_color_host")
+
+
+def build_mesh_texture_host_test() -> str:
+    """g++ -> tests/cpp/test_mesh_texture_host: the atlas layout and the OBJ writer
+    (include/arvx/mesh_texture.hpp) on the host alone, and arvx::textureMesh
+    (include/arvx/marching_cubes.hpp) on a scene from a file, built as build_weld_host_test builds its
+    test."""
+    return _build_host_test("test_mesh_texture_host")
 
 
 def _build_host_test(name: str) -> str:

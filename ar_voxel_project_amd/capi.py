@@ -56,6 +56,8 @@ MESH_DECIMATED = 2
 MESH_REFINED = 3
 MESH_IMAGE_COLORS = 0x100  # OR-ed into `source` of the render_mesh family: draw mesh_color()'s colours
 MESH_COLOR_FOREGROUND = 1  # flags of mesh_color
+MESH_TEXTURED = 0x400  # OR-ed into `source` of the render_mesh family: draw mesh_texture()'s atlas
+MESH_TEXTURE_FOREGROUND = 1  # flags of mesh_texture
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
 # whole test module with the streaming carve forced on every fresh model (the library itself reads
 # no environment variable)
@@ -97,6 +99,7 @@ SYMBOLS = [
     "arvx_render_mesh_stats", "arvx_selftest_render_mesh_list",
     "arvx_mesh_color", "arvx_mesh_color_count", "arvx_mesh_color_download", "arvx_mesh_color_depth_download",
     "arvx_selftest_mesh_color_batch",
+    "arvx_mesh_texture", "arvx_mesh_texture_info", "arvx_mesh_texture_download",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
     "arvx_export_model", "arvx_get_stats", "arvx_last_carve_path", "arvx_last_fast_carve_path",
@@ -287,6 +290,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.arvx_mesh_color_download.argtypes = [p, C.c_void_p, C.c_void_p]
         lib.arvx_mesh_color_depth_download.argtypes = [p, C.c_int, C.c_void_p]
         lib.arvx_selftest_mesh_color_batch.argtypes = [p, C.c_int]
+    if hasattr(lib, "arvx_mesh_texture") or not ab_build:
+        lib.arvx_mesh_texture.argtypes = [p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint, C.POINTER(C.c_int64)]
+        lib.arvx_mesh_texture_info.argtypes = [p, C.POINTER(C.c_int64)]
+        lib.arvx_mesh_texture_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in SYMBOLS:
         if ab_build and not hasattr(lib, name):
             continue
@@ -1134,6 +1141,41 @@ class Context:
     def selftest_mesh_color_batch(self, views_per_batch: int) -> None:
         """Views per batch of mesh_color()'s depth pass from the next call on (0: the default bound)."""
         self._ck(self._lib.arvx_selftest_mesh_color_batch(self._h, int(views_per_batch)))
+
+    def mesh_texture(self, source: int, resolution: int, atlas_width: int, tolerance: float = 0.0, flags: int = 0,
+                     download: bool = True):
+        """arvx_mesh_texture: a texture atlas of the context's mesh `source` with one triangle of texels
+        per face (`resolution` texels along a leg, two faces per cell, `atlas_width` texels per atlas
+        row), each face sampled from the view that sees its three corners within `tolerance` and shows
+        it largest; MESH_TEXTURE_FOREGROUND as MESH_COLOR_FOREGROUND.
+        -> (atlas (AH, AW, 3) uint8 BGR, face_view (T,) int32: the view or -1, face_uv (T, 3, 2)
+        float32, counts (T, textured, AW, AH)).  render_mesh(source | MESH_TEXTURED, ...) draws it.
+        download=False: the call only, -> counts."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.arvx_mesh_texture(self._h, int(source), int(resolution), int(atlas_width),
+                                             float(tolerance), int(flags), out))
+        counts = tuple(int(n) for n in out)
+        if not download:
+            return counts
+        return self.mesh_texture_download() + (counts,)
+
+    def mesh_texture_download(self):
+        """arvx_mesh_texture_download: (atlas, face_view, face_uv) of the product of the last
+        mesh_texture()."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.arvx_mesh_texture_info(self._h, out))
+        T, _, AW, AH = (int(n) for n in out)
+        atlas = np.empty((AH, AW, 3), np.uint8)
+        view = np.empty(T, np.int32)
+        uv = np.empty((T, 3, 2), np.float32)
+        self._ck(self._lib.arvx_mesh_texture_download(self._h, atlas.ctypes.data, view.ctypes.data, uv.ctypes.data))
+        return atlas, view, uv
+
+    def mesh_texture_info(self) -> Tuple[int, int, int, int]:
+        """arvx_mesh_texture_info: (T, textured, AW, AH) of the product."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.arvx_mesh_texture_info(self._h, out))
+        return tuple(int(n) for n in out)
 
     def mc_mesh_count(self, apply_unseen: bool = False) -> int:
         """arvx_mc_mesh without the download: the triangles stay on the device."""

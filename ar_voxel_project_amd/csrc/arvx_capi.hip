@@ -46,6 +46,7 @@
 #include "render_kernels.h"
 #include "render_mesh_kernels.h"
 #include "mesh_color_kernels.h"
+#include "mesh_texture_kernels.h"
 #include "exchange_kernels.h"
 #include <algorithm>
 
@@ -4014,13 +4015,18 @@ struct MeshSource {
     const float *verts, *rgb;
     const unsigned *faces;
     long long V, T;
+    bool textured = false;  // drawn with arvx_mesh_texture's atlas in place of rgb
 };
 
 // The context's mesh `source`, or the refusal: an unknown source, or a mesh that does not exist
 // (slab and striped contexts never build one).  With ARVX_MESH_IMAGE_COLORS (where the caller allows
-// it) the colours are arvx_mesh_color's of that source.
+// it) the colours are arvx_mesh_color's of that source, with ARVX_MESH_TEXTURED arvx_mesh_texture's
+// atlas of that source.
 static int mesh_source(const Ctx *ctx, int source, MeshSource &m, bool image_colours_allowed = true) {
-    const int base = image_colours_allowed ? source & ~ARVX_MESH_IMAGE_COLORS : source;
+    constexpr int both = ARVX_MESH_IMAGE_COLORS | ARVX_MESH_TEXTURED;
+    if (image_colours_allowed && source >= 0 && (source & both) == both)
+        return fail(ARVX_ERR_INVALID, "mesh source %#x: image colours and a texture exclude each other", source);
+    const int base = image_colours_allowed && source >= 0 ? source & ~both : source;
     switch (base) {
     case ARVX_MESH_WELDED:
     case ARVX_MESH_SMOOTHED:
@@ -4043,10 +4049,15 @@ static int mesh_source(const Ctx *ctx, int source, MeshSource &m, bool image_col
     default:
         return fail(ARVX_ERR_INVALID, "unknown mesh source %d", source);
     }
-    if (base != source) {
+    if (base != source && (source & ARVX_MESH_IMAGE_COLORS)) {
         if (!ctx->mesh_color_ready || ctx->mesh_color_source != base)
             return fail(ARVX_ERR_STATE, "no image colours of mesh source %d (call arvx_mesh_color)", base);
         m.rgb = ctx->pool_mcol_rgb.data();  // (as many as the source has vertices: the product ends with them)
+    }
+    if (base != source && (source & ARVX_MESH_TEXTURED)) {
+        if (!ctx->mesh_texture_ready || ctx->mesh_texture_source != base || ctx->mesh_texture_faces != m.T)
+            return fail(ARVX_ERR_STATE, "no texture of mesh source %d (call arvx_mesh_texture)", base);
+        m.textured = true;  // (a cell half per face of the source: the product ends with them)
     }
     return ARVX_OK;
 }
@@ -4107,8 +4118,15 @@ static int render_mesh_launch(Ctx *ctx, const MeshSource &m, const float *M, int
     } else {
         p.T = 0;  // (faces without vertices cannot be: every index is below V)
     }
-    ARVX_TRY(launch(ctx, arvx::render_mesh_resolve_kernel, blocks_for(npix), 256, p, npix, render_id(ctx),
-                    render_depth(ctx), render_bgr(ctx)));
+    if (m.textured) {
+        const arvx::MeshTextureColour tex{ctx->pool_mtex_atlas.data(),
+                                          arvx::texture_layout(m.T, ctx->mesh_texture_R, ctx->mesh_texture_AW)};
+        ARVX_TRY(launch(ctx, arvx::render_mesh_resolve_kernel<arvx::MeshTextureColour>, blocks_for(npix), 256, p,
+                        npix, render_id(ctx), render_depth(ctx), render_bgr(ctx), tex));
+    } else {
+        ARVX_TRY(launch(ctx, arvx::render_mesh_resolve_kernel<arvx::MeshVertexColour>, blocks_for(npix), 256, p,
+                        npix, render_id(ctx), render_depth(ctx), render_bgr(ctx), arvx::MeshVertexColour{}));
+    }
     ctx->render_ready = true;
     ctx->render_tris = true;
     return ARVX_OK;
@@ -4189,7 +4207,7 @@ int arvx_render_triangles(arvx_ctx *ctx, int64_t nv, const float *verts, const f
                                 ctx->stream));
     }
     if (nv > 0 || nt > 0) ARVX_SYNC(ctx);
-    const MeshSource m{ctx->pool_tri_verts.data(), ctx->pool_tri_rgb.data(), ctx->pool_tri_faces.data(), nv, nt};
+    const MeshSource m{ctx->pool_tri_verts.data(), ctx->pool_tri_rgb.data(), ctx->pool_tri_faces.data(), nv, nt, false};
     return render_mesh_launch(ctx, m, M, W, H, background, bg_stride, light);
 }
 
@@ -4219,6 +4237,62 @@ int arvx_selftest_render_mesh_list(arvx_ctx *ctx, int64_t cap) {
 // the projected vertices of one batch of views: never more than this, or one view's
 static constexpr size_t kMeshColorProjBytes = (size_t)64 << 20;
 
+// The depth pass of arvx_mesh_color and arvx_mesh_texture: the keys of mesh m in every view of the
+// context, V x H x W into `keys` (the caller's), by batches of views -- project, raster, large boxes.
+// Launches only.  Workspace: the batch's projected vertices and, behind its zeroed header, the list of
+// large pixel boxes (pool_mcol_proj, pool_mcol_large); after the caller's synchronisation the word
+// kMeshColorNeed holds what the fullest batch wanted to list.
+static int mesh_depth_pass(Ctx *ctx, const MeshSource &m, unsigned long long *keys) {
+    const int V = ctx->V, W = ctx->W, H = ctx->H;
+    const size_t npix = (size_t)W * H;
+    const bool faces = m.T > 0 && m.V > 0;
+    // views per batch: what the bound on the projected vertices holds (one view at least)
+    long long batch = std::max<long long>(1, (long long)(kMeshColorProjBytes / sizeof(arvx::MeshVertex)) / std::max(m.V, 1ll));
+    if (ctx->mesh_color_batch > 0) batch = ctx->mesh_color_batch;
+    batch = std::min<long long>({batch, V, 65535});
+    // large pixel boxes of a batch (large_list_cap): never more than its (triangle, view) pairs
+    const long long pairs = faces ? m.T * batch : 0;
+    const unsigned large_cap =
+        ctx->render_mesh_list_cap >= 0
+            ? (unsigned)std::min<long long>({ctx->render_mesh_list_cap, pairs, (long long)UINT32_MAX})
+            : large_list_cap(pairs, ctx->mesh_color_need, pairs);
+    ARVX_HIP(ctx->pool_mcol_large.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
+    static_assert(sizeof(arvx::MeshColorHeader) <= 64, "the header ends before the list");
+    arvx::MeshColorHeader *head = (arvx::MeshColorHeader *)ctx->pool_mcol_large.p;
+    ARVX_HIP(hipMemsetAsync(keys, 0xFF, (size_t)V * npix * sizeof(unsigned long long), ctx->stream));  // (kRenderEmpty)
+    ARVX_HIP(hipMemsetAsync(head, 0, 64, ctx->stream));
+    if (!faces) return ARVX_OK;
+    const int ncu = compute_units(ctx);
+    ARVX_HIP(ctx->pool_mcol_proj.reserve((size_t)batch * (size_t)m.V * sizeof(arvx::MeshVertex)));
+    arvx::MeshColorParams p{};
+    p.mesh.verts = m.verts, p.mesh.faces = m.faces;
+    p.mesh.V = m.V, p.mesh.T = m.T;
+    p.mesh.s = ctx->s;
+    p.mesh.W = W, p.mesh.H = H;
+    p.mesh.proj = (arvx::MeshVertex *)ctx->pool_mcol_proj.p;
+    p.mesh.large = (arvx::SplatRect *)((uint8_t *)ctx->pool_mcol_large.p + 64);
+    p.mesh.large_cap = large_cap;
+    p.M = (const arvx::SelftestMatrix *)ctx->M();
+    p.head = head;
+    // (the grid strides over the faces: as many workgroups in all as the render's raster has)
+    const unsigned tblocks = (unsigned)std::max<long long>(
+        1, std::min<long long>((m.T + 255) / 256, (8ll * ncu + batch - 1) / batch));
+    for (int v0 = 0; v0 < V; v0 += (int)batch) {
+        p.view0 = v0;
+        p.nviews = (int)std::min<long long>(batch, V - v0);
+        p.mesh.keys = keys + (size_t)v0 * npix;
+        if (v0 > 0) ARVX_HIP(hipMemsetAsync(&head->n_large, 0, sizeof head->n_large, ctx->stream));
+        ARVX_TRY(by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::mesh_color_project_kernel<decltype(left)::value>,
+                          dim3(blocks_for(m.V), p.nviews), 256, p);
+        }));
+        ARVX_TRY(launch(ctx, arvx::mesh_color_raster_kernel, dim3(tblocks, p.nviews), 256, p));
+        ARVX_TRY(launch(ctx, arvx::mesh_color_large_kernel, (unsigned)(4 * ncu), 256, p,
+                        ctx->word_dev(Ctx::kMeshColorNeed)));
+    }
+    return ARVX_OK;
+}
+
 int arvx_mesh_color(arvx_ctx *ctx, int source, int mode, float tolerance, unsigned flags, int64_t *coloured) {
     ARVX_CHECK_CTX(ctx);
     if (!whole_grid(ctx)) return fail(ARVX_ERR_STATE, "arvx_mesh_color needs a whole-grid context");
@@ -4238,55 +4312,12 @@ int arvx_mesh_color(arvx_ctx *ctx, int source, int mode, float tolerance, unsign
     const int V = ctx->V, W = ctx->W, H = ctx->H;
     const size_t npix = (size_t)W * H;
     const bool faces = m.T > 0 && m.V > 0;
-    // views per batch: what the bound on the projected vertices holds (one view at least)
-    long long batch = std::max<long long>(1, (long long)(kMeshColorProjBytes / sizeof(arvx::MeshVertex)) / std::max(m.V, 1ll));
-    if (ctx->mesh_color_batch > 0) batch = ctx->mesh_color_batch;
-    batch = std::min<long long>({batch, V, 65535});
-    // large pixel boxes of a batch (large_list_cap): never more than its (triangle, view) pairs
-    const long long pairs = faces ? m.T * batch : 0;
-    const unsigned large_cap =
-        ctx->render_mesh_list_cap >= 0
-            ? (unsigned)std::min<long long>({ctx->render_mesh_list_cap, pairs, (long long)UINT32_MAX})
-            : large_list_cap(pairs, ctx->mesh_color_need, pairs);
     ARVX_HIP(ctx->pool_mcol_keys.reserve((size_t)V * npix * sizeof(unsigned long long)));
     ARVX_HIP(ctx->pool_mcol_rgb.reserve((size_t)m.V * Ctx::kVertexBytes));
     ARVX_HIP(ctx->pool_mcol_views.reserve((size_t)m.V * sizeof(int)));
-    ARVX_HIP(ctx->pool_mcol_large.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
-    static_assert(sizeof(arvx::MeshColorHeader) <= 64, "the header ends before the list");
-    arvx::MeshColorHeader *head = (arvx::MeshColorHeader *)ctx->pool_mcol_large.p;
     unsigned long long *keys = (unsigned long long *)ctx->pool_mcol_keys.p;
-    ARVX_HIP(hipMemsetAsync(keys, 0xFF, (size_t)V * npix * sizeof(unsigned long long), ctx->stream));  // (kRenderEmpty)
-    ARVX_HIP(hipMemsetAsync(head, 0, 64, ctx->stream));
-    const int ncu = compute_units(ctx);
-    if (faces) {
-        ARVX_HIP(ctx->pool_mcol_proj.reserve((size_t)batch * (size_t)m.V * sizeof(arvx::MeshVertex)));
-        arvx::MeshColorParams p{};
-        p.mesh.verts = m.verts, p.mesh.faces = m.faces;
-        p.mesh.V = m.V, p.mesh.T = m.T;
-        p.mesh.s = ctx->s;
-        p.mesh.W = W, p.mesh.H = H;
-        p.mesh.proj = (arvx::MeshVertex *)ctx->pool_mcol_proj.p;
-        p.mesh.large = (arvx::SplatRect *)((uint8_t *)ctx->pool_mcol_large.p + 64);
-        p.mesh.large_cap = large_cap;
-        p.M = (const arvx::SelftestMatrix *)ctx->M();
-        p.head = head;
-        // (the grid strides over the faces: as many workgroups in all as the render's raster has)
-        const unsigned tblocks = (unsigned)std::max<long long>(
-            1, std::min<long long>((m.T + 255) / 256, (8ll * ncu + batch - 1) / batch));
-        for (int v0 = 0; v0 < V; v0 += (int)batch) {
-            p.view0 = v0;
-            p.nviews = (int)std::min<long long>(batch, V - v0);
-            p.mesh.keys = keys + (size_t)v0 * npix;
-            if (v0 > 0) ARVX_HIP(hipMemsetAsync(&head->n_large, 0, sizeof head->n_large, ctx->stream));
-            ARVX_TRY(by_assoc(ctx, [&](auto left) {
-                return launch(ctx, arvx::mesh_color_project_kernel<decltype(left)::value>,
-                              dim3(blocks_for(m.V), p.nviews), 256, p);
-            }));
-            ARVX_TRY(launch(ctx, arvx::mesh_color_raster_kernel, dim3(tblocks, p.nviews), 256, p));
-            ARVX_TRY(launch(ctx, arvx::mesh_color_large_kernel, (unsigned)(4 * ncu), 256, p,
-                            ctx->word_dev(Ctx::kMeshColorNeed)));
-        }
-    }
+    ARVX_TRY(mesh_depth_pass(ctx, m, keys));
+    arvx::MeshColorHeader *head = (arvx::MeshColorHeader *)ctx->pool_mcol_large.p;
     unsigned long long n_coloured = 0;
     if (m.V > 0) {
         arvx::MeshVoteParams vp{};
@@ -4357,6 +4388,130 @@ int arvx_selftest_mesh_color_batch(arvx_ctx *ctx, int views_per_batch) {
     ARVX_CHECK_CTX(ctx);
     if (views_per_batch < 0) return fail(ARVX_ERR_INVALID, "views_per_batch %d (0: the default bound)", views_per_batch);
     ctx->mesh_color_batch = views_per_batch;
+    return ARVX_OK;
+}
+
+// ---- mesh textures from the images (mesh_texture_kernels.h) ----------------------------------
+
+int arvx_mesh_texture(arvx_ctx *ctx, int source, int resolution, int atlas_width, float tolerance, unsigned flags,
+                      int64_t out[4]) {
+    ARVX_CHECK_CTX(ctx);
+    if (!whole_grid(ctx)) return fail(ARVX_ERR_STATE, "arvx_mesh_texture needs a whole-grid context");
+    MeshSource m;
+    if (int rc = mesh_source(ctx, source, m, false)) return rc;
+    if (resolution < 1 || resolution > ARVX_MESH_TEXTURE_MAX_RESOLUTION)
+        return fail(ARVX_ERR_INVALID, "resolution %d outside [1,%d]", resolution, ARVX_MESH_TEXTURE_MAX_RESOLUTION);
+    if (atlas_width < resolution + 3 || atlas_width > ARVX_MESH_TEXTURE_MAX_WIDTH)
+        return fail(ARVX_ERR_INVALID, "atlas width %d outside [%d,%d]", atlas_width, resolution + 3,
+                    ARVX_MESH_TEXTURE_MAX_WIDTH);
+    if (flags & ~ARVX_MESH_TEXTURE_FOREGROUND) return fail(ARVX_ERR_INVALID, "unknown flag bits %#x", flags);
+    if (std::isnan(tolerance) || tolerance < 0.f)
+        return fail(ARVX_ERR_INVALID, "tolerance %g: must be >= 0 (finite or +inf)", (double)tolerance);
+    if (!out) return fail(ARVX_ERR_INVALID, "null out");
+    if (m.T > (long long)UINT32_MAX) return fail(ARVX_ERR_STATE, "the mesh is too long");
+    {  // (the height before anything is laid out: rows of cells times ch)
+        const long long per_row = atlas_width / (resolution + 3), cells = (m.T + 1) / 2;
+        const long long AH = (cells + per_row - 1) / per_row * (resolution + 2);
+        if (AH > ARVX_MESH_TEXTURE_MAX_HEIGHT)
+            return fail(ARVX_ERR_INVALID, "an atlas %d wide would be %lld high (at most %d): widen it", atlas_width, AH,
+                        ARVX_MESH_TEXTURE_MAX_HEIGHT);
+    }
+    if (!ctx->cameras_ready) return fail(ARVX_ERR_STATE, "arvx_set_views has not been called");
+    if (!ctx->images_ready) return fail(ARVX_ERR_STATE, "arvx_set_images has not been called");
+    if ((flags & ARVX_MESH_TEXTURE_FOREGROUND) && !ctx->views_ready)
+        return fail(ARVX_ERR_STATE, "ARVX_MESH_TEXTURE_FOREGROUND: arvx_set_views was given no masks");
+    ctx->mesh_texture_ready = false;
+    const int V = ctx->V, W = ctx->W, H = ctx->H;
+    const size_t npix = (size_t)W * H;
+    const arvx::TextureLayout lay = arvx::texture_layout(m.T, resolution, atlas_width);
+    const size_t ntex = (size_t)lay.AW * (size_t)lay.AH;
+    const int words = (V + 31) / 32;
+    unsigned long long n_textured = 0;
+    if (m.T > 0 && m.V > 0) {
+        ARVX_HIP(ctx->pool_mtex_keys.reserve((size_t)V * npix * sizeof(unsigned long long)));
+        ARVX_HIP(ctx->pool_mtex_bits.reserve((size_t)words * (size_t)m.V * sizeof(uint32_t)));
+        ARVX_HIP(ctx->pool_mtex_count.reserve(sizeof(unsigned long long)));
+        ARVX_HIP(ctx->pool_mtex_view.reserve((size_t)m.T * sizeof(int)));
+        ARVX_HIP(ctx->pool_mtex_atlas.reserve(ntex * 3));
+        unsigned long long *keys = (unsigned long long *)ctx->pool_mtex_keys.p;
+        unsigned long long *count = (unsigned long long *)ctx->pool_mtex_count.p;
+        ARVX_TRY(mesh_depth_pass(ctx, m, keys));
+        ARVX_HIP(hipMemsetAsync(count, 0, sizeof *count, ctx->stream));
+        arvx::MeshVisibleParams vp{};
+        vp.verts = m.verts;
+        vp.Vn = m.V;
+        vp.s = ctx->s;
+        vp.V = V, vp.W = W, vp.H = H, vp.words = words;
+        vp.M = (const arvx::SelftestMatrix *)ctx->M();
+        vp.keys = keys;
+        vp.bg = (flags & ARVX_MESH_TEXTURE_FOREGROUND) ? ctx->bg() : nullptr;
+        vp.bgWords = ctx->bgWords;
+        vp.tol = tolerance;
+        vp.bits = (uint32_t *)ctx->pool_mtex_bits.p;
+        arvx::MeshSelectParams sp{};
+        sp.verts = m.verts, sp.faces = m.faces;
+        sp.Vn = m.V, sp.T = m.T;
+        sp.s = ctx->s;
+        sp.V = V, sp.words = words;
+        sp.M = vp.M;
+        sp.bits = vp.bits;
+        sp.face_view = ctx->pool_mtex_view.data();
+        sp.textured = count;
+        arvx::MeshFillParams fp{};
+        fp.verts = m.verts, fp.col = m.rgb, fp.faces = m.faces;
+        fp.Vn = m.V;
+        fp.s = ctx->s;
+        fp.W = W, fp.H = H;
+        fp.M = vp.M;
+        fp.images = ctx->images();
+        fp.face_view = sp.face_view;
+        fp.lay = lay;
+        fp.atlas = ctx->pool_mtex_atlas.data();
+        ARVX_TRY(by_assoc(ctx, [&](auto left) {
+            constexpr bool L = decltype(left)::value;
+            ARVX_TRY(launch(ctx, arvx::mesh_texture_visible_kernel<L>, blocks_for(m.V), 256, vp));
+            ARVX_TRY(launch(ctx, arvx::mesh_texture_select_kernel<L>, blocks_for(m.T), 256, sp));
+            return launch(ctx, arvx::mesh_texture_fill_kernel<L>, blocks_for(ntex, 1024), 256, fp);  // (4 texels a lane)
+        }));
+        ARVX_HIP(hipMemcpyAsync(&n_textured, count, sizeof n_textured, hipMemcpyDeviceToHost, ctx->stream));
+        ARVX_SYNC(ctx);
+        ctx->mesh_color_need = std::max(ctx->word(Ctx::kMeshColorNeed), 0ll);
+    }
+    ctx->mesh_texture_source = source;
+    ctx->mesh_texture_R = resolution, ctx->mesh_texture_AW = lay.AW;
+    ctx->mesh_texture_AH = m.T > 0 && m.V > 0 ? lay.AH : 0;
+    ctx->mesh_texture_faces = m.T > 0 && m.V > 0 ? m.T : 0;
+    ctx->mesh_texture_textured = (int64_t)n_textured;
+    ctx->mesh_texture_ready = true;
+    return arvx_mesh_texture_info(ctx, out);
+}
+
+int arvx_mesh_texture_info(arvx_ctx *ctx, int64_t out[4]) {
+    ARVX_CHECK_CTX(ctx);
+    if (!out) return fail(ARVX_ERR_INVALID, "null out");
+    if (!ctx->mesh_texture_ready) return fail(ARVX_ERR_STATE, "no texture (call arvx_mesh_texture)");
+    out[0] = ctx->mesh_texture_faces, out[1] = ctx->mesh_texture_textured;
+    out[2] = ctx->mesh_texture_AW, out[3] = ctx->mesh_texture_AH;
+    return ARVX_OK;
+}
+
+int arvx_mesh_texture_download(arvx_ctx *ctx, uint8_t *atlas_bgr, int32_t *face_view, float *face_uv) {
+    ARVX_CHECK_CTX(ctx);
+    if (!ctx->mesh_texture_ready) return fail(ARVX_ERR_STATE, "no texture (call arvx_mesh_texture)");
+    const size_t T = (size_t)ctx->mesh_texture_faces;
+    const arvx::TextureLayout lay = arvx::texture_layout((long long)T, ctx->mesh_texture_R, ctx->mesh_texture_AW);
+    ARVX_TRY(download(ctx, atlas_bgr, ctx->pool_mtex_atlas.data(), (size_t)lay.AW * (size_t)lay.AH, 3));
+    ARVX_TRY(download(ctx, face_view, ctx->pool_mtex_view.data(), T, sizeof(int32_t)));
+    for (size_t f = 0; face_uv && f < T; ++f) {  // (the layout is the same arithmetic on the host)
+        static const int ci[3] = {0, 1, 0}, cj[3] = {0, 0, 1};
+        for (int k = 0; k < 3; ++k) {
+            int x, y;
+            arvx::texture_texel(lay, (long long)f, ci[k] * lay.R, cj[k] * lay.R, x, y);
+            face_uv[6 * f + 2 * k] = ((float)x + 0.5f) / (float)lay.AW;
+            face_uv[6 * f + 2 * k + 1] = ((float)y + 0.5f) / (float)lay.AH;
+        }
+    }
+    ARVX_SYNC(ctx);
     return ARVX_OK;
 }
 

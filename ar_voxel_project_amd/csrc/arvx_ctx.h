@@ -507,8 +507,21 @@ struct Ctx {
     int mesh_color_source = 0, mesh_color_V = 0, mesh_color_W = 0, mesh_color_H = 0;
     int64_t mesh_color_verts = 0, mesh_color_coloured = 0;
     long long mesh_color_need = 0, mesh_color_batch = 0;  // (batch: arvx_selftest_mesh_color_batch; 0: the bound)
+    // arvx_mesh_texture (mesh_texture_kernels.h): the product -- the atlas and the view of every face,
+    // tagged with its source, its resolution and its layout (read only while mesh_texture_ready is set)
+    // -- and the call's workspace: depth keys of its own (arvx_mesh_color's product keeps its keys), the
+    // vertices' visibility words, the count of textured faces.  The projected vertices and the list of
+    // large pixel boxes are the mesh colours' workspace above.  It ends where the mesh colours' product
+    // of the same source would.
+    DevArray<uint8_t> pool_mtex_atlas;
+    DevArray<int> pool_mtex_view;
+    DevPool pool_mtex_keys{DevPool::Exact}, pool_mtex_bits, pool_mtex_count{DevPool::Exact};
+    bool mesh_texture_ready = false;
+    int mesh_texture_source = 0, mesh_texture_R = 0, mesh_texture_AW = 0, mesh_texture_AH = 0;
+    int64_t mesh_texture_faces = 0, mesh_texture_textured = 0;
     void mesh_color_ended(int source) {
         if (mesh_color_source == source) mesh_color_ready = false;
+        if (mesh_texture_source == source) mesh_texture_ready = false;
     }
 
     // (the device buffers are freed by their DevPool members, after this)

@@ -12,7 +12,8 @@
 //                               to a list (when it is full, swept by the lane's wave instead)
 //   render_mesh_large_kernel    one wave per listed triangle, a pixel of its box per lane
 //   render_mesh_resolve_kernel  one lane per pixel: the winner's edge functions once more, its
-//                               depth, the interpolated colour, the face's shade
+//                               depth, the interpolated colour (or, instantiated with
+//                               MeshTextureColour, the face's texel), the face's shade
 // Coverage is decided by three 64-bit integer edge functions of 28.4 fixed-point corners: exact, so
 // two faces that share an edge agree about its pixels.  A key is bits(depth) << 32 | t with depth a
 // positive fp32: its 64-bit unsigned minimum (key_min, a no-return atomicMin) is the nearest
@@ -277,11 +278,26 @@ __global__ __launch_bounds__(256) void render_mesh_large_kernel(const RenderMesh
 // l of the definition: the length of a vector, every operation rounded on its own
 __device__ __forceinline__ float mesh_length(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 
+// Step 5's v of the winner t before the light, per channel r, g, b: the vertex colours interpolated.
+// (MeshTextureColour, mesh_texture_kernels.h, is the other Colour of the resolve kernel.)
+struct MeshVertexColour {
+    __device__ __forceinline__ void operator()(const RenderMeshParams &p, uint32_t, size_t i0, size_t i1, size_t i2,
+                                               double t0, double t1, double t2, double S, float (&v)[3]) const {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const double n = (t0 * (double)p.rgb[3 * i0 + ch] + t1 * (double)p.rgb[3 * i1 + ch]) +
+                             t2 * (double)p.rgb[3 * i2 + ch];
+            v[ch] = (float)(n / S);
+        }
+    }
+};
+
 // One lane per pixel.  bgr holds the background already (the caller's image or zeros): only the
 // covered pixels are written.
+template <class Colour>
 __global__ __launch_bounds__(256) void render_mesh_resolve_kernel(const RenderMeshParams p, size_t npix,
                                                                   int *__restrict__ id, float *__restrict__ depth,
-                                                                  uint8_t *__restrict__ bgr) {
+                                                                  uint8_t *__restrict__ bgr, const Colour colour) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= npix) return;
     const unsigned long long key = p.keys[i];
@@ -311,13 +327,10 @@ __global__ __launch_bounds__(256) void render_mesh_resolve_kernel(const RenderMe
         shade = 0.25f + 0.75f * f;
     }
     float v[3];
+    colour(p, t, i0, i1, i2, t0, t1, t2, S, v);
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const double n = (t0 * (double)p.rgb[3 * i0 + ch] + t1 * (double)p.rgb[3 * i1 + ch]) +
-                         t2 * (double)p.rgb[3 * i2 + ch];
-        v[ch] = (float)(n / S);
+    for (int ch = 0; ch < 3; ++ch)
         if (p.lit) v[ch] = shade * v[ch];
-    }
     bgr[3 * i] = render_channel(v[2]);
     bgr[3 * i + 1] = render_channel(v[1]);
     bgr[3 * i + 2] = render_channel(v[0]);

@@ -249,3 +249,31 @@ def pit_box_scene(N, V: int, W=IMAGE_W, H=IMAGE_H, extent: float = EXTENT,
     sc.box = (lo, hi)
     sc.pit = (plo, phi)
     return sc
+
+
+# ---- a textured sphere: photographs that agree with each other (arvx_mesh_color, arvx_mesh_texture) --
+
+def textured_sphere_scene(N: int, V: int, W=IMAGE_W, H=IMAGE_H, period: float = 0.25, extent: float = EXTENT,
+                          radius_factor: float = 0.35) -> Scene:
+    """sphere_scene's cameras and masks with images (BGR) rendered analytically: each pixel's ray
+    against the sphere, the pixel texture_rgb(hit, period * extent) at the nearer intersection, black
+    where the ray misses.  Every view photographs the same albedo, so colours taken from different views
+    of one surface point agree up to the sampling."""
+    sc = sphere_scene(N, V, W, H, extent, radius_factor)
+    Rt64 = np.asarray(sc.Rt, np.float64).reshape(-1, 3, 4)
+    centre = np.array([extent / 2, extent / 2, -extent / 2])
+    radius = radius_factor * extent
+    images = np.zeros((V, H, W, 3), np.uint8)
+    for i in range(V):
+        C, d = _rays(sc.K.astype(np.float64), Rt64[i], W, H)
+        oc = centre - C
+        b = d @ oc
+        dd = np.einsum("hwc,hwc->hw", d, d)
+        disc = b * b - dd * (oc @ oc - radius * radius)
+        hit = (disc >= 0) & (b > 0)  # (sphere_masks' test)
+        t = (b - np.sqrt(np.maximum(disc, 0.0))) / dd
+        p = C + t[..., None] * d
+        rgb = np.clip(np.rint(texture_rgb(p, period * extent)), 0, 255)
+        images[i] = np.where(hit[..., None], rgb[..., ::-1], 0).astype(np.uint8)
+    sc.images = images
+    return sc

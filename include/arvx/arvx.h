@@ -955,8 +955,8 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]);
  * Device memory beside the render's, sized at first use and kept: 16 bytes per vertex of projected
  * positions and the list of triangles whose pixel box exceeds 64 pixels (16 bytes each), swept by a
  * wave each; what does not fit the list is swept by the wave that found it.
- * Out of scope: near-plane and guard-band clipping, anti-aliasing, per-vertex normals, textures,
- * slabs and multi-GPU. */
+ * Out of scope: near-plane and guard-band clipping, anti-aliasing, per-vertex normals, slabs and
+ * multi-GPU.  (Textures: the mesh textures' block below, ARVX_MESH_TEXTURED.) */
 #define ARVX_MESH_WELDED 0
 #define ARVX_MESH_SMOOTHED 1
 #define ARVX_MESH_DECIMATED 2
@@ -1030,7 +1030,7 @@ int arvx_selftest_render_mesh_list(arvx_ctx *ctx, int64_t cap);
  * floor(64 MiB / 16 Vn) views, one at least --; the list of a batch's (triangle, view) pairs whose pixel
  * box exceeds 64 pixels (16 bytes each; what does not fit is swept by the wave that found it, and
  * arvx_selftest_render_mesh_list bounds this list too); W * H * 4 bytes for a depth download.
- * Out of scope: texture atlases and per-face textures, view weighting by surface normal, blending
+ * Out of scope (per-face textures are the next block's): view weighting by surface normal, blending
  * across seams, a caller's mesh (arvx_render_triangles), near-plane clipping, slabs and multi-GPU,
  * writing the colours back into the meshes' own vertex_rgb or the voxel colour list. */
 #define ARVX_MESH_COLOR_FOREGROUND 1u /* flags of arvx_mesh_color */
@@ -1042,6 +1042,81 @@ int arvx_mesh_color_depth_download(arvx_ctx *ctx, int view, float *depth);
 /* Self-test hook: views per batch of arvx_mesh_color's depth pass from the next call on (0: the bound
  * above).  The batches change the workspace and the launches, never the product. */
 int arvx_selftest_mesh_color_batch(arvx_ctx *ctx, int views_per_batch);
+
+/* ---- mesh textures from the images (extension beyond the reference) ----------------------------
+ * Builds, for a held mesh, a texture atlas with one small triangle of texels per face, each face
+ * sampled from the one view that sees its three corners and shows it largest.  Definition, bit for bit
+ * and without a thread order in it.  Inputs: a whole-grid context with its V views (M_v, W, H) and
+ * images; a source among ARVX_MESH_WELDED, _SMOOTHED, _DECIMATED, _REFINED with its Vn positions p,
+ * vertex colours col and T faces -- exactly the arrays arvx_render_mesh would draw --; a resolution R,
+ * 1 <= R <= 253; an atlas width AW in texels; tol as arvx_mesh_color takes it; flags:
+ * ARVX_MESH_TEXTURE_FOREGROUND, with the meaning of ARVX_MESH_COLOR_FOREGROUND.
+ *  1. Layout, in integers, the same on host and device.  A cell is cw = R + 3 texels wide and
+ *     ch = R + 2 high and holds two faces: face f lives in cell f >> 1, half f & 1.  The atlas has
+ *     per_row = AW / cw >= 1 cells per row, rows = ceil(ceil(T / 2) / per_row) rows of cells and the
+ *     height AH = rows * ch; cell k has its top-left texel at ((k % per_row) * cw, (k / per_row) * ch).
+ *     A face's local texels (i, j) have i, j >= 0 and i + j <= R + 1: (R + 2)(R + 3) / 2 of them.  Half
+ *     0 puts (i, j) at cell texel (i, j), half 1 at (cw - 1 - i, ch - 1 - j): the two halves tile the
+ *     cell exactly.  Corners 0, 1, 2 of the face sit on the centres of local texels (0, 0), (R, 0),
+ *     (0, R); the texels with i + j = R + 1 are a gutter along the hypotenuse.  The corners lie on
+ *     texel centres, so the two legs need none, for nearest and for bilinear look-ups without mip
+ *     levels.  Zero are: the padding columns of every atlas row where cw does not divide AW, the unused
+ *     cells of the last row, and the second half of the last cell when T is odd.  The corner at atlas
+ *     texel (x, y) has the UV ((float)x + 0.5f) / (float)AW, ((float)y + 0.5f) / (float)AH: row 0 is
+ *     the top row, as in the images.
+ *  2. Best view of face f.  View v is a candidate iff all three corners are VISIBLE in v -- step 3 of
+ *     arvx_mesh_color with tol and with the foreground flag, D_v that definition's step 2 -- and the
+ *     doubled area A_v of step 2 of the triangle render (int64) is not zero.  The best view is the
+ *     candidate with the greatest |A_v|, among equals the least v; there is no back-face test, as in the
+ *     render.  face_view[f] is that view, or -1 without a candidate.
+ *  3. Texel (i, j) of a face with best view v.  b1 = i, b2 = j, b0 = R - i - j: integers, b0 = -1 in
+ *     the gutter.  Per coordinate q = (float)((((double)b0 * p0 + (double)b1 * p1) + (double)b2 * p2) /
+ *     (double)R) of the corners' positions.  q is projected with step 1 of the triangle render under
+ *     M_v.  If it is VALID: fx is clamped to [0, 16 (W - 1)], fy to [0, 16 (H - 1)], S is step 4 of
+ *     arvx_mesh_color (the integer bilinear sample) and the texel's channel is (S + 128) >> 8, stored B,
+ *     G, R.  If it is not VALID, the texel is a fall-back texel.
+ *  4. Fall-back texel (a face without a view, or a projection that is not VALID).  Per channel
+ *     w = (float)((((double)b0 * col0 + (double)b1 * col1) + (double)b2 * col2) / (double)R), stored as
+ *     the render stores a channel: (uint8_t)roundf(fminf(fmaxf(w, 0.f), 255.f)).
+ *  5. Product: the atlas, AH x AW x 3 u8; face_view, T int32; face_uv, T x 3 x 2 fp32; the four numbers
+ *     {T, textured faces (face_view >= 0), AW, AH}.  An empty mesh gives AH = 0 and empty arrays.
+ *  6. Drawing: in arvx_render_mesh, _view and _agreement, source | ARVX_MESH_TEXTURED replaces the
+ *     interpolated vertex colour of the render's step 5.  With the winner's t1, t2 and S:
+ *     i = (int)floor((t1 / S) * (double)R + 0.5), j = (int)floor((t2 / S) * (double)R + 0.5), each
+ *     clamped to [0, R] (i + j <= R + 1 always holds: what the gutter is for); v is the channel of the
+ *     face's local texel (i, j) as a float.  The light factor and the final rounding are unchanged.
+ *     ARVX_MESH_IMAGE_COLORS and ARVX_MESH_TEXTURED together are ARVX_ERR_INVALID.
+ * arvx_mesh_texture takes ONE host synchronisation, for the textured count, and fills out[4] with the
+ * four numbers; arvx_mesh_texture_info returns them again (host bookkeeping);
+ * arvx_mesh_texture_download copies the three arrays (any pointer may be null; face_uv is computed on
+ * the host from the layout).
+ * Refusals.  ARVX_ERR_STATE: a slab or a striped context; the source mesh does not exist; no views, or
+ * no images; ARVX_MESH_TEXTURE_FOREGROUND when the views were set with masks == NULL; info or download
+ * before a product; ARVX_MESH_TEXTURED in a render when the product does not exist or was computed for
+ * another source.  ARVX_ERR_INVALID: R outside [1, 253], AW outside [cw, 16384], AH above 32768, an
+ * unknown source, unknown flag bits, a NaN or negative tolerance, a null `out`.  A refused call leaves
+ * the previous product as it was.
+ * Lifetime.  One product per context, tagged with its source: a snapshot of the mesh, the views and
+ * the images at the call.  It ends at the next successful arvx_mesh_texture and wherever
+ * arvx_mesh_color's product of the same source would end (that block's lifetime paragraph).  Its
+ * buffers are its own: it ends neither the current render nor the mesh colours' product, and
+ * arvx_mesh_color does not end it.
+ * Device memory.  Kept with the product: 3 AW AH bytes of atlas and 4 T bytes of views.  Workspace:
+ * depth keys of its own, V * W * H * 8 bytes (arvx_mesh_color_depth_download stays right after a
+ * texture call); ceil(V / 32) words per vertex of visibility bits; the batches' projected vertices and
+ * list of large boxes are arvx_mesh_color's, bounded by the same two self-test hooks.
+ * Out of scope: blending across the seams between faces that chose different views, view weighting by
+ * normals, mip levels, packing by projected area, charts larger than one face, a caller's mesh,
+ * near-plane clipping, slabs and multi-GPU. */
+#define ARVX_MESH_TEXTURE_FOREGROUND 1u /* flags of arvx_mesh_texture */
+#define ARVX_MESH_TEXTURED 0x400       /* OR-ed into `source` of the arvx_render_mesh family */
+#define ARVX_MESH_TEXTURE_MAX_RESOLUTION 253
+#define ARVX_MESH_TEXTURE_MAX_WIDTH 16384
+#define ARVX_MESH_TEXTURE_MAX_HEIGHT 32768
+int arvx_mesh_texture(arvx_ctx *ctx, int source, int resolution, int atlas_width, float tolerance, unsigned flags,
+                      int64_t out[4]);
+int arvx_mesh_texture_info(arvx_ctx *ctx, int64_t out[4]);
+int arvx_mesh_texture_download(arvx_ctx *ctx, uint8_t *atlas_bgr, int32_t *face_view, float *face_uv);
 
 /* Model::voxels as the reference would hold it after carve [+ colour]
  * [+ handleUnseen]: n*4 floats (RGBA), n = slab voxels. */

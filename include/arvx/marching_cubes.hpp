@@ -36,6 +36,7 @@
 
 #include "arvx/host_pool.hpp"
 #include "arvx/mc_tables.hpp"
+#include "arvx/mesh_texture.hpp"
 #include "arvx/voxel_carving.hpp"
 
 namespace arvx {
@@ -716,7 +717,8 @@ inline RenderedView rendered_view(arvx_ctx *ctx, int W, int H) {
 // on the device, also after the model has moved on (renderWelded's note).  Only a missing welded mesh
 // is built here, as renderWelded builds it; any other source that the context does not hold throws.
 // source | ARVX_MESH_IMAGE_COLORS draws the mesh with the colours of the last colorMesh of that source
-// (below); without them the call throws.
+// (below), source | ARVX_MESH_TEXTURED with the atlas of the last textureMesh of that source; without
+// that product the call throws.
 inline RenderedView renderMesh(Model *model, int source, const float M[12], int W, int H,
                                const uint8_t *background = nullptr, const float *light = nullptr) {
     arvx_ctx *ctx = model->device_for_reading();
@@ -785,6 +787,67 @@ inline MeshColors colorMesh(const Intrinsics &intr, Model *model, const std::vec
     out.views.resize((size_t)vertices);
     detail::check(arvx_mesh_color_download(ctx, out.rgb.data(), out.views.data()), "arvx_mesh_color_download");
     return out;
+}
+
+// ---- mesh textures from the images (an extension beyond the reference) ----------------------------
+//
+// A texture atlas of the mesh `source` that the model's context holds (arvx_mesh_texture, defined in
+// include/arvx/arvx.h): one triangle of texels per face, `resolution` texels along a leg, two faces per
+// cell, `atlas_width` texels per atlas row; each face sampled from the view that sees its three corners
+// within `tolerance` (world units) and shows it largest.  ARVX_MESH_TEXTURE_FOREGROUND in `flags` as
+// ARVX_MESH_COLOR_FOREGROUND.  The views are bound with their masks and their images, as colorMesh
+// binds them.  renderMesh(model, source | ARVX_MESH_TEXTURED, ...) then draws the mesh with the atlas,
+// until the source mesh is built again; writeOBJ (include/arvx/mesh_texture.hpp) writes it.
+inline MeshTexture textureMesh(const Intrinsics &intr, Model *model, const std::vector<View> &views, int source,
+                               int resolution, int atlas_width = 4096, float tolerance = 0.f, unsigned flags = 0) {
+    arvx_ctx *ctx = detail::bind_views(intr, *model, views, false);
+    model->set_colors_on_device(false);  // (arvx_set_views drops the context's colour list)
+    std::vector<const uint8_t *> imgs(views.size());
+    for (size_t i = 0; i < views.size(); ++i) {
+        const Image &im = views[i].image;
+        if (!im.data || im.channels != 3 || im.width != views[0].mask.width || im.height != views[0].mask.height ||
+            im.stride != views[0].image.stride)
+            throw Error(ARVX_ERR_INVALID, "textureMesh: colour images must be BGR u8 with the masks' size");
+        imgs[i] = im.data;
+    }
+    detail::check(arvx_set_images(ctx, imgs.data(), views[0].image.stride), "arvx_set_images");
+    int64_t n[4] = {0, 0, 0, 0};
+    int rc = arvx_mesh_texture(ctx, source, resolution, atlas_width, tolerance, flags, n);
+    if (rc == ARVX_ERR_STATE && source == ARVX_MESH_WELDED) {  // no welded mesh yet: built as renderMesh builds it
+        bool on_device = false;
+        (void)model->inside_state(0.5f, on_device);
+        if (on_device) {
+            int apply_unseen = 0;
+            ctx = detail::mesh_context(model, apply_unseen);
+            int64_t nv = 0, nt = 0;
+            detail::check(arvx_mc_mesh_welded(ctx, apply_unseen, &nv, &nt), "arvx_mc_mesh_welded");
+            rc = arvx_mesh_texture(ctx, source, resolution, atlas_width, tolerance, flags, n);
+        }
+    }
+    detail::check(rc, "arvx_mesh_texture");
+    MeshTexture out;
+    out.faces = n[0], out.textured = n[1];
+    out.width = (int)n[2], out.height = (int)n[3], out.resolution = resolution;
+    out.atlas.resize((size_t)n[2] * (size_t)n[3] * 3);
+    out.face_view.resize((size_t)n[0]);
+    out.face_uv.resize(6 * (size_t)n[0]);
+    detail::check(arvx_mesh_texture_download(ctx, out.atlas.data(), out.face_view.data(), out.face_uv.data()),
+                  "arvx_mesh_texture_download");
+    return out;
+}
+
+// writeOBJ of a SimpleMesh: its vertices scaled and moved as WriteMesh scales and moves them.
+inline bool writeOBJ(const std::string &path, const SimpleMesh &mesh, const MeshTexture &texture, float scaleFactor = 1.f,
+                     Vec3f translation = Vec3f(0, 0, 0)) {
+    const HostVector<Vec3f> &mv = mesh.GetVertices();
+    const HostVector<Triangle> &mt = mesh.GetTriangles();
+    std::vector<float> v(3 * mv.size());
+    for (size_t i = 0; i < mv.size(); ++i) {
+        volatile float px = mv[i].x() * scaleFactor, py = mv[i].y() * scaleFactor, pz = mv[i].z() * scaleFactor;
+        v[3 * i] = px + translation.x(), v[3 * i + 1] = py + translation.y(), v[3 * i + 2] = pz + translation.z();
+    }
+    static_assert(sizeof(Triangle) == 24, "a face record: three indices, then r, g, b");
+    return writeOBJ(path, v.data(), mv.size(), mt.empty() ? nullptr : &mt[0].idx0, mt.size(), 6, texture);
 }
 
 // Draws a mesh of the caller's on the model's context (arvx_render_triangles): its vertices in voxel

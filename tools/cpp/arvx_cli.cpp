@@ -223,6 +223,23 @@ bool render_views(const std::string &dir, const Inputs &in, arvx::Model &model, 
     return true;
 }
 
+// the vertices and the faces' indices of an OFF file as SimpleMesh::WriteMesh writes it
+bool read_off(const std::string &path, std::vector<float> &verts, std::vector<unsigned> &faces) {
+    std::ifstream f(path);
+    std::string magic;
+    size_t nv = 0, nt = 0, ne = 0;
+    if (!(f >> magic >> nv >> nt >> ne) || magic != "OFF") return false;
+    verts.resize(3 * nv);
+    for (float &c : verts) f >> c;
+    faces.resize(3 * nt);
+    for (size_t t = 0; t < nt; ++t) {
+        unsigned n = 0, r, g, b;
+        f >> n >> faces[3 * t] >> faces[3 * t + 1] >> faces[3 * t + 2] >> r >> g >> b;
+        if (n != 3) return false;
+    }
+    return (bool)f;
+}
+
 }  // namespace
 
 int main(int argc, char *argv[]) {
@@ -238,7 +255,7 @@ int main(int argc, char *argv[]) {
         {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
         {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"},
         {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"renderMesh", "false"},
-        {"meshColor", ""}, {"meshForeground", "false"}};
+        {"meshColor", ""}, {"meshForeground", "false"}, {"texture", "0"}, {"atlasWidth", "4096"}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -278,7 +295,14 @@ int main(int argc, char *argv[]) {
                      "    vertex a vote over the views that see it within -visibleTol voxel edges, sampled\n"
                      "    bilinearly -- and the renders drawn with those colours),\n"
                      "  -meshForeground=true (with -meshColor: a view votes only where its mask has the\n"
-                     "    vertex's pixel as foreground)\n";
+                     "    vertex's pixel as foreground),\n"
+                     "  -texture=R (the mesh the run wrote after -weld, -smooth, -decimate or -refine, textured\n"
+                     "    from the input images: a triangle of texels per face, R texels along a leg, 1 <= R <=\n"
+                     "    253, each face sampled from the view that sees its corners within -visibleTol voxel\n"
+                     "    edges and shows it largest; written beside -outFile as <stem>.obj, .mtl and .ppm;\n"
+                     "    with -render and -renderMesh=true the renders draw the texture; -meshForeground applies;\n"
+                     "    not together with -meshColor),\n"
+                     "  -atlasWidth=AW (texels per row of the texture atlas, default 4096)\n";
         return 0;
     }
     const int choose = parser.i("c");
@@ -546,6 +570,38 @@ int main(int argc, char *argv[]) {
             std::cout << "LOG - MESH COLOR: " << col.coloured << " of " << col.views.size()
                       << " vertices coloured from the images" << std::endl;
             drawn = mesh_source | ARVX_MESH_IMAGE_COLORS;
+        }
+        // -texture=R -atlasWidth=AW: the mesh written above textured from the images, written beside the
+        // OFF file with the OFF file's own vertices, and drawn by the renders
+        if (parser.i("texture") != 0) {
+            const int source = !parser.str("refine").empty() ? ARVX_MESH_REFINED
+                               : parser.i("decimate") > 0    ? ARVX_MESH_DECIMATED
+                               : parser.i("smooth") > 0      ? ARVX_MESH_SMOOTHED
+                               : parser.b("weld")            ? ARVX_MESH_WELDED
+                                                             : -1;
+            if (source < 0) {
+                std::cerr << "-texture needs a mesh with shared vertices: -weld, -smooth, -decimate or -refine" << std::endl;
+                return 1;
+            }
+            if (!meshColor.empty()) {
+                std::cerr << "-texture and -meshColor exclude each other" << std::endl;
+                return 1;
+            }
+            const arvx::MeshTexture tex = arvx::textureMesh(
+                in.intr, &model, in.views, source, parser.i("texture"), parser.i("atlasWidth"), tol * model.getSize(),
+                parser.b("meshForeground") ? ARVX_MESH_TEXTURE_FOREGROUND : 0u);
+            std::cout << "LOG - MESH TEXTURE: " << tex.textured << " of " << tex.faces << " faces textured from the images, atlas "
+                      << tex.width << " x " << tex.height << std::endl;
+            std::vector<float> verts;
+            std::vector<unsigned> faces;
+            const fs::path off(parser.str("outFile"));
+            if (!read_off(off.string(), verts, faces) || faces.size() != 3 * (size_t)tex.faces ||
+                !arvx::writeOBJ(fs::path(off).replace_extension(".obj").string(), verts.data(), verts.size() / 3, faces.data(),
+                                faces.size() / 3, 3, tex)) {
+                std::cerr << "Could not write the textured mesh beside " << off.string() << " (--texture)" << std::endl;
+                return 1;
+            }
+            if (mesh_source >= 0) drawn = mesh_source | ARVX_MESH_TEXTURED;
         }
         if (!parser.str("render").empty() && !render_views(parser.str("render"), in, model, drawn)) return 1;
     } catch (const arvx::Error &e) {
