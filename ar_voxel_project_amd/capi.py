@@ -96,7 +96,7 @@ SYMBOLS = [
     "arvx_mc_mesh_refined", "arvx_mc_mesh_refined_download",
     "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
     "arvx_render_mesh", "arvx_render_mesh_view", "arvx_render_mesh_agreement", "arvx_render_triangles",
-    "arvx_render_mesh_stats", "arvx_selftest_render_mesh_list",
+    "arvx_render_mesh_stats", "arvx_selftest_render_mesh_list", "arvx_selftest_compute_units",
     "arvx_mesh_color", "arvx_mesh_color_count", "arvx_mesh_color_download", "arvx_mesh_color_depth_download",
     "arvx_selftest_mesh_color_batch",
     "arvx_mesh_texture", "arvx_mesh_texture_info", "arvx_mesh_texture_download",
@@ -284,6 +284,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                               C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.arvx_render_mesh_stats.argtypes = [p, C.POINTER(C.c_int64)]
         lib.arvx_selftest_render_mesh_list.argtypes = [p, C.c_int64]
+    if hasattr(lib, "arvx_selftest_compute_units") or not ab_build:
+        lib.arvx_selftest_compute_units.argtypes = [p, C.c_int]
     if hasattr(lib, "arvx_mesh_color") or not ab_build:
         lib.arvx_mesh_color.argtypes = [p, C.c_int, C.c_int, C.c_float, C.c_uint, C.POINTER(C.c_int64)]
         lib.arvx_mesh_color_count.argtypes = [p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -1103,6 +1105,11 @@ class Context:
     def selftest_render_mesh_list(self, cap: int) -> None:
         """Room of the triangle render's list of large pixel boxes from the next render on (-1: default)."""
         self._ck(self._lib.arvx_selftest_render_mesh_list(self._h, int(cap)))
+
+    def selftest_compute_units(self, n: int) -> None:
+        """Compute units that size the context's launches from the next call on (0: the device's own
+        count; never more than that)."""
+        self._ck(self._lib.arvx_selftest_compute_units(self._h, int(n)))
 
     def mesh_color(self, source: int, mode: int, tolerance: float, flags: int = 0, download: bool = True):
         """arvx_mesh_color: the vertices of the context's mesh `source` coloured from the images -- per

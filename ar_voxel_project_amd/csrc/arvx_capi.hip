@@ -230,6 +230,7 @@ static int compute_units(Ctx *ctx) {
         ctx->ncu = 256;
         (void)hipDeviceGetAttribute(&ctx->ncu, hipDeviceAttributeMultiprocessorCount, ctx->device);
         if (ctx->ncu <= 0) ctx->ncu = 256;
+        ctx->ncu_device = ctx->ncu;
     }
     return ctx->ncu;
 }
@@ -2350,8 +2351,9 @@ static int launch_depth_buffers(Ctx *ctx, const int *index, long long cap, const
     sp.large = large;
     sp.n_large = n_large;
     sp.large_cap = large_cap;
-    // (the x grid strides over the list: its capacity can be several times its length)
-    const dim3 sgrid((unsigned)std::min<long long>((cap + 255) / 256, 1024), (unsigned)ctx->V);
+    // (the x grid strides over the list: its capacity can be several times its length; 4 workgroups
+    // per compute unit and view, 1024 on 256 units)
+    const dim3 sgrid((unsigned)std::min<long long>((cap + 255) / 256, 4 * ncu), (unsigned)ctx->V);
     ARVX_TRY(by_assoc(ctx, [&](auto left) {
         return launch(ctx, arvx::vis_splat_kernel<decltype(left)::value>, sgrid, 256, sp);
     }));
@@ -3919,7 +3921,11 @@ static int render_launch(Ctx *ctx, const float *M, int W, int H, const uint8_t *
     // render_need is the count word as it stood at the last synchronisation of a render call
     // (arvx_render_download, arvx_render_agreement): renders launched back to back without one all
     // use the same capacity, whatever the device has finished by then.
-    const unsigned large_cap = large_list_cap(n, ctx->render_need, n);
+    // (arvx_selftest_render_mesh_list bounds this list too: a small model cannot fill its own)
+    const unsigned large_cap =
+        ctx->render_mesh_list_cap >= 0
+            ? (unsigned)std::min<long long>({ctx->render_mesh_list_cap, n, (long long)UINT32_MAX})
+            : large_list_cap(n, ctx->render_need, n);
     ARVX_TRY(render_begin(ctx, W, H, background, bg_stride, 64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
     unsigned long long *keys = (unsigned long long *)ctx->pool_render_keys.p;
     arvx::RenderHeader *head = (arvx::RenderHeader *)ctx->pool_render_large.p;
@@ -4229,6 +4235,16 @@ int arvx_selftest_render_mesh_list(arvx_ctx *ctx, int64_t cap) {
     ARVX_CHECK_CTX(ctx);
     if (cap < -1) return fail(ARVX_ERR_INVALID, "cap %lld (-1: the default room)", (long long)cap);
     ctx->render_mesh_list_cap = cap;
+    return ARVX_OK;
+}
+
+int arvx_selftest_compute_units(arvx_ctx *ctx, int n) {
+    ARVX_CHECK_CTX(ctx);
+    (void)compute_units(ctx);  // (the device's own count, once)
+    if (n < 0 || n > ctx->ncu_device)
+        return fail(ARVX_ERR_INVALID, "compute units %d: must be 0 (the device's %d) or 1 .. %d", n,
+                    ctx->ncu_device, ctx->ncu_device);
+    ctx->ncu = n > 0 ? n : ctx->ncu_device;
     return ARVX_OK;
 }
 

@@ -156,7 +156,8 @@ struct Ctx {
     uint8_t *owned() const { return (uint8_t *)pool_state_bytes.p + (size_t)(z0 - ze0) * X * Y; }
     DevPool pool_paint;          // bit plane (bitplane_kernels.h layout) over planes ze0..ze1-1
     bool paint_valid = false;    // some voxel is painted: the plane takes part in the stages
-    int ncu = 0;                 // compute units of the device (cached)
+    int ncu = 0;                 // compute units that size the launches: the device's (cached), or
+    int ncu_device = 0;          // ... fewer of them (arvx_selftest_compute_units); the device's own
     int carve_seq = 0;           // parity of the undecided-list counters (carve_coarse_kernel)
     size_t carve_layout = 0;     // pool_coarse layout those counters were zeroed for
     // arvx_last_carve_path: the last launch_carve's ARVX_PATH_* bits, its dense classify grid, and

@@ -970,9 +970,15 @@ int arvx_render_triangles(arvx_ctx *ctx, int64_t nv, const float *verts, const f
                           size_t bg_stride, const float *light);
 int arvx_render_mesh_stats(arvx_ctx *ctx, int64_t out[4]);
 /* Self-test hook: room of the triangle render's list of large pixel boxes from the next render on
- * (0: everything large is swept in place; -1: the default sizing).  The room changes the time, never
- * the images. */
+ * (0: everything large is swept in place; -1: the default sizing), and of arvx_render's list of large
+ * footprints.  The room changes the time, never the images. */
 int arvx_selftest_render_mesh_list(arvx_ctx *ctx, int64_t cap);
+/* Self-test hook: the compute-unit count that sizes the context's launches from the next call on
+ * (every grid and ticket pool that is "so many workgroups per compute unit"), as a partition of the
+ * device would show it.  0: back to the device's own count; 1 .. the device's count: that many;
+ * anything else: ARVX_ERR_INVALID, nothing changed -- the hook only ever shrinks a launch.  The count
+ * changes the time, never a result. */
+int arvx_selftest_compute_units(arvx_ctx *ctx, int n);
 
 /* ---- mesh colours from the images (extension beyond the reference) -----------------------------
  * Colours the vertices of a held mesh from the photographs: per view the depth buffer of the mesh's

@@ -52,6 +52,84 @@ def signed_sq(state, dims, border_occupied=False):
     return np.where(occ, d, -d).astype(np.int32).reshape(-1)
 
 
+def signed_sq_sparse(dims, sites, site_kind, border_occupied=False):
+    """signed_sq of the grid that is all of one kind except for the voxels `sites` ((x, y, z) each),
+    which are occupied if site_kind and empty if not -- straight from the definition, a minimum over
+    the listed sites and the six borders in int64, O(voxels * sites): for axes too long for the
+    separable route's O(n^2).  -> int32 per voxel, flat index order."""
+    X, Y, Z = dims
+    z, y, x = np.meshgrid(np.arange(Z, dtype=np.int64), np.arange(Y, dtype=np.int64),
+                          np.arange(X, dtype=np.int64), indexing="ij")
+    listed = np.zeros((Z, Y, X), bool)
+    for sx, sy, sz in sites:
+        listed[sz, sy, sx] = True
+    border = np.minimum.reduce([x + 1, X - x, y + 1, Y - y, z + 1, Z - z]) ** 2
+    # the other voxels: the nearest listed site -- and the border, where the sites are the empty ones
+    to_site = np.full((Z, Y, X), _BIG, np.int64)
+    # the listed voxels: the nearest voxel that is not listed -- and the border, where those are empty
+    to_rest = np.full(len(sites), _BIG, np.int64)
+    for k, (sx, sy, sz) in enumerate(sites):
+        d = (x - sx) ** 2 + (y - sy) ** 2 + (z - sz) ** 2
+        np.minimum(to_site, d, out=to_site)
+        if not listed.all():
+            to_rest[k] = d[~listed].min()
+    d = to_site
+    for k, (sx, sy, sz) in enumerate(sites):
+        d[sz, sy, sx] = to_rest[k]
+    occ = listed if site_kind else ~listed
+    if not border_occupied:  # (the border's sites are empty ones: the occupied voxels look for them)
+        d = np.where(occ, np.minimum(d, border), d)
+    d = np.where(d >= _BIG // 2, np.int64(INF), d)
+    return np.where(occ, d, -d).astype(np.int32).reshape(-1)
+
+
+def signed_sq_near(state, dims, border_occupied=False, reach=8):
+    """signed_sq of a state in which every voxel has its nearest opposite site within `reach` (asserted):
+    the minimum over the offsets of the cube of that half-width, straight from the definition, in int64,
+    O(voxels * offsets) whatever the lengths of the axes -- for densely mixed states on a long axis."""
+    occ = _occ(state, dims)
+    Z, Y, X = occ.shape
+    rz, ry, rx = min(reach, Z), min(reach, Y), min(reach, X)
+
+    def to_sites(is_site, outside):
+        p = np.pad(is_site, ((rz, rz), (ry, ry), (rx, rx)), constant_values=outside)
+        d = np.full(occ.shape, _BIG, np.int64)
+        for dz in range(-rz, rz + 1):
+            for dy in range(-ry, ry + 1):
+                for dx in range(-rx, rx + 1):
+                    there = p[rz + dz:rz + dz + Z, ry + dy:ry + dy + Y, rx + dx:rx + dx + X]
+                    np.minimum(d, np.where(there, np.int64(dx * dx + dy * dy + dz * dz), _BIG), out=d)
+        return d
+
+    d = np.where(occ, to_sites(~occ, not border_occupied), to_sites(occ, False))
+    # (a site nearer than the one found would lie inside the cube too)
+    assert d.max() <= reach * reach, "a voxel without an opposite site within reach"
+    return np.where(occ, d, -d).astype(np.int32).reshape(-1)
+
+
+def signed_sq_two_lines(n, lines, border_occupied=False):
+    """signed_sq of a 2 x n x 1 grid (and of a 2 x 1 x n one: the flat order is the same, x + 2 j) whose
+    line x is all of one kind except for the voxels lines[x] = (positions, site_kind) -- from
+    signed_sq_sparse of each line alone, joined by the one step there is between the two lines."""
+    to_empty, to_occupied, occ = [], [], []
+    j = np.arange(n, dtype=np.int64)
+    for sites, kind in lines:
+        f = signed_sq_sparse((1, n, 1), [(0, int(k), 0) for k in sites], kind, True).astype(np.int64)
+        to_empty.append(np.where(f > 0, np.where(f == INF, _BIG, f), 0))
+        to_occupied.append(np.where(f < 0, np.where(f == -INF, _BIG, -f), 0))
+        occ.append(f > 0)
+    out = np.empty((n, 2), np.int64)
+    for x in (0, 1):
+        e = np.minimum(to_empty[x], to_empty[1 - x] + 1)
+        if not border_occupied:  # (the line's two ends; the lattice point beside the voxel, off the grid)
+            e = np.minimum.reduce([e, (j + 1) ** 2, (n - j) ** 2, np.ones(n, np.int64)])
+        o = np.minimum(to_occupied[x], to_occupied[1 - x] + 1)
+        d = np.where(occ[x], e, o)
+        d = np.where(d >= _BIG // 2, np.int64(INF), d)
+        out[:, x] = np.where(occ[x], d, -d)
+    return out.astype(np.int32).reshape(-1)
+
+
 def ball(radius_sq, dims):
     """The offsets (dx, dy, dz) with |o|^2 <= radius_sq.  An offset of X or more along x leaves the grid
     from every voxel, as one of exactly X does: the ball is cut there (and likewise along y and z)."""

@@ -102,6 +102,66 @@ def test_signed_sq_special_values():
     assert d.max() == 50  # (the centre voxel: the nearest lattice points beyond radius 7 are (5, 5, 0) and (7, 1, 0))
 
 
+def _state_of_sites(dims, sites, site_kind):
+    X, Y, Z = dims
+    occ = np.full((Z, Y, X), not site_kind)
+    for x, y, z in sites:
+        occ[z, y, x] = site_kind
+    return occ.astype(np.uint8).reshape(-1)
+
+
+@pytest.mark.parametrize("dims,sites", [
+    ((33, 17, 9), [(0, 0, 0), (32, 16, 8), (5, 9, 4), (6, 9, 4), (20, 0, 3)]),
+    ((70, 2, 3), [(69, 1, 2), (64, 0, 0), (63, 0, 0), (3, 1, 1)]),
+    ((1, 40, 1), [(0, 0, 0), (0, 39, 0), (0, 17, 0)]),
+    ((5, 4, 3), []),
+    ((2, 1, 1), [(0, 0, 0), (1, 0, 0)]),
+])
+def test_signed_sq_sparse_against_signed_sq(dims, sites):
+    """The direct minimum over a few sites and the borders is the separable route's field."""
+    for site_kind in (False, True):
+        st = _state_of_sites(dims, sites, site_kind)
+        for border_occupied in (False, True):
+            got = dist.signed_sq_sparse(dims, sites, site_kind, border_occupied)
+            assert got.dtype == np.int32
+            assert np.array_equal(got, dist.signed_sq(st, dims, border_occupied)), (site_kind, border_occupied)
+
+
+@pytest.mark.parametrize("dims,seed", [((33, 17, 9), 2), ((5, 70, 1), 4), ((5, 1, 70), 5), ((1, 1, 9), 7)])
+def test_signed_sq_near_against_signed_sq(dims, seed):
+    """The minimum over a cube of offsets is the separable route's field where no distance exceeds the
+    cube's half-width, and says so where one does."""
+    st = dist.bytes_of(dist.random_occ(dims, 0.5, seed), seed=7)
+    for border_occupied in (False, True):
+        want = dist.signed_sq(st, dims, border_occupied)
+        assert np.abs(want.astype(np.int64)).max() <= 64
+        got = dist.signed_sq_near(st, dims, border_occupied)
+        assert got.dtype == np.int32 and np.array_equal(got, want), border_occupied
+    with pytest.raises(AssertionError):
+        dist.signed_sq_near(dist.bytes_of(dist.one_corner((33, 17, 9), True)), (33, 17, 9))
+
+
+@pytest.mark.parametrize("lines", [
+    (([0, 39], False), ([5, 20, 33], True)),
+    (([3], True), ([3, 4], True)),
+    (([], False), ([], True)),
+    (([0], False), ([39], False)),
+    (([], True), ([7], True)),
+])
+def test_signed_sq_two_lines_against_signed_sq(lines):
+    n = 40
+    occ = np.empty((n, 2), bool)
+    for x, (sites, kind) in enumerate(lines):
+        occ[:, x] = not kind
+        occ[sites, x] = kind
+    st = occ.astype(np.uint8).reshape(-1)
+    for border_occupied in (False, True):
+        got = dist.signed_sq_two_lines(n, lines, border_occupied)
+        assert got.dtype == np.int32
+        assert np.array_equal(got, dist.signed_sq(st, (2, n, 1), border_occupied)), border_occupied
+        assert np.array_equal(got, dist.signed_sq(st, (2, 1, n), border_occupied)), border_occupied
+
+
 @pytest.mark.parametrize("name", sorted(HAND))
 def test_morph_against_scipy_and_the_distance_route(name):
     dims, make = HAND[name]

@@ -4,8 +4,11 @@ the four ops at squared radii 0, 1, 2, 3, 9 and one above the grid, on the grids
 go wrong (a partial word, rows of several words, many workgroups on every axis, degenerate axes, columns
 longer than any chunk of the scan, a row of 17 words) with random fills, the empty and the full grid,
 single voxels, the checkerboard, far corners and a solid ball, and on the lazy state a carve leaves;
-what a morph drops and keeps; the carve and the stages after one; the refusals; the C++ layer; the
-CLI."""
+rows of 130 words (pass 1 beyond its window of 64 words, both ways, for both kinds, with a short last
+word) and columns of 33 000 and 46 339 entries (the stack's 16-bit halves above 32 767), against the
+direct minimum over a few sites, or over a cube of offsets, where the separable restatement is too
+slow; what a morph drops and keeps; the carve and the stages after one; the refusals; the C++ layer;
+the CLI."""
 import ctypes
 import os
 import subprocess
@@ -152,6 +155,172 @@ def test_special_values(arvx):
         assert d[32, 48, 64] == -(63 ** 2 + 47 ** 2 + 31 ** 2)  # (the far corner is the nearer one)
         ctx.upload_state(dist.bytes_of(dist.solid_ball(dims, 30)))
         assert ctx.distance().max() == 901  # (the centre: the nearest lattice point beyond 30 is (30, 1, 0))
+
+
+# ---- rows of more than 64 words, columns of more than 32 767 entries -----------------------------------
+
+LONG_ROW = (8300, 2, 1)  # 130 words a row: three windows of 64 words in pass 1, a last word of 44 bits
+
+
+def _two_long_rows():
+    """Row 0 empty but for x = 100 and x = 8250, row 1 occupied but for x = 4200 and x = 8299: from most
+    words the nearest word with a voxel of the other kind lies outside the window of 64, on either side,
+    and the row's last word, short of 20 bits, is the far word of a search."""
+    occ = np.zeros(_zyx(LONG_ROW), bool)
+    occ[0, 0, [100, 8250]] = True
+    occ[0, 1, :] = True
+    occ[0, 1, [4200, 8299]] = False
+    return occ
+
+
+LONG_ROWS = {
+    "two rows": (LONG_ROW, _two_long_rows),
+    "two rows, complement": (LONG_ROW, lambda: ~_two_long_rows()),
+    "p=0.0003": (LONG_ROW, lambda: dist.random_occ(LONG_ROW, 0.0003, 301)),
+    "p=0.9997": (LONG_ROW, lambda: dist.random_occ(LONG_ROW, 0.9997, 302)),
+}
+# each of the two rows as a grid of its own: with the other row one step away the passes along y and z
+# take most of pass 1's long distances back, alone (and with the border occupied) they are the field
+for _r in (0, 1):
+    LONG_ROWS[f"row {_r} alone"] = ((8300, 1, 1), lambda r=_r: _two_long_rows()[:, r:r + 1, :])
+    LONG_ROWS[f"row {_r} alone, complement"] = ((8300, 1, 1), lambda r=_r: ~_two_long_rows()[:, r:r + 1, :])
+
+
+def check_erode_dilate(ctx, key, st, dims):
+    for op in (dist.ERODE, dist.DILATE):
+        ctx.upload_state(st)
+        check_morph(ctx, key, st, dims, op, 9)
+
+
+@pytest.mark.parametrize("name", sorted(LONG_ROWS))
+def test_long_rows(arvx, name):
+    """Pass 1 beyond its window of 64 words: the searches through memory towards either end, for either
+    kind, and the tail mask on a far word."""
+    dims, make = LONG_ROWS[name]
+    key = f"{_name(dims)} {name}"
+    occ = make()
+    assert occ.shape == _zyx(dims) and occ.any() and not occ.all()
+    if "row" in name:  # in every row, a voxel whose nearest opposite voxel of the row is 63 words or more away
+        x = np.arange(dims[0])
+        for row in occ[0]:
+            kind = row.sum() * 2 > len(row)  # (the row's many)
+            assert np.abs(x[row == kind][:, None] - x[row != kind][None, :]).min(axis=1).max() > 63 * 64
+    st = dist.bytes_of(occ, seed=11)
+    with arvx.Context(*dims, S) as ctx:
+        ctx.upload_state(st)
+        check_field(ctx, key, st, dims)
+        if "alone" in name:  # (what the case is for: pass 1's long distances in the field)
+            assert np.abs(expected_field(key, st, dims, True).astype(np.int64)).max() > (63 * 64) ** 2
+        check_erode_dilate(ctx, key, st, dims)
+        assert ctx.stats()["host_total_fallbacks"] == 0
+
+
+LONG_LINES = (([0, 32999], False), ([5, 16500, 32768], True))  # line x = 0: occupied but for ..; x = 1: empty but for ..
+
+
+@pytest.mark.parametrize("axis", (1, 2))
+def test_long_columns(arvx, axis):
+    """Columns of 33 000 entries along y and along z: sites and first coordinates above 32 767 in the
+    stack's 16-bit halves.  Line x = 0 puts every voxel on its lane's stack (33 000 entries), line x = 1
+    three sites far apart; the expected field comes from the direct minimum over the sites."""
+    n = 33000
+    dims = (2, n, 1) if axis == 1 else (2, 1, n)
+    occ = np.empty((n, 2), bool)
+    for x, (sites, kind) in enumerate(LONG_LINES):
+        occ[:, x] = not kind
+        occ[sites, x] = kind
+    st = dist.bytes_of(occ.reshape(_zyx(dims)), seed=11)
+    key = f"2x{n} lines"
+    with arvx.Context(*dims, S) as ctx:
+        ctx.upload_state(st)
+        for border_occupied in (False, True):
+            k = (key, border_occupied)
+            if k not in _fields:
+                _fields[k] = dist.signed_sq_two_lines(n, LONG_LINES, border_occupied)
+                _fields[k].setflags(write=False)
+            want = _fields[k]
+            got = ctx.distance(border_occupied)
+            assert got.dtype == np.int32 and np.array_equal(got, want), (dims, border_occupied)
+        k = f"{_name(dims)} lines"
+        check_erode_dilate(ctx, k, st, dims)
+        assert ctx.stats()["host_total_fallbacks"] == 0
+
+
+@pytest.mark.parametrize("line", (0, 1))
+@pytest.mark.parametrize("axis", (1, 2))
+def test_long_column_alone(arvx, axis, line):
+    """Each of the two lines as a grid of its own, where no neighbouring line is one step away and the
+    values are those of sites thousands of entries off, on either side of 32 767."""
+    n = 33000
+    dims = (1, n, 1) if axis == 1 else (1, 1, n)
+    where, kind = LONG_LINES[line]
+    sites = [(0, j, 0) if axis == 1 else (0, 0, j) for j in where]
+    st = np.full(n, 0 if kind else 1, np.uint8)
+    st[where] = 1 if kind else 0
+    with arvx.Context(*dims, S) as ctx:
+        ctx.upload_state(st)
+        for border_occupied in (False, True):
+            k = (f"1x{n} line {line}", border_occupied)
+            if k not in _fields:
+                _fields[k] = dist.signed_sq_sparse((1, n, 1), [(0, j, 0) for j in where], kind, border_occupied)
+                _fields[k].setflags(write=False)
+            want = _fields[k]
+            if border_occupied:  # (what the case is for)
+                d = want.astype(np.int64)
+                assert (d[32000] == -(768 ** 2) and d[10000] == -(6500 ** 2)) if line else \
+                    (d[20000] == 12999 ** 2 and d[32767] == 232 ** 2)
+            got = ctx.distance(border_occupied)
+            assert got.dtype == np.int32 and np.array_equal(got, want), (dims, line, border_occupied)
+        check_erode_dilate(ctx, f"{_name(dims)} line {line}", st, dims)
+
+
+@pytest.mark.parametrize("axis", (1, 2))
+def test_long_column_random(arvx, axis):
+    """Five columns of 33 000 entries, random fill 0.8: pass 1 leaves partial distances of 1, 4, 9, ..
+    side by side, so a site of the column pass takes several entries off its lane's stack at a time,
+    and past entry 32 767 every entry it reloads has a first coordinate above 2^15 (the sparse columns
+    above never reload one)."""
+    n = 33000
+    dims = (5, n, 1) if axis == 1 else (5, 1, n)
+    st = dist.bytes_of(dist.random_occ(dims, 0.8, 311), seed=11)
+    with arvx.Context(*dims, S) as ctx:
+        ctx.upload_state(st)
+        for border_occupied in (False, True):
+            k = (f"{_name(dims)} p=0.8", border_occupied)
+            if k not in _fields:
+                _fields[k] = dist.signed_sq_near(st, dims, border_occupied)
+                _fields[k].setflags(write=False)
+            want = _fields[k]
+            if border_occupied:  # (what the case is for: distances along the column, past 32 767)
+                d = np.abs(want.astype(np.int64)).reshape(n, 5)
+                assert (d[32768:] >= 4).sum() > 100
+            got = ctx.distance(border_occupied)
+            assert got.dtype == np.int32 and np.array_equal(got, want), (dims, border_occupied)
+
+
+@pytest.mark.parametrize("far_end", (False, True))
+@pytest.mark.parametrize("axis", (1, 2))
+def test_longest_column(arvx, axis, far_end):
+    """46 339 entries, the longest column there is, occupied but for one end: with the border occupied
+    the field is the squared distance to that end, up to 46 338^2."""
+    n = 46339
+    dims = (1, n, 1) if axis == 1 else (1, 1, n)
+    hole = n - 1 if far_end else 0
+    site = (0, hole, 0) if axis == 1 else (0, 0, hole)
+    st = np.ones(n, np.uint8)
+    st[hole] = 0
+    j = np.arange(n, dtype=np.int64)
+    with arvx.Context(*dims, S) as ctx:
+        ctx.upload_state(st)
+        d = ctx.distance(True)
+        assert d.dtype == np.int32
+        want = (j - hole) ** 2
+        want[hole] = -1
+        assert want.max() == 46338 ** 2 < arvx.DISTANCE_INF
+        assert np.array_equal(d.astype(np.int64), want)
+        assert np.array_equal(d, dist.signed_sq_sparse(dims, [site], False, True))
+        assert np.array_equal(ctx.distance(False), dist.signed_sq_sparse(dims, [site], False, False))
+        check_erode_dilate(ctx, f"{_name(dims)} hole at {hole}", st, dims)
 
 
 # ---- the lazy state of a carve underneath -----------------------------------------------------------
