@@ -58,6 +58,9 @@ MESH_IMAGE_COLORS = 0x100  # OR-ed into `source` of the render_mesh family: draw
 MESH_COLOR_FOREGROUND = 1  # flags of mesh_color
 MESH_TEXTURED = 0x400  # OR-ed into `source` of the render_mesh family: draw mesh_texture()'s atlas
 MESH_TEXTURE_FOREGROUND = 1  # flags of mesh_texture
+SEGMENT_RANGE = 0  # rules of segment_views
+SEGMENT_PLATE = 1
+SEGMENT_LARGEST = 1  # flags of segment_views
 # test plumbing: flags OR-ed into every carve of this process, e.g. ARVX_CARVE_EXTRA_FLAGS=16 runs a
 # whole test module with the streaming carve forced on every fresh model (the library itself reads
 # no environment variable)
@@ -108,6 +111,8 @@ SYMBOLS = [
     "arvx_ctx_set_rect_cache_limit", "arvx_selftest_rect_cache",
     "arvx_ctx_set_view_window", "arvx_view_window", "arvx_view_window_host",
     "arvx_selftest_fill_view_tables", "arvx_selftest_view_table_raw",
+    "arvx_segment_views", "arvx_segment_views_device", "arvx_segment_download", "arvx_segment_counts",
+    "arvx_selftest_segment_batch",
 ]
 
 
@@ -115,6 +120,22 @@ class ArvxError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"arvx error {code}: {msg}")
         self.code = code
+
+
+class SegmentParams(C.Structure):
+    """arvx_segment_params (include/arvx/arvx.h)."""
+    _fields_ = [
+        ("rule", C.c_int32),
+        ("lo", C.c_uint8 * 3),
+        ("hi", C.c_uint8 * 3),
+        ("reserved", C.c_uint8 * 2),
+        ("threshold", C.c_int32),
+        ("open_radius", C.c_int32),
+        ("close_radius", C.c_int32),
+        ("flags", C.c_uint32),
+        ("min_area", C.c_int64),
+        ("max_hole", C.c_int64),
+    ]
 
 
 class Stats(C.Structure):
@@ -296,6 +317,15 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.arvx_mesh_texture.argtypes = [p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint, C.POINTER(C.c_int64)]
         lib.arvx_mesh_texture_info.argtypes = [p, C.POINTER(C.c_int64)]
         lib.arvx_mesh_texture_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "arvx_segment_views") or not ab_build:
+        sp = C.POINTER(SegmentParams)
+        lib.arvx_segment_views.argtypes = [p, C.c_int, f32p, f32p, C.c_void_p, C.c_int, C.c_int, C.c_size_t,
+                                           C.c_void_p, C.c_int, sp]
+        lib.arvx_segment_views_device.argtypes = [p, C.c_int, f32p, f32p, C.c_void_p, C.c_int, C.c_int,
+                                                  C.c_void_p, C.c_int, sp]
+        lib.arvx_segment_download.argtypes = [p, C.c_int, C.c_void_p]
+        lib.arvx_segment_counts.argtypes = [p, C.c_int, C.POINTER(C.c_int64)]
+        lib.arvx_selftest_segment_batch.argtypes = [p, C.c_int]
     for name in SYMBOLS:
         if ab_build and not hasattr(lib, name):
             continue
@@ -504,6 +534,87 @@ class Context:
         assert Cn == 3 and V == self.V and H == self.H and W == self.W
         ptrs = (C.c_void_p * V)(*[images[i].ctypes.data for i in range(V)])
         self._ck(self._lib.arvx_set_images(self._h, ptrs, W * 3))
+
+    # -- silhouettes from the photographs --
+    @staticmethod
+    def _segment_params(rule, lo, hi, threshold, open_radius, close_radius, min_area, largest, max_hole):
+        sp = SegmentParams()
+        sp.rule = int(rule)
+        for c in range(3):
+            sp.lo[c], sp.hi[c] = int(lo[c]), int(hi[c])
+        sp.threshold = int(threshold)
+        sp.open_radius, sp.close_radius = int(open_radius), int(close_radius)
+        sp.flags = SEGMENT_LARGEST if largest else 0
+        sp.min_area, sp.max_hole = int(min_area), int(max_hole)
+        return sp
+
+    def segment_views(self, M, images, campos=None, plates=None, rule: int = SEGMENT_RANGE,
+                      lo=(120, 120, 120), hi=(255, 255, 255), threshold: int = 0, open_radius: int = 0,
+                      close_radius: int = 0, min_area: int = 0, largest: bool = False, max_hole: int = 0,
+                      params: Optional[SegmentParams] = None) -> None:
+        """arvx_segment_views: the views from the photographs.  M: (V,3,4) float32; images: (V,H,W,3)
+        uint8 BGR, left resident as set_images would; plates (rule SEGMENT_PLATE): (H,W,3), (1,H,W,3)
+        or (V,H,W,3).  The rule and the cleaning steps are those of include/arvx/arvx.h; the defaults
+        are the reference's range rule (background 120..255) without cleaning.  `params`: a ready
+        SegmentParams instead of the keywords."""
+        M = _f32(M).reshape(-1, 12)
+        images = np.ascontiguousarray(images, dtype=np.uint8)
+        V, H, W, Cn = images.shape
+        assert Cn == 3 and M.shape[0] == V
+        ptrs = (C.c_void_p * V)(*[images[i].ctypes.data for i in range(V)])
+        pp, n_plates = None, 0
+        if plates is not None:
+            plates = np.ascontiguousarray(plates, dtype=np.uint8).reshape(-1, H, W, 3)
+            n_plates = len(plates)
+            pp = (C.c_void_p * n_plates)(*[plates[i].ctypes.data for i in range(n_plates)])
+        cp = None
+        if campos is not None:
+            campos = _f32(campos).reshape(V, 3)
+            cp = _fp(campos)
+        sp = params if params is not None else self._segment_params(
+            rule, lo, hi, threshold, open_radius, close_radius, min_area, largest, max_hole)
+        self._ck(self._lib.arvx_segment_views(self._h, V, _fp(M), cp, ptrs, W, H, W * 3, pp, n_plates,
+                                              C.byref(sp)))
+        self.V, self.W, self.H = V, W, H
+
+    def segment_views_device(self, M, dev_images_ptr: int, W: int, H: int, campos=None, dev_plates_ptr: int = 0,
+                             plate_count: int = 0, params: Optional[SegmentParams] = None, **kw) -> None:
+        """arvx_segment_views_device: as segment_views, the images (and plates) tightly packed in device
+        memory; no host synchronisation.  Keywords as segment_views."""
+        M = _f32(M).reshape(-1, 12)
+        V = M.shape[0]
+        cp = None
+        if campos is not None:
+            campos = _f32(campos).reshape(V, 3)
+            cp = _fp(campos)
+        if params is None:
+            d = dict(rule=SEGMENT_RANGE, lo=(120, 120, 120), hi=(255, 255, 255), threshold=0, open_radius=0,
+                     close_radius=0, min_area=0, largest=False, max_hole=0)
+            d.update(kw)
+            params = self._segment_params(**d)
+        self._keep = [M, campos]
+        self._ck(self._lib.arvx_segment_views_device(
+            self._h, V, _fp(M), cp, C.c_void_p(dev_images_ptr), W, H,
+            C.c_void_p(dev_plates_ptr) if dev_plates_ptr else None, int(plate_count), C.byref(params)))
+        self.V, self.W, self.H = V, W, H
+
+    def segment_mask(self, view: int) -> np.ndarray:
+        """arvx_segment_download: the final mask of a view, (H, W) uint8, 255 foreground."""
+        self._ck(self._lib.arvx_segment_counts(self._h, int(view), (C.c_int64 * 8)()))  # (refused before any buffer)
+        out = np.empty((self.H, self.W), np.uint8)
+        self._ck(self._lib.arvx_segment_download(self._h, int(view), out.ctypes.data))
+        return out
+
+    def segment_counts(self, view: int) -> np.ndarray:
+        """arvx_segment_counts: foreground pixels after the rule, the closing, the specks and the holes;
+        speck components and pixels removed; hole components and pixels filled."""
+        out = (C.c_int64 * 8)()
+        self._ck(self._lib.arvx_segment_counts(self._h, int(view), out))
+        return np.array(list(out), np.int64)
+
+    def selftest_segment_batch(self, views_per_batch: int) -> None:
+        """Views per labelling batch of segment_views from the next call on (0: the default bound)."""
+        self._ck(self._lib.arvx_selftest_segment_batch(self._h, int(views_per_batch)))
 
     # -- state --
     def reset(self) -> None:

@@ -26,6 +26,7 @@
 #include "carve_stream_kernels.h"  // the one-launch carve: loses by 11-24 %, experiment builds only
 #endif
 #include "views_kernels.h"
+#include "segment_kernels.h"
 #include "state_kernels.h"
 #include "undistort_kernels.h"
 #include "color_kernels.h"
@@ -828,6 +829,7 @@ static int views_common(Ctx *ctx, int V, const float *M, const float *campos, in
     ctx->drop(Event::SetViews);  // colour results belong to the previous views
     ctx->views_ready = false;
     ctx->cameras_ready = false;
+    ctx->seg_ready = false;  // (arvx_segment_views sets it again once its masks are the views)
     if (!same) {
         ctx->free_views();
         ctx->pool_images.release();
@@ -2151,6 +2153,21 @@ static void owned_part(const Ctx *ctx, const std::vector<int> &idx, size_t &lo, 
 
 // ---- colour pass -----------------------------------------------------------------
 
+// n host images of the views' size (BGR, rows of `stride` bytes), tightly packed into dst
+static int images_upload(Ctx *ctx, uint8_t *dst, const uint8_t *const *images, int n, size_t stride) {
+    const size_t rowb = (size_t)ctx->W * 3, img = rowb * ctx->H;
+    bool packed = stride == rowb;  // all of them back to back in host memory: one copy
+    for (int i = 1; i < n && packed; ++i) packed = images[i] == images[i - 1] + img;
+    if (packed) {
+        ARVX_HIP(hipMemcpyAsync(dst, images[0], img * n, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        for (int i = 0; i < n; ++i)
+            ARVX_HIP(hipMemcpy2DAsync(dst + img * i, rowb, images[i], stride, rowb, ctx->H, hipMemcpyHostToDevice,
+                                      ctx->stream));
+    }
+    return ARVX_OK;
+}
+
 int arvx_set_images(arvx_ctx *ctx, const uint8_t *const *images, size_t stride) {
     ARVX_CHECK_CTX(ctx);
     if (!ctx->cameras_ready) return fail(ARVX_ERR_STATE, "arvx_set_views must come first");
@@ -2162,18 +2179,241 @@ int arvx_set_images(arvx_ctx *ctx, const uint8_t *const *images, size_t stride) 
     const size_t img = rowb * ctx->H;
     ctx->drop(Event::SetImages);
     ARVX_HIP(ctx->pool_images.reserve(img * ctx->V));
-    bool packed = stride == rowb;
-    for (int i = 1; i < ctx->V && packed; ++i) packed = images[i] == images[i - 1] + img;
-    if (packed) {
-        ARVX_HIP(hipMemcpyAsync(ctx->images(), images[0], img * ctx->V, hipMemcpyHostToDevice,
-                                ctx->stream));
-    } else {
-        for (int i = 0; i < ctx->V; ++i)
-            ARVX_HIP(hipMemcpy2DAsync(ctx->images() + img * i, rowb, images[i], stride, rowb,
-                                      ctx->H, hipMemcpyHostToDevice, ctx->stream));
-    }
+    ARVX_TRY(images_upload(ctx, ctx->images(), images, ctx->V, stride));
     ARVX_SYNC(ctx);
     ctx->images_ready = true;
+    return ARVX_OK;
+}
+
+// ---- silhouettes from the photographs (segment_kernels.h) -------------------------------------
+
+// pixels whose labels and areas (an int32 each) one batch of views may hold: 1 GiB; a single view
+// larger than that is a batch of its own (W, H <= kMaxImageDim: 2^28 pixels, int32 indices still)
+static constexpr long long kSegBatchPixels = 1ll << 27;
+
+static int segment_refusals(int V, const void *images, int W, int H, const void *plates, int plate_count,
+                            const arvx_segment_params *p) {
+    if (!images || !p) return fail(ARVX_ERR_INVALID, "null argument");
+    // (views_common's ranges, before anything is read through V, W or H)
+    if (V < 1 || V > 4096) return fail(ARVX_ERR_INVALID, "V=%d out of range [1,4096]", V);
+    if (W < 1 || H < 1 || W > arvx::kMaxImageDim || H > arvx::kMaxImageDim)
+        return fail(ARVX_ERR_INVALID, "image size %dx%d out of range", W, H);
+    if (p->rule != ARVX_SEGMENT_RANGE && p->rule != ARVX_SEGMENT_PLATE)
+        return fail(ARVX_ERR_INVALID, "unknown segmentation rule %d", p->rule);
+    for (int c = 0; c < 3; ++c)
+        if (p->lo[c] > p->hi[c]) return fail(ARVX_ERR_INVALID, "lo[%d] > hi[%d]", c, c);
+    if (p->threshold < 0 || p->threshold > 255)
+        return fail(ARVX_ERR_INVALID, "threshold %d outside [0,255]", p->threshold);
+    if (p->rule == ARVX_SEGMENT_PLATE) {
+        if (!plates) return fail(ARVX_ERR_INVALID, "ARVX_SEGMENT_PLATE: null plates");
+        if (plate_count != 1 && plate_count != V)
+            return fail(ARVX_ERR_INVALID, "plate_count %d is neither 1 nor V", plate_count);
+    }
+    if (p->open_radius < 0 || p->close_radius < 0) return fail(ARVX_ERR_INVALID, "negative radius");
+    if (p->min_area < 0) return fail(ARVX_ERR_INVALID, "negative min_area");
+    if (p->flags & ~ARVX_SEGMENT_LARGEST) return fail(ARVX_ERR_INVALID, "unknown flag bits %#x", p->flags);
+    return ARVX_OK;
+}
+
+// One row or column pass of a box erosion (op_and) or dilation of radius r: *cur holds the result, *tmp
+// what is left over.  Radii up to 8 combine their 2 r + 1 shifts in one launch; larger ones double a
+// forward window up to r + 1 pixels, then a backward one over that -- together [-r, r], every partial
+// window starting inside the image, so that "outside" never stands for pixels of the image.
+static int segment_pass(Ctx *ctx, const arvx::BitGrid &g, unsigned long long **cur, unsigned long long **tmp,
+                        int r, bool along_x, int op_and) {
+    r = std::min(r, (along_x ? g.X : g.Y) - 1);  // (a window beyond the image adds the identity)
+    if (r <= 0) return ARVX_OK;
+    const unsigned grid = blocks_for(bit_words(g));
+    const auto step = [&](int n, int s0, int ds) {
+        const int rc = launch(ctx, arvx::seg_combine_kernel, grid, 256, *cur, *tmp, g, op_and, n, along_x ? s0 : 0,
+                              along_x ? ds : 0, along_x ? 0 : s0, along_x ? 0 : ds);
+        std::swap(*cur, *tmp);
+        return rc;
+    };
+    if (r <= 8) return step(2 * r + 1, -r, 1);
+    for (int dir = 1; dir >= -1; dir -= 2) {
+        int len = 1;
+        for (; 2 * len <= r + 1; len *= 2) ARVX_TRY(step(2, 0, dir * len));
+        if (len < r + 1) ARVX_TRY(step(2, 0, dir * (r + 1 - len)));
+    }
+    return ARVX_OK;
+}
+
+static int segment_box(Ctx *ctx, const arvx::BitGrid &g, unsigned long long **cur, unsigned long long **tmp, int r,
+                       int op_and) {
+    ARVX_TRY(segment_pass(ctx, g, cur, tmp, r, true, op_and));
+    return segment_pass(ctx, g, cur, tmp, r, false, op_and);
+}
+
+// The components of one kind (1 foreground, 2 background) of the views v0 .. v0 + gb.Z - 1 of `plane`:
+// labels, then areas
+static int segment_label(Ctx *ctx, const arvx::BitGrid &gb, const unsigned long long *plane, int which, int *L,
+                         unsigned *area) {
+    const size_t n = (size_t)gb.X * gb.Y * gb.Z;
+    const unsigned lanes = blocks_for(bit_words(gb) * 64);
+    ARVX_TRY(launch(ctx, arvx::seg_init_kernel, lanes, 256, plane, gb, which, L));
+    ARVX_TRY(launch(ctx, arvx::seg_link_kernel, lanes, 256, plane, gb, which, L));
+    ARVX_TRY(launch(ctx, arvx::seg_roots_kernel, blocks_for(n), 256, L, (int)n));
+    ARVX_HIP(hipMemsetAsync(area, 0, n * sizeof(unsigned), ctx->stream));
+    return launch(ctx, arvx::seg_area_kernel, blocks_for(n, arvx::kSegAreaBlock), arvx::kSegAreaBlock, L, (int)n, gb.X,
+                  gb.Y, area);
+}
+
+// The stage behind both entry points: the images are in pool_images, views_common has run.
+static int segment_run(Ctx *ctx, const uint8_t *d_plates, int plate_count, const arvx_segment_params &p) {
+    const int V = ctx->V, W = ctx->W, H = ctx->H;
+    const arvx::BitGrid g{W, H, V, (W + 63) / 64};
+    const size_t words = bit_words(g), view_words = (size_t)g.XW * H;
+    ARVX_HIP(ctx->pool_seg_planes.reserve(2 * words * sizeof(unsigned long long)));
+    ARVX_HIP(ctx->pool_seg_counts.reserve((size_t)V * 8 * sizeof(unsigned long long)));
+    unsigned long long *plane0 = (unsigned long long *)ctx->pool_seg_planes.p;
+    unsigned long long *cur = plane0, *tmp = plane0 + words;
+    unsigned long long *counts = (unsigned long long *)ctx->pool_seg_counts.p;
+    ARVX_HIP(hipMemsetAsync(counts, 0, (size_t)V * 8 * sizeof(unsigned long long), ctx->stream));
+    const dim3 count_grid(blocks_for(view_words), V);
+
+    // 1. the rule
+    arvx::SegRule rule{p.rule, 0u, 0u, p.threshold};
+    for (int c = 0; c < 3; ++c) {
+        rule.lo |= (uint32_t)p.lo[c] << (8 * c);
+        rule.hi |= (uint32_t)p.hi[c] << (8 * c);
+    }
+    ARVX_TRY(launch(ctx, arvx::seg_rule_kernel, blocks_for(words * 16), 256, ctx->images(), d_plates,
+                    plate_count == 1 ? (size_t)0 : (size_t)W * H * 3, g, rule, cur));
+    ARVX_TRY(launch(ctx, arvx::seg_count_kernel, count_grid, 256, cur, g, counts, 0));
+    // 2. opening, 3. closing
+    ARVX_TRY(segment_box(ctx, g, &cur, &tmp, p.open_radius, 1));
+    ARVX_TRY(segment_box(ctx, g, &cur, &tmp, p.open_radius, 0));
+    ARVX_TRY(segment_box(ctx, g, &cur, &tmp, p.close_radius, 0));
+    ARVX_TRY(segment_box(ctx, g, &cur, &tmp, p.close_radius, 1));
+    ARVX_TRY(launch(ctx, arvx::seg_count_kernel, count_grid, 256, cur, g, counts, 1));
+
+    // 4. specks and 5. holes: each labels its own kind of pixel, batch by batch -- the holes on the plane
+    // the specks left, so that background a removed speck joined is one component
+    const int largest = (p.flags & ARVX_SEGMENT_LARGEST) ? 1 : 0;
+    const long long bound = std::max(1ll, kSegBatchPixels / ((long long)W * H));
+    const int per_batch = (int)std::min<long long>(ctx->seg_batch > 0 ? std::min<long long>(ctx->seg_batch, bound) : bound, V);
+    const bool specks = p.min_area > 0 || largest, holes = p.max_hole != 0;
+    int *L = nullptr;
+    unsigned *area = nullptr;
+    unsigned long long *best = nullptr;
+    if (specks || holes) {
+        const size_t n = (size_t)per_batch * W * H;
+        ARVX_HIP(ctx->pool_seg_label.reserve(2 * n * sizeof(int) + (size_t)per_batch * sizeof(unsigned long long)));
+        best = (unsigned long long *)ctx->pool_seg_label.p;  // (first: 8-byte aligned whatever n is)
+        L = (int *)(best + per_batch);
+        area = (unsigned *)(L + n);
+    }
+    for (int step = 4; step <= 5; ++step) {
+        if (step == 4 ? specks : holes)
+            for (int v0 = 0; v0 < V; v0 += per_batch) {
+                const arvx::BitGrid gb{W, H, std::min(per_batch, V - v0), g.XW};
+                unsigned long long *plane = cur + (size_t)v0 * view_words;
+                const size_t n = (size_t)W * H * gb.Z;
+                const unsigned lanes = blocks_for(bit_words(gb) * 64);
+                ARVX_TRY(segment_label(ctx, gb, plane, step == 4 ? 1 : 2, L, area));
+                if (step == 4) {
+                    if (largest) {
+                        ARVX_HIP(hipMemsetAsync(best, 0, (size_t)gb.Z * sizeof(unsigned long long), ctx->stream));
+                        ARVX_TRY(launch(ctx, arvx::seg_best_kernel, blocks_for(n), 256, L, area, (int)n, W * H,
+                                        (long long)p.min_area, best));
+                    }
+                    ARVX_TRY(launch(ctx, arvx::seg_specks_kernel, lanes, 256, plane, gb, L, area,
+                                    (long long)p.min_area, largest, best, counts + 8 * (size_t)v0));
+                } else {
+                    ARVX_TRY(launch(ctx, arvx::seg_holes_kernel, lanes, 256, plane, gb, L, area,
+                                    (long long)p.max_hole, counts + 8 * (size_t)v0));
+                }
+            }
+        ARVX_TRY(launch(ctx, arvx::seg_count_kernel, count_grid, 256, cur, g, counts, step - 2));
+    }
+    ctx->seg_final = cur == plane0 ? 0 : 1;
+
+    // the views: the flat background plane, then whole tables from it
+    ARVX_TRY(launch(ctx, arvx::seg_publish_kernel, dim3(blocks_for((size_t)ctx->bgWords), V), 256, cur, g,
+                    ctx->bg(), ctx->bgWords));
+    ARVX_TRY(views_windows(ctx, false));
+    ARVX_TRY(views_tables_from_bits(ctx));
+    ctx->views_ready = true;
+    ctx->cameras_ready = true;
+    ctx->images_ready = true;
+    ctx->seg_ready = true;
+    return ARVX_OK;
+}
+
+int arvx_segment_views(arvx_ctx *ctx, int V, const float *M, const float *campos, const uint8_t *const *images,
+                       int W, int H, size_t stride, const uint8_t *const *plates, int plate_count,
+                       const arvx_segment_params *params) {
+    ARVX_CHECK_CTX(ctx);
+    ARVX_TRY(segment_refusals(V, images, W, H, plates, plate_count, params));
+    const bool plate = params->rule == ARVX_SEGMENT_PLATE;
+    if (W >= 1 && stride < (size_t)W * 3) return fail(ARVX_ERR_INVALID, "stride %zu < W*3", stride);
+    for (int i = 0; i < V; ++i)
+        if (!images[i]) return fail(ARVX_ERR_INVALID, "null image %d", i);
+    for (int i = 0; plate && i < plate_count; ++i)
+        if (!plates[i]) return fail(ARVX_ERR_INVALID, "null plate %d", i);
+    ARVX_TRY(views_common(ctx, V, M, campos, W, H, 1));
+    ctx->drop(Event::SetImages);
+    const size_t rowb = (size_t)W * 3, img = rowb * H;
+    ARVX_HIP(ctx->pool_images.reserve(img * V));
+    ARVX_TRY(images_upload(ctx, ctx->images(), images, V, stride));
+    if (plate) {
+        ARVX_HIP(ctx->pool_seg_plates.reserve(img * plate_count));
+        ARVX_TRY(images_upload(ctx, (uint8_t *)ctx->pool_seg_plates.p, plates, plate_count, stride));
+    }
+    ARVX_TRY(segment_run(ctx, plate ? (const uint8_t *)ctx->pool_seg_plates.p : nullptr, plate_count, *params));
+    ARVX_SYNC(ctx);  // host buffers may go away
+    return ARVX_OK;
+}
+
+int arvx_segment_views_device(arvx_ctx *ctx, int V, const float *M, const float *campos, const void *dev_images,
+                              int W, int H, const void *dev_plates, int plate_count,
+                              const arvx_segment_params *params) {
+    ARVX_CHECK_CTX(ctx);
+    ARVX_TRY(segment_refusals(V, dev_images, W, H, dev_plates, plate_count, params));
+    ARVX_TRY(views_common(ctx, V, M, campos, W, H, 1));
+    ctx->drop(Event::SetImages);
+    const size_t bytes = (size_t)W * H * 3 * V;
+    ARVX_HIP(ctx->pool_images.reserve(bytes));
+    ARVX_HIP(hipMemcpyAsync(ctx->images(), dev_images, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return segment_run(ctx, params->rule == ARVX_SEGMENT_PLATE ? (const uint8_t *)dev_plates : nullptr, plate_count,
+                       *params);
+}
+
+static int segment_result(Ctx *ctx, int view, const void *out) {
+    if (!ctx->seg_ready || !ctx->views_ready)
+        return fail(ARVX_ERR_STATE, "the views are not those of an arvx_segment_views call");
+    if (view < 0 || view >= ctx->V) return fail(ARVX_ERR_INVALID, "view %d outside [0,%d)", view, ctx->V);
+    if (!out) return fail(ARVX_ERR_INVALID, "null argument");
+    return ARVX_OK;
+}
+
+int arvx_segment_download(arvx_ctx *ctx, int view, uint8_t *mask) {
+    ARVX_CHECK_CTX(ctx);
+    ARVX_TRY(segment_result(ctx, view, mask));
+    const arvx::BitGrid g{ctx->W, ctx->H, ctx->V, (ctx->W + 63) / 64};
+    const size_t npix = (size_t)ctx->W * ctx->H;
+    ARVX_HIP(ctx->pool_seg_bytes.reserve(npix));
+    const unsigned long long *plane = (const unsigned long long *)ctx->pool_seg_planes.p + ctx->seg_final * bit_words(g);
+    ARVX_TRY(launch(ctx, arvx::seg_bytes_kernel, blocks_for(npix), 256, plane, g, view, (uint8_t *)ctx->pool_seg_bytes.p));
+    ARVX_HIP(hipMemcpyAsync(mask, ctx->pool_seg_bytes.p, npix, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+int arvx_segment_counts(arvx_ctx *ctx, int view, int64_t out[8]) {
+    ARVX_CHECK_CTX(ctx);
+    ARVX_TRY(segment_result(ctx, view, out));
+    ARVX_HIP(hipMemcpyAsync(out, (const unsigned long long *)ctx->pool_seg_counts.p + 8 * (size_t)view,
+                            8 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    return ARVX_OK;
+}
+
+int arvx_selftest_segment_batch(arvx_ctx *ctx, int views_per_batch) {
+    ARVX_CHECK_CTX(ctx);
+    if (views_per_batch < 0) return fail(ARVX_ERR_INVALID, "views_per_batch %d (0: the default bound)", views_per_batch);
+    ctx->seg_batch = views_per_batch;
     return ARVX_OK;
 }
 

@@ -241,6 +241,16 @@ struct Ctx {
     std::vector<uint32_t> h_win;      // what the device holds in pool_win: the last derivation's
     DevPool pool_win{DevPool::Exact};
 
+    // arvx_segment_views (segment_kernels.h): two work planes of V x H rows of whole 64-bit words (the
+    // final masks are plane seg_final; read only while seg_ready is set: the views are still the ones the
+    // call derived), eight count words per view, the labels and areas of one batch of views (an int32
+    // each per pixel) before the batch's "largest" words, the plates of the host form, a view as bytes
+    DevPool pool_seg_planes{DevPool::Exact}, pool_seg_counts{DevPool::Exact}, pool_seg_label{DevPool::Exact},
+        pool_seg_plates{DevPool::Exact}, pool_seg_bytes{DevPool::Exact};
+    bool seg_ready = false;
+    int seg_final = 0;
+    int seg_batch = 0;  // arvx_selftest_segment_batch (0: the bound)
+
     // colour pass
     DevPool pool_images{DevPool::Exact};  // V x H x W x 3, BGR
     uint8_t *images() const { return (uint8_t *)pool_images.p; }

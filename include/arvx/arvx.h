@@ -211,6 +211,79 @@ int arvx_undistort_device(arvx_ctx *ctx, int V, const void *dev_src, int W, int 
  * of `stride` bytes, same W/H as the masks. */
 int arvx_set_images(arvx_ctx *ctx, const uint8_t *const *images, size_t stride);
 
+/* ---- silhouettes from the photographs (extension beyond the reference's -c=4) -------------------
+ * arvx_segment_views turns V BGR photographs into the context's views -- the background bit planes
+ * and summed-area tables arvx_set_views would derive from the masks defined below -- and leaves the
+ * photographs resident as arvx_set_images would.  Everything is integer arithmetic, so a restatement
+ * (tests/segment.py) is matched bit for bit.
+ *
+ * Definition.  Per view, on W x H pixels, flat pixel index i = y * W + x, the steps in this order:
+ *  1. Rule: the raw foreground.
+ *     ARVX_SEGMENT_RANGE  a pixel is background iff lo[c] <= p[c] <= hi[c] in all three channels (lo, hi
+ *                         in B, G, R order); foreground is the complement: the reference's
+ *                         ~inRange(lo, hi), src/Segmentation.h:10-11, whose constants are lo = 120,
+ *                         hi = 255 in every channel.
+ *     ARVX_SEGMENT_PLATE  a pixel is foreground iff max over c of |p[c] - plate[c]| > threshold, against
+ *                         a background plate of the same size and stride: plate_count = 1 plate for all
+ *                         views, or V, one per view.  threshold in [0, 255].
+ *  2. Opening by a square of side 2 * open_radius + 1: erosion, then dilation.  The erosion treats
+ *     pixels outside the image as foreground, the dilation as background.  Radius 0 skips the step; a
+ *     radius of max(W, H) and more is legal.
+ *  3. Closing by a square of side 2 * close_radius + 1: dilation, then erosion, borders as in step 2.
+ *  4. Specks.  The foreground's components under 8-connectivity; a component's label is its least
+ *     flat pixel index.  min_area > 0: components of fewer than min_area pixels become background.
+ *     ARVX_SEGMENT_LARGEST: all but the largest surviving component become background, ties going
+ *     to the smaller label.
+ *  5. Holes, on the result of step 4.  The background's components under 4-connectivity (the pair
+ *     that is consistent with 8 for the foreground: a pocket that reaches the outside only through a
+ *     diagonal gap is a hole); a component with no pixel on the image border and an area of at most
+ *     max_hole becomes foreground.  max_hole < 0: any area; max_hole == 0: the step is off.
+ * The final mask gives background bit i = 1 iff pixel i is background, in the layout arvx_set_views
+ * derives: bit index y * W + x, rows not word-aligned, padding bits and the word behind the pixels 0.
+ *
+ * Contract of both forms: in every later observation the context is as if arvx_set_views (with the
+ * final masks, one channel, 255 = foreground) and then arvx_set_images (with these photographs) had
+ * been called -- what those two calls drop is dropped, matrices that did not change keep the cached
+ * rectangles, and the tables are written whole.  The host form takes V host pointers (H rows of
+ * `stride` bytes each, plates too) and returns when the host buffers may go; the _device form takes
+ * tightly packed device images (and plates) and does not synchronise with the host.
+ * Refusals (ARVX_ERR_INVALID, nothing changed): null pointers (plates only under PLATE), V, W, H
+ * outside arvx_set_views' ranges, an unknown rule, lo[c] > hi[c], a threshold outside [0, 255] (under
+ * either rule), a plate_count that is neither 1 nor V under PLATE, negative radii, a negative
+ * min_area, unknown flag bits, a stride below 3 * W.
+ *
+ * arvx_segment_download: the final mask of a view, W x H bytes, 255 foreground, 0 background.
+ * arvx_segment_counts: out[0..3] foreground pixels after steps 1, 3, 4 and 5; out[4], out[5] the speck
+ * components and pixels step 4 removed; out[6], out[7] the hole components and pixels step 5 filled.
+ * Both answer ARVX_ERR_STATE before the first call and once a later arvx_set_views[_device] has
+ * replaced the views; a view outside [0, V) or a null pointer: ARVX_ERR_INVALID.
+ *
+ * Memory: two work planes of a bit per pixel (rows padded to 64), and for steps 4 and 5 a label and
+ * an area, int32 each, per pixel of one batch of views -- the views go through in batches of at most
+ * 2^27 pixels (1 GiB), at least one view.  arvx_selftest_segment_batch: views per batch from the next
+ * call on (0: that bound; larger values are clipped to it); batches never change the result. */
+#define ARVX_SEGMENT_RANGE 0
+#define ARVX_SEGMENT_PLATE 1
+#define ARVX_SEGMENT_LARGEST 1u /* flags of arvx_segment_params */
+typedef struct arvx_segment_params {
+    int32_t rule;         /* ARVX_SEGMENT_RANGE or ARVX_SEGMENT_PLATE */
+    uint8_t lo[3], hi[3]; /* RANGE: the background's range, B, G, R */
+    uint8_t reserved[2];
+    int32_t threshold;    /* PLATE */
+    int32_t open_radius, close_radius;
+    uint32_t flags;
+    int64_t min_area, max_hole;
+} arvx_segment_params;
+int arvx_segment_views(arvx_ctx *ctx, int V, const float *M, const float *campos,
+                       const uint8_t *const *images, int W, int H, size_t stride,
+                       const uint8_t *const *plates, int plate_count, const arvx_segment_params *params);
+int arvx_segment_views_device(arvx_ctx *ctx, int V, const float *M, const float *campos,
+                              const void *dev_images, int W, int H, const void *dev_plates,
+                              int plate_count, const arvx_segment_params *params);
+int arvx_segment_download(arvx_ctx *ctx, int view, uint8_t *mask);
+int arvx_segment_counts(arvx_ctx *ctx, int view, int64_t out[8]);
+int arvx_selftest_segment_batch(arvx_ctx *ctx, int views_per_batch);
+
 /* ---- state ------------------------------------------------------------ */
 
 /* All voxels occupied, none seen: the state a fresh Model has. */

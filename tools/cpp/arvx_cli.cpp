@@ -13,12 +13,15 @@
 //                                top three rows of estimatePoseFromImage(...).inv()
 //                                (src/VoxelCarving.cpp:25-26)
 //   -scene=<file>                or all of it in one binary file (tests/cpp/test_host.cpp)
+//   -segment=range|plate         the masks from the images, on the device (arvx_segment_views):
+//                                -masks is then not needed
 //   -calibration=<yml>           the reference's calibration file; its camera matrix is used
 //                                (src/PoseEstimation.h:11-16), the distortion coefficients only
 //                                with -undistort=true: then the inputs are RAW images and
 //                                arvx_undistort remaps them on the device (see arvx.h)
 // -c=1..4 (board creation, camera calibration, live pose estimation, segmentation) are
-// OpenCV/aruco programs around the path and are not provided.
+// OpenCV/aruco programs around the path and are not provided; the range rule of -c=4
+// (src/Segmentation.h:10-11) runs inside -c=5 / -c=6 as -segment=range.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -31,6 +34,7 @@
 #include <vector>
 
 #include "arvx/calibration.hpp"
+#include "arvx/segmentation.hpp"
 #include "bench6.hpp"
 
 namespace fs = std::filesystem;
@@ -255,7 +259,10 @@ int main(int argc, char *argv[]) {
         {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
         {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"},
         {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"renderMesh", "false"},
-        {"meshColor", ""}, {"meshForeground", "false"}, {"texture", "0"}, {"atlasWidth", "4096"}};
+        {"meshColor", ""}, {"meshForeground", "false"}, {"texture", "0"}, {"atlasWidth", "4096"},
+        {"segment", ""}, {"segLo", "120,120,120"}, {"segHi", "255,255,255"}, {"plates", ""}, {"segThreshold", "30"},
+        {"segOpen", "0"}, {"segClose", "0"}, {"segMinArea", "0"}, {"segLargest", "false"}, {"segMaxHole", "0"},
+        {"writeMasks", ""}};
     Args parser(argc, argv, defaults);
     if (argc < 2) {
         std::cout << about
@@ -302,7 +309,16 @@ int main(int argc, char *argv[]) {
                      "    edges and shows it largest; written beside -outFile as <stem>.obj, .mtl and .ppm;\n"
                      "    with -render and -renderMesh=true the renders draw the texture; -meshForeground applies;\n"
                      "    not together with -meshColor),\n"
-                     "  -atlasWidth=AW (texels per row of the texture atlas, default 4096)\n";
+                     "  -atlasWidth=AW (texels per row of the texture atlas, default 4096),\n"
+                     "  -segment=range|plate (the masks from the images, on the device; -masks is not needed:\n"
+                     "    range: background where -segLo=B,G,R <= pixel <= -segHi=B,G,R, defaults 120,120,120 and\n"
+                     "    255,255,255, the reference's -c=4; plate: foreground where a channel differs by more than\n"
+                     "    -segThreshold=T, default 30, from the plate in -plates=<dir>, one file or one per image),\n"
+                     "  -segOpen=R -segClose=R (the masks opened, then closed, by squares of side 2 R + 1),\n"
+                     "  -segMinArea=N (foreground components of fewer than N pixels go, 8-connectivity),\n"
+                     "  -segLargest=true (only the largest foreground component stays),\n"
+                     "  -segMaxHole=N (enclosed background of at most N pixels is filled; -1: of any size),\n"
+                     "  -writeMasks=DIR (with -segment: the final masks as DIR/maskNNNN.pgm)\n";
         return 0;
     }
     const int choose = parser.i("c");
@@ -376,14 +392,22 @@ int main(int argc, char *argv[]) {
         }
         std::cout << "LOG - " << tag << ": images read." << std::endl;
         const std::string masks_dir = parser.str("masks");
-        if (masks_dir.empty()) {
+        if (masks_dir.empty() && !parser.str("segment").empty()) {
+            // -segment: the masks come from the images (below)
+            if (in.images.empty()) {
+                std::cerr << "No readable PPM/PGM files in --images" << std::endl;
+                return 1;
+            }
+            in.masks.resize(in.images.size());
+        } else if (masks_dir.empty()) {
             std::cerr << "You need to define a image masks path (--masks)" << std::endl;
             return 1;
         }
-        for (const std::string &name : glob_sorted(masks_dir)) {
-            Picture p;
-            if (read_pnm(name, p, true)) in.masks.push_back(std::move(p));
-        }
+        if (!masks_dir.empty())
+            for (const std::string &name : glob_sorted(masks_dir)) {
+                Picture p;
+                if (read_pnm(name, p, true)) in.masks.push_back(std::move(p));
+            }
         std::cout << "LOG - " << tag << ": masks read." << std::endl;
         if (in.images.size() != in.masks.size()) {
             std::cerr << "Number of images doesn't match number of masks." << std::endl;
@@ -463,13 +487,87 @@ int main(int argc, char *argv[]) {
         std::cout << "LOG - " << tag << ": undistorted masks and images." << std::endl;
     }
     const arvx::Vec3f modelTranslation(parser.f("dx"), parser.f("dy"), parser.f("dz"));
+    // -segment (an extension beyond the reference's -c=4): the masks from the images, on the device
+    arvx::SegmentedMasks segmented;
+    std::vector<Picture> plate_pictures;
+    const auto segment = [&](arvx::Model &m) {
+        const std::string kind = parser.str("segment");
+        if (kind.empty()) return true;
+        arvx::SegmentParams sp;
+        if (kind == "plate") sp.rule = ARVX_SEGMENT_PLATE;
+        else if (kind != "range") {
+            std::cerr << "Invalid segment argument (range or plate)." << std::endl;
+            return false;
+        }
+        int lo[3], hi[3];
+        if (std::sscanf(parser.str("segLo").c_str(), "%d,%d,%d", lo, lo + 1, lo + 2) != 3 ||
+            std::sscanf(parser.str("segHi").c_str(), "%d,%d,%d", hi, hi + 1, hi + 2) != 3) {
+            std::cerr << "Invalid segLo / segHi argument (B,G,R)." << std::endl;
+            return false;
+        }
+        for (int c = 0; c < 3; ++c) {
+            if (lo[c] < 0 || hi[c] > 255 || lo[c] > hi[c]) {
+                std::cerr << "Invalid segLo / segHi argument (0 <= lo <= hi <= 255)." << std::endl;
+                return false;
+            }
+            sp.lo[c] = (uint8_t)lo[c];
+            sp.hi[c] = (uint8_t)hi[c];
+        }
+        sp.threshold = parser.i("segThreshold");
+        sp.open_radius = parser.i("segOpen");
+        sp.close_radius = parser.i("segClose");
+        sp.min_area = parser.i("segMinArea");
+        sp.max_hole = parser.i("segMaxHole");
+        sp.flags = parser.b("segLargest") ? ARVX_SEGMENT_LARGEST : 0u;
+        std::vector<arvx::Image> plates;
+        if (sp.rule == ARVX_SEGMENT_PLATE) {
+            for (const std::string &name : glob_sorted(parser.str("plates"))) {
+                Picture p;
+                if (read_pnm(name, p, true)) plate_pictures.push_back(std::move(p));
+            }
+            if (plate_pictures.empty()) {
+                std::cerr << "You need to define a background plates path (--plates)" << std::endl;
+                return false;
+            }
+            for (const Picture &p : plate_pictures) plates.push_back({p.px.data(), p.w, p.h, p.c, (size_t)p.w * p.c});
+        }
+        arvx::segmentViews(m, in.views, sp, plates, segmented);
+        for (size_t i = 0; i < segmented.counts.size(); ++i) {
+            const auto &n = segmented.counts[i];
+            std::cout << "LOG - SEG: view " << i << " foreground " << n[0] << " cleaned " << n[1] << " specks " << n[2]
+                      << " holes " << n[3] << " (specks removed " << n[4] << ", " << n[5] << " px; holes filled "
+                      << n[6] << ", " << n[7] << " px)" << std::endl;
+        }
+        const std::string dir = parser.str("writeMasks");
+        if (!dir.empty()) {
+            fs::create_directories(dir);
+            for (size_t i = 0; i < segmented.masks.size(); ++i) {
+                char name[32];
+                std::snprintf(name, sizeof name, "mask%04d.pgm", (int)i);
+                std::ofstream f((fs::path(dir) / name).string(), std::ios::binary);
+                f << "P5\n" << segmented.width << " " << segmented.height << "\n255\n";
+                f.write((const char *)segmented.masks[i].data(), (std::streamsize)segmented.masks[i].size());
+                if (!f) {
+                    std::cerr << "Could not write " << name << " (--writeMasks)" << std::endl;
+                    return false;
+                }
+            }
+        }
+        std::cout << "LOG - SEG: masks segmented." << std::endl;
+        return true;
+    };
     try {
         if (choose == 6) {
+            if (!parser.str("segment").empty()) {
+                arvx::Model scratch(8, 8, 8, 1.f);  // (a context to segment on: the table makes its own models)
+                if (!segment(scratch)) return 1;
+            }
             bench6::run(in.intr, in.views, parser.f("scale"), modelTranslation);
             return 0;
         }
         // 100, 100, 100, 0.0028 ~ Caruco
         arvx::Model model(x, y, z, size);
+        if (!segment(model)) return 1;
         switch (parser.i("carve")) {
             case 1:
                 // -misses=K (an extension beyond the reference): the vote carve in place of carve()
