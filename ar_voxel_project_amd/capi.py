@@ -36,6 +36,7 @@ PATH_FUSED = 16
 PATH_BRUTE_FORCE = 32
 PATH_STREAM = 64
 PATH_RECT_BLOCKS = 128
+PATH_PIXEL_TABLE = 256
 # bits of Context.last_fast_carve_path()["bits"] (ARVX_FLOOD_*)
 FLOOD_PREPASS = 1
 FLOOD_FRESH = 2
@@ -109,6 +110,7 @@ SYMBOLS = [
     "arvx_selftest_divide",
     "arvx_selftest_round",
     "arvx_ctx_set_rect_cache_limit", "arvx_selftest_rect_cache",
+    "arvx_ctx_set_pixel_cache_limit", "arvx_pixel_cache_views", "arvx_selftest_pixel_cache",
     "arvx_ctx_set_view_window", "arvx_view_window", "arvx_view_window_host",
     "arvx_selftest_fill_view_tables", "arvx_selftest_view_table_raw",
     "arvx_segment_views", "arvx_segment_views_device", "arvx_segment_download", "arvx_segment_counts",
@@ -238,6 +240,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if hasattr(lib, "arvx_selftest_rect_cache") or not ab_build:
         lib.arvx_ctx_set_rect_cache_limit.argtypes = [p, C.c_uint64]
         lib.arvx_selftest_rect_cache.argtypes = [p, C.POINTER(C.c_int64)]
+    if hasattr(lib, "arvx_ctx_set_pixel_cache_limit") or not ab_build:
+        lib.arvx_ctx_set_pixel_cache_limit.argtypes = [p, C.c_uint64]
+    if hasattr(lib, "arvx_pixel_cache_views") or not ab_build:
+        lib.arvx_pixel_cache_views.argtypes = [p, C.POINTER(C.c_uint64), C.c_int]
+    if hasattr(lib, "arvx_selftest_pixel_cache") or not ab_build:
+        lib.arvx_selftest_pixel_cache.argtypes = [p, C.POINTER(C.c_int64)]
     if hasattr(lib, "arvx_view_window") or not ab_build:
         lib.arvx_ctx_set_view_window.argtypes = [p, C.c_int]
         lib.arvx_view_window.argtypes = [p, C.c_int, C.POINTER(C.c_int)]
@@ -1323,6 +1331,26 @@ class Context:
         """Bytes the context's table of cached rectangles may take (0: none).  Releases the table;
         it is built again, under the new limit, by the carves that follow."""
         self._ck(self._lib.arvx_ctx_set_rect_cache_limit(self._h, nbytes))
+
+    def set_pixel_cache_limit(self, nbytes: int) -> None:
+        """Bytes the context's table of cached pixels may take (0: none; default 6 GiB).  Releases
+        the table; it is built again, under the new limit, with or right after the block table."""
+        self._ck(self._lib.arvx_ctx_set_pixel_cache_limit(self._h, nbytes))
+
+    def pixel_cache_views(self, V: int) -> Sequence[bool]:
+        """Per view of the context: its pixels are read from the table of cached pixels (all False
+        while the context holds no such table)."""
+        nw = (V + 63) // 64
+        words = (C.c_uint64 * nw)()
+        self._ck(self._lib.arvx_pixel_cache_views(self._h, words, nw))
+        return [bool((int(words[v // 64]) >> (v % 64)) & 1) for v in range(V)]
+
+    def selftest_pixel_cache(self) -> int:
+        """Bytes of the table of cached pixels that differ from a recomputation: must be 0
+        (-1: the context holds no table)."""
+        n = C.c_int64(-2)
+        self._ck(self._lib.arvx_selftest_pixel_cache(self._h, C.byref(n)))
+        return int(n.value)
 
     def set_view_window(self, on: bool) -> None:
         """Whether set_views writes only the part of each summed-area table that this context's

@@ -21,6 +21,7 @@
 
 #include "arvx_ctx.h"
 #include "carve_kernels.h"
+#include "pixel_cache_kernels.h"
 #include "rect_cache_kernels.h"
 #ifdef ARVX_EXPERIMENTS
 #include "carve_stream_kernels.h"  // the one-launch carve: loses by 11-24 %, experiment builds only
@@ -1705,6 +1706,52 @@ static void rect_params(const Ctx *ctx, arvx::CarveParams &p) {
     p.rcDB = rb.db;
 }
 
+// lanes of the table of cached pixels (16 bytes each), and the words of its per-view "does not fit"
+// mask behind them (one more than the views need: the kernel reads the word after a chunk's)
+static size_t pixel_lanes(const Ctx *ctx, const arvx::CarveParams &p) {
+    return (arvx::rec_count(p) << 6) * (size_t)ctx->V;
+}
+static size_t pixel_miss_words(const Ctx *ctx) { return (size_t)(ctx->V + 63) / 64 + 1; }
+static unsigned pixel_grid(size_t n) { return (unsigned)std::min<size_t>((n + 255) / 256, (size_t)1 << 20); }
+
+// The table of pixels, for a carve that reads the block table (p.rcBlk stands): built once per set
+// of cameras and grouping, under its own limit; handed to p once it stands.  Like the block table's,
+// the build ends with a synchronisation, after which the host knows which views fit.
+static int pixel_cache_prepare(Ctx *ctx, arvx::CarveParams &p) {
+    if (!ctx->pix_limit) return ARVX_OK;
+    if (ctx->pix_state != Ctx::Rect::None && ctx->pix_assoc != ctx->assoc) ctx->pix_state = Ctx::Rect::None;
+    if (ctx->pix_state == Ctx::Rect::None) {
+        ctx->pix_state = Ctx::Rect::Refused;
+        ctx->pix_assoc = ctx->assoc;
+        const size_t n = pixel_lanes(ctx, p), nw = pixel_miss_words(ctx);
+        const size_t bytes = n * sizeof(uint4) + nw * sizeof(unsigned long long);
+        if (bytes > ctx->pix_limit) {
+            ctx->pool_pix.release();  // (one of an earlier, smaller set of views)
+            return ARVX_OK;
+        }
+        if (ctx->pool_pix.reserve(bytes) != hipSuccess) {  // (no room on the device: no table, no error)
+            (void)hipGetLastError();
+            return ARVX_OK;
+        }
+        uint4 *tab = (uint4 *)ctx->pool_pix.p;
+        unsigned long long *miss = (unsigned long long *)(tab + n);
+        ARVX_HIP(hipMemsetAsync(miss, 0, nw * sizeof *miss, ctx->stream));
+        ARVX_TRY(by_assoc(ctx, [&](auto left) {
+            return launch(ctx, arvx::pixel_cache_kernel<decltype(left)::value, false>, pixel_grid(n), 256, p, tab,
+                          n, miss, nullptr);
+        }));
+        ctx->pix_miss.assign(nw, 0ull);
+        ARVX_HIP(hipMemcpyAsync(ctx->pix_miss.data(), miss, nw * sizeof *miss, hipMemcpyDeviceToHost, ctx->stream));
+        ARVX_SYNC(ctx);
+        ctx->pix_state = Ctx::Rect::Built;
+    }
+    if (ctx->pix_state == Ctx::Rect::Built) {
+        p.pxTab = (const uint4 *)ctx->pool_pix.p;
+        p.pxMiss = (const unsigned long long *)(p.pxTab + pixel_lanes(ctx, p));
+    }
+    return ARVX_OK;
+}
+
 // A carve of a fresh model that runs the dense classify kernel and the unshared block-mapped exact
 // kernel on the context's own records: counts it, builds the table at the second one in a row
 // under the same views, and hands p the table once it stands.  The build ends with a synchronisation -- once per set of
@@ -1734,8 +1781,9 @@ static int rect_cache_prepare(Ctx *ctx, arvx::CarveParams &p) {
         }
         ctx->rect_state = Ctx::Rect::Built;
     }
-    if (ctx->rect_state == Ctx::Rect::Built) p.rcBlk = (const uint32_t *)ctx->pool_rect.p;
-    return ARVX_OK;
+    if (ctx->rect_state != Ctx::Rect::Built) return ARVX_OK;
+    p.rcBlk = (const uint32_t *)ctx->pool_rect.p;
+    return pixel_cache_prepare(ctx, p);
 }
 
 // `fresh`: the model is all-occupied/unseen and exists only as that flag: nothing is read,
@@ -1890,6 +1938,13 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
     if (blocks && force_split) p.flags |= 8u | 64u;
     static const bool no_block_tests = experiment_flag("ARVX_NO_BLOCK_TESTS");
     if (no_block_tests) p.flags |= 32u;
+    // (experiment builds: the block-mapped exact kernel counts its items, listed views, (item, view)
+    // pairs and projected blocks into the statistics words -- read with arvx_get_stats)
+    static const bool count_blocks = experiment_flag("ARVX_COUNT_BLOCKS");
+    if (count_blocks && blocks) {
+        p.flags |= 256u;
+        ARVX_HIP(hipMemsetAsync(ctx->stats(), 0, 64, ctx->stream));
+    }
     if (split) {
         // coarse tiles: classified, and the decided ones written as constant records, one
         // workgroup each
@@ -1935,6 +1990,8 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         // for callers whose masks leave most blocks of an item to be projected (ARVX_CARVE_FILTER)
         const bool filter = (flags & ARVX_CARVE_FILTER) != 0;
 #endif
+        // ... and the pixels from theirs, where that stands too
+        const bool pixels = cached && p.pxTab && !no_block_tests;
         // the exact kernel's instantiation: that of the first line whose condition holds
         void (*exact)(arvx::CarveParams) =
 #ifdef ARVX_EXPERIMENTS
@@ -1946,7 +2003,9 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
             : blocks && filter                    ? arvx::carve_exact_blocks_kernel<false, false, false, true>
             :
 #endif
-            cached && left                ? arvx::carve_exact_blocks_kernel<true, false, true, false, true>
+            pixels && left                ? arvx::carve_exact_blocks_kernel<true, false, true, false, true, true>
+            : pixels                      ? arvx::carve_exact_blocks_kernel<false, false, true, false, true, true>
+            : cached && left              ? arvx::carve_exact_blocks_kernel<true, false, true, false, true>
             : cached                      ? arvx::carve_exact_blocks_kernel<false, false, true, false, true>
             : blocks && left && may_split ? arvx::carve_exact_blocks_kernel<true, true>
             : blocks && left && fresh     ? arvx::carve_exact_blocks_kernel<true, false, true>
@@ -1962,7 +2021,7 @@ static int launch_carve(Ctx *ctx, uint16_t *rec, int first, int count, unsigned 
         // (arvx_last_carve_path: all of it once every launch is out, or nothing)
         ctx->path_bits = (dense ? ARVX_PATH_DENSE_CLASSIFY : 0u) | (may_split ? ARVX_PATH_ITEM_SHARING : 0u) |
                          (fresh ? ARVX_PATH_FRESH : 0u) | (lazy ? ARVX_PATH_LAZY_CODES : 0u) |
-                         (cached ? ARVX_PATH_RECT_BLOCKS : 0u);
+                         (cached ? ARVX_PATH_RECT_BLOCKS : 0u) | (pixels ? ARVX_PATH_PIXEL_TABLE : 0u);
         ctx->path_dense_grid = dense ? (unsigned)ncu * (unsigned)ARVX_DENSE_WGS_PER_CU : 0u;
         ctx->path_off_listed = (size_t)((uint8_t *)p.undecidedCount - (uint8_t *)ctx->pool_coarse.p);
         ctx->path_off_work = (size_t)((uint8_t *)p.workCount - (uint8_t *)ctx->pool_coarse.p);
@@ -3284,8 +3343,59 @@ int arvx_ctx_set_rect_cache_limit(arvx_ctx *ctx, uint64_t bytes) {
     if (bytes > (uint64_t)1 << 46) return fail(ARVX_ERR_INVALID, "limit of %llu bytes", (unsigned long long)bytes);
     if (ctx->pool_rect.p) ARVX_SYNC(ctx);  // (a kernel of the stream may still be reading the table)
     ctx->pool_rect.release();
-    ctx->rect_state = Ctx::Rect::None;  // (decided again under the new limit)
+    ctx->pool_pix.release();  // (the pixels are relative to the block table's rectangles)
+    ctx->rect_state = ctx->pix_state = Ctx::Rect::None;  // (decided again under the new limit)
     ctx->rect_limit = (size_t)bytes;
+    return ARVX_OK;
+}
+
+int arvx_ctx_set_pixel_cache_limit(arvx_ctx *ctx, uint64_t bytes) {
+    ARVX_CHECK_CTX(ctx);
+    if (bytes > (uint64_t)1 << 46) return fail(ARVX_ERR_INVALID, "limit of %llu bytes", (unsigned long long)bytes);
+    if (ctx->pool_pix.p) ARVX_SYNC(ctx);  // (a kernel of the stream may still be reading the table)
+    ctx->pool_pix.release();
+    ctx->pix_state = Ctx::Rect::None;  // (decided again under the new limit)
+    ctx->pix_limit = (size_t)bytes;
+    return ARVX_OK;
+}
+
+int arvx_pixel_cache_views(arvx_ctx *ctx, uint64_t *fits, int nwords) {
+    ARVX_CHECK_CTX(ctx);
+    if (!fits || nwords < 0) return fail(ARVX_ERR_INVALID, "null fits or %d words", nwords);
+    const bool built = ctx->pix_state == Ctx::Rect::Built && ctx->pix_assoc == ctx->assoc;
+    for (int w = 0; w < nwords; ++w) {
+        const int left = ctx->V - 64 * w;  // views of this word
+        const uint64_t all = left >= 64 ? ~0ull : left > 0 ? (1ull << left) - 1 : 0ull;
+        fits[w] = built && left > 0 ? ~(uint64_t)ctx->pix_miss[w] & all : 0ull;
+    }
+    return ARVX_OK;
+}
+
+int arvx_selftest_pixel_cache(arvx_ctx *ctx, int64_t *mismatches) {
+    ARVX_CHECK_CTX(ctx);
+    if (!mismatches) return fail(ARVX_ERR_INVALID, "null mismatches");
+    *mismatches = -1;
+    // (a table built under the other grouping is as good as none: the next carve that could read
+    // it builds it again)
+    if (ctx->pix_state != Ctx::Rect::Built || ctx->rect_state != Ctx::Rect::Built || ctx->pix_assoc != ctx->assoc)
+        return ARVX_OK;
+    arvx::CarveParams p;
+    carve_geometry(ctx, p);
+    carve_views(ctx, p);
+    rect_params(ctx, p);
+    p.rcBlk = (const uint32_t *)ctx->pool_rect.p;
+    ARVX_HIP(ctx->pool_scratch.reserve(64));
+    unsigned long long *d_bad = (unsigned long long *)ctx->pool_scratch.p;
+    ARVX_HIP(hipMemsetAsync(d_bad, 0, sizeof *d_bad, ctx->stream));
+    const size_t n = pixel_lanes(ctx, p);
+    ARVX_TRY(by_assoc(ctx, [&](auto left) {
+        return launch(ctx, arvx::pixel_cache_kernel<decltype(left)::value, true>, pixel_grid(n), 256, p,
+                      (uint4 *)ctx->pool_pix.p, n, (unsigned long long *)nullptr, d_bad);
+    }));
+    unsigned long long bad = 0;
+    ARVX_HIP(hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    *mismatches = (int64_t)bad;
     return ARVX_OK;
 }
 

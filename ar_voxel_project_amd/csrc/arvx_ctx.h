@@ -221,8 +221,20 @@ struct Ctx {
     int rect_streak = 0;
     size_t rect_limit = (size_t)1 << 30;  // arvx_ctx_set_rect_cache_limit (0: no table)
     DevPool pool_rect{DevPool::Exact};
+    // Cached pixels (carve_kernels.h table_view_blocks, pixel_cache_kernels.h): one byte per (voxel,
+    // view), the pixel the exact kernel's projection gives, relative to the origin of the block's
+    // cached rectangle.  Built right after the block table and only while that stands, under a
+    // limit of its own (pix_limit); it also follows the grouping of the row sums (pix_assoc: built
+    // again when that changes).  pix_miss: bit v = some pixel of view v does not fit its byte (the
+    // device's words follow the table in pool_pix); such a view is projected as before.
+    Rect pix_state = Rect::None;
+    int pix_assoc = 0;
+    size_t pix_limit = (size_t)6 << 30;  // arvx_ctx_set_pixel_cache_limit (0: no table)
+    DevPool pool_pix{DevPool::Exact};
+    std::vector<unsigned long long> pix_miss;
     void rect_invalidate() {
         rect_state = Rect::None;
+        pix_state = Rect::None;
         rect_streak = 0;
         win_valid = false;  // (the windows follow the same inputs as the cached rectangles)
     }
@@ -557,6 +569,7 @@ struct Ctx {
         pool_bg.release();
         pool_sat.release();
         pool_rect.release();
+        pool_pix.release();
         rect_invalidate();
         views_ready = false;
         cameras_ready = false;

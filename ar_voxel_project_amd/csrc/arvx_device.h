@@ -71,7 +71,8 @@ struct CarveParams {
                             // as a fresh model, bit5 no block tests, bit6 always two parts
                             // (5, 6: experiment builds), bit7 the decided coarse tiles are
                             // not written: their code (coarseCarved -> the context's ccode) is
-                            // their state
+                            // their state, bit8 the block-mapped exact kernel counts its
+                            // projected blocks into `stats` (experiment builds)
     int tilesX, tilesY, tilesZ;
     // coarse pre-pass results
     int coarseX, coarseY, coarseZ, nchunks;
@@ -111,6 +112,11 @@ struct CarveParams {
     // them: [view of the context][record (rec_index)][16 blocks]
     const uint32_t *rcBlk;
     int rcXB, rcYB, rcDB;       // field widths of an entry (RectBits)
+    // cached pixels (pixel_cache_kernels.h), null where the exact kernel projects: [view of the
+    // context][record][lane] 16 bytes, byte 4 m + j = the pixel of the lane's voxel in block j of
+    // group m, relative to the origin of the block's rectangle (low nibble x, high nibble y)
+    const uint4 *pxTab;
+    const unsigned long long *pxMiss;  // bit v: some pixel of view v does not fit its byte
 };
 
 // global z of local plane lz

@@ -1354,6 +1354,13 @@ __device__ __forceinline__ bool exact_view_blocks(const CarveParams &p, const in
         }
     }
     }
+#ifdef ARVX_EXPERIMENTS  // (flags bit8, ARVX_COUNT_BLOCKS: what a table of pixels would replace, EXPERIMENTS.md round 8)
+    if ((p.flags & 256u) && (threadIdx.x & 63) == 0) {
+        atomicAdd(&p.stats[5], (unsigned long long)__popc(did));   // (block, view) passes projected
+        atomicAdd(&p.stats[6], 1ull);                              // (item, view) pairs that got here
+        atomicAdd(&p.stats[7], (unsigned long long)__popc(need));  // blocks their rectangles left open
+    }
+#endif
     if (!did) return false;
     uint32_t word[4][4];
 #pragma unroll
@@ -1371,6 +1378,77 @@ __device__ __forceinline__ bool exact_view_blocks(const CarveParams &p, const in
             const uint32_t isbg = __builtin_amdgcn_ubfe(word[m][j], pix[m][j], 1u);  // bit pix & 31
             const uint32_t seen = (pix[m][j] >> 31) << (8 * j + 1);
             w = (w | seen) & ~(isbg << (8 * j));
+        }
+        st[m] = w;
+    }
+    return __all(st[0] == kDone4 && st[1] == kDone4 && st[2] == kDone4 && st[3] == kDone4);
+}
+
+// The same view from the context's table of pixels (p.pxTab, pixel_cache_kernels.h) -- for a view
+// whose pixels all fit their bytes and whose blocks in `need` all have a rectangle entry in the block
+// table: nothing is projected and no matrix is loaded.  The sixteen block entries of (view, ri), 64
+// contiguous bytes, the same for every lane, come through the scalar cache; a block's pixel is its
+// rectangle's origin plus the two nibbles of the lane's byte.  A rectangle lies inside the image, so
+// every voxel of such a block is seen.  off: the lane's sixteen bytes for this view, arrived.  next
+// (where has_next): the lane's bytes of the view that may follow, requested before anything else
+// and handed back in nxt.  `did`, the reads and the update are exact_view_blocks'.
+__device__ __forceinline__ bool table_view_blocks(const CarveParams &p, const int view, const size_t ri,
+                                                  const uint4 off, const bool has_next,
+                                                  const uint4 *__restrict__ next, uint4 &nxt,
+                                                  uint32_t (&st)[4], const unsigned need) {
+    const uint32_t *__restrict__ bgv = p.bg + (size_t)view * p.bgWords;
+    // (requested first: the read from HBM runs beside everything this view does, and nothing is in
+    // flight when the view ends)
+    nxt = off;
+    if (has_next) nxt = *next;
+    typedef uint32_t u8 __attribute__((ext_vector_type(8)));
+    u8 e0, e1;
+    const uint32_t *ent = p.rcBlk + (((size_t)view * rec_count(p) + ri) << 4);
+    asm volatile(
+        "s_load_dwordx8 %0, %2, 0x0\n\t"
+        "s_load_dwordx8 %1, %2, 0x20\n\t"
+        "s_waitcnt lgkmcnt(0)"
+        : "=&s"(e0), "=&s"(e1)
+        : "s"(ent)
+        : "memory");
+    const uint32_t e[16] = {e0.s0, e0.s1, e0.s2, e0.s3, e0.s4, e0.s5, e0.s6, e0.s7,
+                            e1.s0, e1.s1, e1.s2, e1.s3, e1.s4, e1.s5, e1.s6, e1.s7};
+    const uint32_t o[4] = {off.x, off.y, off.z, off.w};
+    const uint32_t xb = (uint32_t)p.rcXB, xmask = (1u << xb) - 1u, ymask = (1u << p.rcYB) - 1u;
+    uint32_t pix[4][4];  // bit index in the view's background plane
+    unsigned did = 0;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        const uint32_t w = st[m];
+        if (!((need >> (4 * m)) & 15u) || !__any(w != kDone4)) continue;  // nothing to do here
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!((need >> (4 * m + j)) & 1u)) continue;  // decided by its rectangle
+            if (!__any(((w >> (8 * j)) & 0xffu) != 2u)) continue;  // block j is finished
+            did |= 1u << (4 * m + j);
+            // (the origin's bit index is the same in every lane: shifts and masks, which stay scalar)
+            const uint32_t ee = e[4 * m + j];
+            const uint32_t origin = ((ee >> xb) & ymask) * (uint32_t)p.W + (ee & xmask);
+            pix[m][j] = __umul24(__builtin_amdgcn_ubfe(o[m], 8u * j + 4u, 4u), (uint32_t)p.W) +
+                        (__builtin_amdgcn_ubfe(o[m], 8u * j, 4u) + origin);
+        }
+    }
+    uint32_t word[4][4];
+#pragma unroll
+    for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if ((did >> (4 * m + j)) & 1u) word[m][j] = bgv[pix[m][j] >> 5];
+    if (!did) return false;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+        if (!((did >> (4 * m)) & 15u)) continue;
+        uint32_t w = st[m];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (!((did >> (4 * m + j)) & 1u)) continue;
+            const uint32_t isbg = __builtin_amdgcn_ubfe(word[m][j], pix[m][j], 1u);  // bit pix & 31
+            w = (w | (2u << (8 * j))) & ~(isbg << (8 * j));
         }
         st[m] = w;
     }
@@ -1769,6 +1847,9 @@ __device__ __forceinline__ unsigned block_tests(const CarveParams &p, const SubT
 // the matrix and runs rect_prepare.  ri: the sub-tile's record index.  Every view of `views`
 // belongs to this wave (the large grids' instantiations: items are never shared).  A block outside
 // the grid has the entry "outside".
+// NOLOOK: bits 16 + k of a lane's answer mark the blocks k of `need` whose entry is "mixed without
+// a look" -- no rectangle, so no origin for the table of pixels (table_view_blocks).
+template <bool NOLOOK = false>
 __device__ __forceinline__ unsigned block_tests_cached(const CarveParams &p, const size_t ri, int vbase,
                                                        unsigned long long views, int lane,
                                                        unsigned &carved, unsigned &seen) {
@@ -1792,19 +1873,23 @@ __device__ __forceinline__ unsigned block_tests_cached(const CarveParams &p, con
         }
         const int myb = q == 0 ? vb[0] : (q == 1 ? vb[1] : (q == 2 ? vb[2] : vb[3]));
         int cls = kClsOut;
+        bool nolook = false;
         if (q < n) {
             const int view = vbase + myb;
-            cls = classify_block_entry(tab[(size_t)view * vstride], rb,
-                                       p.sat + (size_t)view * p.satStride, p.satW) & 3;
+            const uint32_t e = tab[(size_t)view * vstride];
+            cls = classify_block_entry(e, rb, p.sat + (size_t)view * p.satStride, p.satW) & 3;
+            nolook = e == kRectBlkMixed;
         }
         const unsigned long long c = __ballot(cls == kClsCarved), f = __ballot(cls == kClsFg),
                                  x = __ballot(cls == kClsMixed);
+        const unsigned long long y = NOLOOK ? __ballot(nolook) : 0ull;
         carved |= (unsigned)((c | (c >> 16) | (c >> 32) | (c >> 48)) & 0xffffu);
         seen |= (unsigned)((f | (f >> 16) | (f >> 32) | (f >> 48)) & 0xffffu);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (k < n) {
-                const unsigned need16 = (unsigned)((x >> (16 * k)) & 0xffffu);
+                unsigned need16 = (unsigned)((x >> (16 * k)) & 0xffffu);
+                if (NOLOOK) need16 |= (unsigned)((y >> (16 * k)) & 0xffffu) << 16;
                 if (lane == slot) needLanes = need16;
                 ++slot;
             }
@@ -1903,7 +1988,11 @@ __device__ __forceinline__ unsigned block_tests_lds(const CarveParams &p, const 
 // CACHED: the block tests take their rectangles from the context's table (block_tests_cached) --
 // instantiated for the large grids' fresh kernels only: the kernel slows down with every run-time
 // path added to it.
-template <bool LEFT, bool SPLIT = true, bool FRESH = false, bool FILTER = false, bool CACHED = false>
+// PIXELS (with CACHED): the views that qualify take their pixels from the context's table
+// (table_view_blocks); the others -- a pixel that does not fit its byte, a needed block without a
+// rectangle -- are projected as before.
+template <bool LEFT, bool SPLIT = true, bool FRESH = false, bool FILTER = false, bool CACHED = false,
+          bool PIXELS = false>
 __global__ __launch_bounds__(256, (SPLIT && !FRESH ? ARVX_EXACT_SPLIT_WAVES_PER_SIMD : ARVX_EXACT_WAVES_PER_SIMD))
 void carve_exact_blocks_kernel(const CarveParams p) {
 #ifdef ARVX_TIMELINE
@@ -2009,11 +2098,28 @@ void carve_exact_blocks_kernel(const CarveParams p) {
                 constexpr bool no_bt = false;
 #endif
                 unsigned needLanes = 0xffffu;
+#ifdef ARVX_EXPERIMENTS  // (flags bit8: see exact_view_blocks)
+                if ((p.flags & 256u) && lane == 0) {
+                    if (c == 0) atomicAdd(&p.stats[0], 1ull);                           // items
+                    atomicAdd(&p.stats[2], (unsigned long long)__popcll(mixed));        // their listed views
+                }
+#endif
+                // (PIXELS) the chunk's views with a pixel that does not fit its byte; the lane's bytes
+                // of view pxView, where one was requested ahead
+                unsigned long long pxMiss = 0;
+                uint4 pxOff = make_uint4(0u, 0u, 0u, 0u);
+                int pxView = -1;
+                if constexpr (PIXELS) {
+                    static_assert(CACHED, "the pixels are relative to the cached rectangles");
+                    const int vb = p.v0 + 64 * c, sh = vb & 63;
+                    const unsigned long long lo = p.pxMiss[vb >> 6], hi = p.pxMiss[(vb >> 6) + 1];
+                    pxMiss = uniform64(sh ? (lo >> sh) | (hi << (64 - sh)) : lo);
+                }
                 if constexpr (CACHED) {
                     static_assert(!SPLIT, "the table's variant takes every view of an item");
                     if (!no_bt)
-                        needLanes = block_tests_cached(p, rec_index(p, tx, ty, tz, wave), p.v0 + 64 * c,
-                                                       mixed, lane, bcarved, bseen);
+                        needLanes = block_tests_cached<PIXELS>(p, rec_index(p, tx, ty, tz, wave), p.v0 + 64 * c,
+                                                               mixed, lane, bcarved, bseen);
                 } else if (!no_bt) {
                     needLanes = block_tests(p, t, p.v0 + 64 * c, mixed, part, pshift, lane, bcarved, bseen);
                 }
@@ -2035,11 +2141,39 @@ void carve_exact_blocks_kernel(const CarveParams p) {
                     const int b = __ffsll((long long)mixed) - 1;
                     mixed &= mixed - 1;
                     if ((nth & ((1 << pshift) - 1)) != part) continue;  // another part's view
-                    const unsigned need = no_bt
-                                              ? 0xffffu
-                                              : (unsigned)__builtin_amdgcn_readlane(needLanes, slot);
+                    const unsigned need32 = no_bt
+                                                ? 0xffffu
+                                                : (unsigned)__builtin_amdgcn_readlane(needLanes, slot);
+                    const unsigned need = need32 & 0xffffu;
                     ++slot;
                     if (!need) continue;  // every block settled by its rectangle
+                    if constexpr (PIXELS) {
+                        if (!no_bt && !(need32 >> 16) && !((pxMiss >> b) & 1ull)) {
+                            // (the record's 1 KB of a view: a scalar base, the lane as the offset)
+                            const size_t ri = uniform64(rec_index(p, tx, ty, tz, wave));
+                            const size_t nrec = rec_count(p);
+                            const int view = __builtin_amdgcn_readfirstlane(p.v0 + 64 * c + b);
+                            if (pxView != view) {  // not requested ahead: the item's first such view
+                                pxOff = (p.pxTab + (((size_t)view * nrec + ri) << 6))[lane];
+                                __builtin_amdgcn_s_waitcnt(0x0f70);  // vmcnt(0)
+                            }
+                            // (the next listed view may not take this path: its bytes are then dropped)
+                            pxView = mixed ? p.v0 + 64 * c + __ffsll((long long)mixed) - 1 : -1;
+                            uint4 nxt;
+                            done = table_view_blocks(p, view, ri, pxOff, pxView >= 0,
+                                                     p.pxTab + (((size_t)max(pxView, 0) * nrec + ri) << 6) + lane,
+                                                     nxt, st, need);
+                            pxOff = nxt;
+#ifdef ARVX_TIMELINE
+                            wave_timeline.view_done();
+#endif
+                            continue;
+                        }
+                        // (bytes requested ahead for this view are dropped here: they would stay
+                        // live across the projection, which has no register to spare)
+                        pxView = -1;
+                        pxOff = make_uint4(0u, 0u, 0u, 0u);
+                    }
 #ifdef ARVX_EXPERIMENTS
                     if (FILTER)
                         done = filtered_view_blocks<LEFT>(p, __builtin_amdgcn_readfirstlane(p.v0 + 64 * c + b),

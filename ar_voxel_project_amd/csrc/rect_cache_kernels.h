@@ -12,10 +12,8 @@
 
 namespace arvx {
 
-// entry (view, ri, blk) of the table: block blk (block_tests: j = blk & 3, m = blk >> 2) of the
-// sub-tile with record index ri.  false: the rectangle does not fit an entry.
-__device__ inline bool rect_cache_block_entry(const CarveParams &p, int view, size_t ri, int blk,
-                                              uint32_t &e) {
+// the inverse of rec_index: first voxel (slab-local z) of the sub-tile with record index ri
+__device__ inline void rec_origin(const CarveParams &p, size_t ri, int &sx0, int &sy0, int &sz0) {
     const int tshift = p.cyShift + p.czShift;
     const int wave = (int)(ri & 3);
     const int tl = (int)((ri >> 2) & ((1u << tshift) - 1u));
@@ -23,7 +21,17 @@ __device__ inline bool rect_cache_block_entry(const CarveParams &p, int view, si
     const int tx = ct % p.coarseX;
     const int ty = (((ct / p.coarseX) % p.coarseY) << p.cyShift) + (tl & ((1 << p.cyShift) - 1));
     const int tz = ((ct / (p.coarseX * p.coarseY)) << p.czShift) + (tl >> p.cyShift);
-    const int sx0 = tx * kTileX + wave * kSubX, sy0 = ty * kTileY, sz0 = tz * kTileZ;
+    sx0 = tx * kTileX + wave * kSubX;
+    sy0 = ty * kTileY;
+    sz0 = tz * kTileZ;
+}
+
+// entry (view, ri, blk) of the table: block blk (block_tests: j = blk & 3, m = blk >> 2) of the
+// sub-tile with record index ri.  false: the rectangle does not fit an entry.
+__device__ inline bool rect_cache_block_entry(const CarveParams &p, int view, size_t ri, int blk,
+                                              uint32_t &e) {
+    int sx0, sy0, sz0;
+    rec_origin(p, ri, sx0, sy0, sz0);
     const int j = blk & 3, m = blk >> 2, byi = m >> 1, bzi = m & 1;
     const int x0 = sx0 + 4 * j, y0 = sy0 + 4 * byi, z0 = sz0 + 4 * bzi;
     RectQ q;

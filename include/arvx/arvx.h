@@ -1221,6 +1221,7 @@ int arvx_get_stats(arvx_ctx *ctx, arvx_stats *out);
 #define ARVX_PATH_BRUTE_FORCE 32u   /* no rectangle tests at all (ARVX_CARVE_NO_CULL) */
 #define ARVX_PATH_STREAM 64u        /* the one-launch streaming carve (-DARVX_EXPERIMENTS builds) */
 #define ARVX_PATH_RECT_BLOCKS 128u  /* the exact kernel's block tests came from the table of cached rectangles */
+#define ARVX_PATH_PIXEL_TABLE 256u  /* ... and the pixels of the views that fit from the table of cached pixels */
 int arvx_last_carve_path(arvx_ctx *ctx, uint32_t out[4]);
 
 /* Diagnostic: how the context's last arvx_fast_carve grew its component.  Host bookkeeping; the
@@ -1283,6 +1284,30 @@ int arvx_ctx_set_rect_cache_limit(arvx_ctx *ctx, uint64_t bytes);
 /* Self-test hook: recomputes every entry of the table of cached rectangles; *mismatches, the entries
  * that differ, must come back 0 (-1: the context holds no table). */
 int arvx_selftest_rect_cache(arvx_ctx *ctx, int64_t *mismatches);
+
+/* Cached pixels.  The pixel a voxel projects to in a view follows the same inputs as the block
+ * rectangles above, plus the grouping of the row sums (arvx_ctx_set_projection_assoc); the masks only
+ * decide which bit is found there.  Together with the table of block rectangles, and only while
+ * that one stands, the context therefore tabulates the exact kernel's projection: one byte per
+ * (voxel, view) -- the pixel relative to the origin of the block's rectangle, a nibble each way --,
+ * 1 KB per (sub-tile record, view): 4.83 GB at 512^3 x 36 views.  The exact kernel of the carves
+ * that follow reads a view's pixels instead of projecting (ARVX_PATH_PIXEL_TABLE; the results are the
+ * same bit for bit).  A view with a pixel more than 15 pixels from its rectangle's origin is
+ * projected as before, as is a view of a sub-tile in which a block that needs a look has no
+ * rectangle (it crosses the image's edge or the camera's plane).  The table has its own limit
+ * (default 6 GiB; 0: no table): 512^3 x 36 fits, 1024^3 x 36 (38.7 GB) and 512^3 x 72 do not and
+ * run as before.  A failed allocation means no table, not an error.  New matrices or sizes, a new
+ * limit of either table, or another grouping drop it; it is built again with (or right after) the
+ * block table.  The call releases the table; it is decided again under the new limit. */
+int arvx_ctx_set_pixel_cache_limit(arvx_ctx *ctx, uint64_t bytes);
+
+/* The views whose pixels are read from the table: bit v % 64 of fits[v / 64], nwords words (all 0
+ * while the context holds no table of pixels). */
+int arvx_pixel_cache_views(arvx_ctx *ctx, uint64_t *fits, int nwords);
+
+/* Self-test hook: recomputes every byte of the table of cached pixels; *mismatches, the bytes that
+ * differ, must come back 0 (-1: the context holds no table). */
+int arvx_selftest_pixel_cache(arvx_ctx *ctx, int64_t *mismatches);
 
 /* View windows.  A rectangle test of the carve reads a view's summed-area table only inside the
  * pixel rectangle that the whole grid projects into (plus a margin and the table's border row and
