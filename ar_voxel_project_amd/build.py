@@ -57,6 +57,7 @@ def build_host_tests() -> str:
     build_morph_host_test()
     build_refine_host_test()
     build_render_mesh_host_test()
+    build_render_mesh_clip_host_test()
     build_mesh_color_host_test()
     build_mesh_texture_host_test()
     build_segment_host_test()
@@ -99,6 +100,13 @@ def build_render_mesh_host_test() -> str:
     """g++ -> tests/cpp/test_render_mesh_host: arvx::renderMesh (include/arvx/marching_cubes.hpp) on a
     scene from a file, built as build_weld_host_test builds its test."""
     return _build_host_test("test_render_mesh_host")
+
+
+def build_render_mesh_clip_host_test() -> str:
+    """g++ -> tests/cpp/test_render_mesh_clip_host: arvx::setRenderNear and arvx::renderMesh under a near
+    plane (include/arvx/marching_cubes.hpp) on a scene from a file, built as build_weld_host_test
+    builds its test."""
+    return _build_host_test("test_render_mesh_clip_host")
 
 
 def build_mesh_color_host_test() -> str:

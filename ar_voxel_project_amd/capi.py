@@ -101,6 +101,7 @@ SYMBOLS = [
     "arvx_render", "arvx_render_view", "arvx_render_download", "arvx_render_agreement",
     "arvx_render_mesh", "arvx_render_mesh_view", "arvx_render_mesh_agreement", "arvx_render_triangles",
     "arvx_render_mesh_stats", "arvx_selftest_render_mesh_list", "arvx_selftest_compute_units",
+    "arvx_ctx_set_render_near", "arvx_ctx_render_near", "arvx_render_mesh_clip_stats",
     "arvx_mesh_color", "arvx_mesh_color_count", "arvx_mesh_color_download", "arvx_mesh_color_depth_download",
     "arvx_selftest_mesh_color_batch",
     "arvx_mesh_texture", "arvx_mesh_texture_info", "arvx_mesh_texture_download",
@@ -313,6 +314,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                               C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.arvx_render_mesh_stats.argtypes = [p, C.POINTER(C.c_int64)]
         lib.arvx_selftest_render_mesh_list.argtypes = [p, C.c_int64]
+    if hasattr(lib, "arvx_ctx_set_render_near") or not ab_build:
+        lib.arvx_ctx_set_render_near.argtypes = [p, C.c_float]
+        lib.arvx_ctx_render_near.argtypes = [p, C.POINTER(C.c_float)]
+        lib.arvx_render_mesh_clip_stats.argtypes = [p, C.POINTER(C.c_int64)]
     if hasattr(lib, "arvx_selftest_compute_units") or not ab_build:
         lib.arvx_selftest_compute_units.argtypes = [p, C.c_int]
     if hasattr(lib, "arvx_mesh_color") or not ab_build:
@@ -1219,6 +1224,24 @@ class Context:
         """arvx_render_mesh_stats: (drawn, empty, flat, refused) triangles of the current triangle render."""
         out = (C.c_int64 * 4)()
         self._ck(self._lib.arvx_render_mesh_stats(self._h, out))
+        return tuple(int(n) for n in out)
+
+    def set_render_near(self, near: float) -> None:
+        """arvx_ctx_set_render_near: the near plane of the triangle renders from the next one on -- faces
+        that cross a2 = near are clipped against it.  0: none (the default)."""
+        self._ck(self._lib.arvx_ctx_set_render_near(self._h, float(near)))
+
+    def render_near(self) -> float:
+        """arvx_ctx_render_near: the near plane as set (0: none)."""
+        out = C.c_float()
+        self._ck(self._lib.arvx_ctx_render_near(self._h, C.byref(out)))
+        return float(out.value)
+
+    def render_mesh_clip_stats(self) -> Tuple[int, int, int, int]:
+        """arvx_render_mesh_clip_stats: (faces wholly behind the near plane, faces that straddle it,
+        pieces made, pieces drawn) of the current triangle render; zeros for one made without a plane."""
+        out = (C.c_int64 * 4)()
+        self._ck(self._lib.arvx_render_mesh_clip_stats(self._h, out))
         return tuple(int(n) for n in out)
 
     def selftest_render_mesh_list(self, cap: int) -> None:

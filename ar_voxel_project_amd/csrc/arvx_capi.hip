@@ -47,6 +47,7 @@
 #include "vote_kernels.h"
 #include "render_kernels.h"
 #include "render_mesh_kernels.h"
+#include "render_mesh_clip_kernels.h"
 #include "mesh_color_kernels.h"
 #include "mesh_texture_kernels.h"
 #include "exchange_kernels.h"
@@ -4444,7 +4445,12 @@ static int render_mesh_launch(Ctx *ctx, const MeshSource &m, const float *M, int
         ctx->render_mesh_list_cap >= 0
             ? (unsigned)std::min<long long>({ctx->render_mesh_list_cap, m.T, (long long)UINT32_MAX})
             : large_list_cap(m.T, ctx->render_mesh_need, m.T);
-    ARVX_HIP(ctx->pool_render_tris.reserve(64 + (size_t)large_cap * sizeof(arvx::SplatRect)));
+    // (with a near plane the four clip counts lie behind the list)
+    const bool clip = ctx->render_near > 0.f;
+    const size_t clip_at = 64 + (size_t)large_cap * sizeof(arvx::SplatRect);
+    constexpr size_t clip_bytes = arvx::kClipCounts * sizeof(unsigned long long);
+    ARVX_HIP(ctx->pool_render_tris.reserve(clip_at + (clip ? clip_bytes : 0)));
+    ctx->render_clip_at = 0;
     arvx::RenderMeshParams p{};
     p.verts = m.verts, p.rgb = m.rgb, p.faces = m.faces;
     p.V = m.V, p.T = m.T;
@@ -4459,6 +4465,11 @@ static int render_mesh_launch(Ctx *ctx, const MeshSource &m, const float *M, int
     for (int k = 0; k < 3; ++k) p.light[k] = light ? light[k] : 0.f;
     static_assert(sizeof(arvx::RenderMeshHeader) <= 64, "the header ends before the list");
     ARVX_HIP(hipMemsetAsync(p.head, 0, 64, ctx->stream));
+    if (clip) {
+        p.near = ctx->render_near;
+        p.clip = (unsigned long long *)((uint8_t *)ctx->pool_render_tris.p + clip_at);
+        ARVX_HIP(hipMemsetAsync(p.clip, 0, clip_bytes, ctx->stream));
+    }
     if (m.T > 0 && m.V > 0) {
         ARVX_HIP(ctx->pool_render_proj.reserve((size_t)m.V * sizeof(arvx::MeshVertex)));
         p.proj = (arvx::MeshVertex *)ctx->pool_render_proj.p;
@@ -4467,14 +4478,36 @@ static int render_mesh_launch(Ctx *ctx, const MeshSource &m, const float *M, int
             return launch(ctx, arvx::render_mesh_project_kernel<decltype(left)::value>, blocks_for(m.V), 256, p);
         }));
         // (the grid strides over the faces)
-        ARVX_TRY(launch(ctx, arvx::render_mesh_raster_kernel,
-                        (unsigned)std::min<long long>((m.T + 255) / 256, 8 * ncu), 256, p));
-        ARVX_TRY(launch(ctx, arvx::render_mesh_large_kernel, (unsigned)(4 * ncu), 256, p,
-                        ctx->word_dev(Ctx::kRenderMeshNeed)));
+        const unsigned raster_blocks = (unsigned)std::min<long long>((m.T + 255) / 256, 8 * ncu);
+        if (clip) {
+            ARVX_TRY(by_assoc(ctx, [&](auto left) {
+                constexpr bool L = decltype(left)::value;
+                ARVX_TRY(launch(ctx, arvx::render_mesh_clip_raster_kernel<L>, raster_blocks, 256, p));
+                return launch(ctx, arvx::render_mesh_clip_large_kernel<L>, (unsigned)(4 * ncu), 256, p,
+                              ctx->word_dev(Ctx::kRenderMeshNeed));
+            }));
+        } else {
+            ARVX_TRY(launch(ctx, arvx::render_mesh_raster_kernel, raster_blocks, 256, p));
+            ARVX_TRY(launch(ctx, arvx::render_mesh_large_kernel, (unsigned)(4 * ncu), 256, p,
+                            ctx->word_dev(Ctx::kRenderMeshNeed)));
+        }
     } else {
         p.T = 0;  // (faces without vertices cannot be: every index is below V)
     }
-    if (m.textured) {
+    if (clip && p.T > 0) {
+        // (the plane's resolve: the winner's piece re-derived)
+        ARVX_TRY(by_assoc(ctx, [&](auto left) {
+            constexpr bool L = decltype(left)::value;
+            if (m.textured) {
+                const arvx::MeshTextureColour tex{ctx->pool_mtex_atlas.data(),
+                                                  arvx::texture_layout(m.T, ctx->mesh_texture_R, ctx->mesh_texture_AW)};
+                return launch(ctx, arvx::render_mesh_clip_resolve_kernel<arvx::MeshTextureColour, L>, blocks_for(npix),
+                              256, p, npix, render_id(ctx), render_depth(ctx), render_bgr(ctx), tex);
+            }
+            return launch(ctx, arvx::render_mesh_clip_resolve_kernel<arvx::MeshVertexColour, L>, blocks_for(npix), 256,
+                          p, npix, render_id(ctx), render_depth(ctx), render_bgr(ctx), arvx::MeshVertexColour{});
+        }));
+    } else if (m.textured) {
         const arvx::MeshTextureColour tex{ctx->pool_mtex_atlas.data(),
                                           arvx::texture_layout(m.T, ctx->mesh_texture_R, ctx->mesh_texture_AW)};
         ARVX_TRY(launch(ctx, arvx::render_mesh_resolve_kernel<arvx::MeshTextureColour>, blocks_for(npix), 256, p,
@@ -4485,6 +4518,7 @@ static int render_mesh_launch(Ctx *ctx, const MeshSource &m, const float *M, int
     }
     ctx->render_ready = true;
     ctx->render_tris = true;
+    ctx->render_clip_at = clip ? clip_at : 0;
     return ARVX_OK;
 }
 
@@ -4578,6 +4612,36 @@ int arvx_render_mesh_stats(arvx_ctx *ctx, int64_t out[4]) {
     ARVX_SYNC(ctx);
     ctx->render_mesh_need = std::max(ctx->word(Ctx::kRenderMeshNeed), 0ll);
     for (int k = 0; k < arvx::kMeshClasses; ++k) out[k] = (int64_t)classes[k];
+    return ARVX_OK;
+}
+
+int arvx_ctx_set_render_near(arvx_ctx *ctx, float near) {
+    ARVX_CHECK_CTX(ctx);
+    if (!(near == 0.f || (std::isfinite(near) && near >= FLT_MIN)))
+        return fail(ARVX_ERR_INVALID, "near %g (0: no near plane; otherwise finite and >= FLT_MIN)", (double)near);
+    ctx->render_near = near == 0.f ? 0.f : near;  // (-0 is 0)
+    return ARVX_OK;
+}
+
+int arvx_ctx_render_near(const arvx_ctx *ctx, float *near) {
+    ARVX_CHECK_CTX(ctx);
+    if (!near) return fail(ARVX_ERR_INVALID, "null near");
+    *near = ctx->render_near;
+    return ARVX_OK;
+}
+
+int arvx_render_mesh_clip_stats(arvx_ctx *ctx, int64_t out[4]) {
+    ARVX_CHECK_CTX(ctx);
+    if (!out) return fail(ARVX_ERR_INVALID, "null out");
+    if (!ctx->render_ready || !ctx->render_tris)
+        return fail(ARVX_ERR_STATE, "the current render is no triangle render (call arvx_render_mesh)");
+    unsigned long long counts[arvx::kClipCounts] = {0, 0, 0, 0};
+    if (ctx->render_clip_at)
+        ARVX_HIP(hipMemcpyAsync(counts, (const uint8_t *)ctx->pool_render_tris.p + ctx->render_clip_at, sizeof counts,
+                                hipMemcpyDeviceToHost, ctx->stream));
+    ARVX_SYNC(ctx);
+    ctx->render_mesh_need = std::max(ctx->word(Ctx::kRenderMeshNeed), 0ll);
+    for (int k = 0; k < arvx::kClipCounts; ++k) out[k] = (int64_t)counts[k];
     return ARVX_OK;
 }
 

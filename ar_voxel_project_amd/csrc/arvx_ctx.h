@@ -516,6 +516,11 @@ struct Ctx {
     DevArray<unsigned> pool_tri_faces;
     bool render_tris = false;
     long long render_mesh_need = 0, render_mesh_list_cap = -1;
+    // arvx_ctx_set_render_near (render_mesh_clip_kernels.h): the plane of the next triangle render (0:
+    // none), and where the current one's four clip counts lie in pool_render_tris, behind its list (0:
+    // it was made without a plane and has none).
+    float render_near = 0.f;
+    size_t render_clip_at = 0;
     // arvx_mesh_color (mesh_color_kernels.h): the product -- per vertex r, g, b and the number of views
     // that see it, the V x H x W depth keys, tagged with its source (read only while mesh_color_ready is
     // set) -- and its workspace: the projected vertices of one batch of views, the list of large pixel

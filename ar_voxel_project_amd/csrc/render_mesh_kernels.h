@@ -14,6 +14,8 @@
 //   render_mesh_resolve_kernel  one lane per pixel: the winner's edge functions once more, its
 //                               depth, the interpolated colour (or, instantiated with
 //                               MeshTextureColour, the face's texel), the face's shade
+// With a near plane set (arvx_ctx_set_render_near) the raster, large and resolve kernels launched are
+// those of render_mesh_clip_kernels.h instead; the ones here have no clip path.
 // Coverage is decided by three 64-bit integer edge functions of 28.4 fixed-point corners: exact, so
 // two faces that share an edge agree about its pixels.  A key is bits(depth) << 32 | t with depth a
 // positive fp32: its 64-bit unsigned minimum (key_min, a no-return atomicMin) is the nearest
@@ -61,18 +63,28 @@ struct RenderMeshParams {
     unsigned large_cap;
     float light[3];
     int lit;
+    // near-plane clipping (render_mesh_clip_kernels.h; read by its kernels only): the plane, > 0, and
+    // the four clip counts
+    float near;
+    unsigned long long *clip;
 };
 
 // Step 1 of the definition for the point (px, py, pz) under camera M: the one place it is computed
 // (the mesh colours' kernels, mesh_color_kernels.h, project with it too).
 template <bool LEFT>
-__device__ __forceinline__ MeshVertex mesh_project(const SelftestMatrix &M, float s, float px, float py, float pz) {
+__device__ __forceinline__ void mesh_project_rows(const SelftestMatrix &M, float s, float px, float py, float pz,
+                                                  float (&a)[3]) {
     const double w0 = (double)(py * s), w1 = (double)(px * s), w2 = (double)((-pz) * s);
-    float a[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r)
         a[r] = row_sum<LEFT>((double)M.m[4 * r] * w0, (double)M.m[4 * r + 1] * w1, (double)M.m[4 * r + 2] * w2,
                              (double)M.m[4 * r + 3]);
+}
+
+template <bool LEFT>
+__device__ __forceinline__ MeshVertex mesh_project(const SelftestMatrix &M, float s, float px, float py, float pz) {
+    float a[3];
+    mesh_project_rows<LEFT>(M, s, px, py, pz, a);
     const float qu = a[0] / a[2], qv = a[1] / a[2];
     const bool valid = a[2] >= FLT_MIN && isfinite(qu) && isfinite(qv) && fabsf(qu) <= kMeshMaxPixel &&
                        fabsf(qv) <= kMeshMaxPixel;
@@ -116,6 +128,25 @@ __device__ __forceinline__ long long mesh_det(int a, int b, int c, int d) {
     return (long long)a * b - (long long)c * d;
 }
 
+// Steps 2 and 3 for the corners already in `tri`: kMeshFlat, kMeshEmpty for an empty pixel box, or
+// kMeshDrawn with A, its sign and the box set.
+__device__ __forceinline__ int mesh_tri_box(const RenderMeshParams &p, MeshTri &tri) {
+    const long long A = mesh_det(tri.x1 - tri.x0, tri.y2 - tri.y0, tri.x2 - tri.x0, tri.y1 - tri.y0);
+    if (A == 0) return kMeshFlat;
+    tri.neg = A < 0;
+    tri.A = tri.neg ? -A : A;
+    const int xmin = min(tri.x0, min(tri.x1, tri.x2)), xmax = max(tri.x0, max(tri.x1, tri.x2));
+    const int ymin = min(tri.y0, min(tri.y1, tri.y2)), ymax = max(tri.y0, max(tri.y1, tri.y2));
+    // (an arithmetic shift is the floor; + 15 first makes it the ceiling)
+    tri.c0 = max((xmin + 15) >> 4, 0);
+    tri.c1 = min(xmax >> 4, p.W - 1);
+    tri.r0 = max((ymin + 15) >> 4, 0);
+    tri.r1 = min(ymax >> 4, p.H - 1);
+    // (most triangles of a fine mesh lie between the pixel centres: they end here, before the divisions)
+    if (tri.c0 > tri.c1 || tri.r0 > tri.r1) return kMeshEmpty;
+    return kMeshDrawn;
+}
+
 // The class of triangle t as far as its corners decide it: kMeshRefused, kMeshFlat, kMeshEmpty for one
 // whose pixel box is empty, or kMeshDrawn for a triangle with an area and a box (it may still turn
 // out kMeshEmpty); only then is `tri` complete.
@@ -125,19 +156,7 @@ __device__ __forceinline__ int mesh_tri_setup(const RenderMeshParams &p, long lo
     const MeshVertex v0 = mesh_vertex(p.proj, i0), v1 = mesh_vertex(p.proj, i1), v2 = mesh_vertex(p.proj, i2);
     if (!(v0.valid && v1.valid && v2.valid)) return kMeshRefused;
     tri.x0 = v0.fx, tri.y0 = v0.fy, tri.x1 = v1.fx, tri.y1 = v1.fy, tri.x2 = v2.fx, tri.y2 = v2.fy;
-    const long long A = mesh_det(tri.x1 - tri.x0, tri.y2 - tri.y0, tri.x2 - tri.x0, tri.y1 - tri.y0);
-    if (A == 0) return kMeshFlat;
-    tri.neg = A < 0;
-    tri.A = tri.neg ? -A : A;
-    const int xmin = min(v0.fx, min(v1.fx, v2.fx)), xmax = max(v0.fx, max(v1.fx, v2.fx));
-    const int ymin = min(v0.fy, min(v1.fy, v2.fy)), ymax = max(v0.fy, max(v1.fy, v2.fy));
-    // (an arithmetic shift is the floor; + 15 first makes it the ceiling)
-    tri.c0 = max((xmin + 15) >> 4, 0);
-    tri.c1 = min(xmax >> 4, p.W - 1);
-    tri.r0 = max((ymin + 15) >> 4, 0);
-    tri.r1 = min(ymax >> 4, p.H - 1);
-    // (most triangles of a fine mesh lie between the pixel centres: they end here, before the divisions)
-    if (tri.c0 > tri.c1 || tri.r0 > tri.r1) return kMeshEmpty;
+    if (const int cls = mesh_tri_box(p, tri); cls != kMeshDrawn) return cls;
     tri.iz0 = 1.0 / (double)__uint_as_float(v0.a2);
     tri.iz1 = 1.0 / (double)__uint_as_float(v1.a2);
     tri.iz2 = 1.0 / (double)__uint_as_float(v2.a2);
@@ -292,8 +311,39 @@ struct MeshVertexColour {
     }
 };
 
-// One lane per pixel.  bgr holds the background already (the caller's image or zeros): only the
-// covered pixels are written.
+// The winner t of pixel i with its weights (w0, w1, w2, S): its id and depth, step 5's colour and
+// shade.  bgr holds the background already (the caller's image or zeros).
+template <class Colour>
+__device__ __forceinline__ void mesh_pixel_out(const RenderMeshParams &p, size_t i, unsigned long long key, double w0,
+                                               double w1, double w2, double S, int *__restrict__ id,
+                                               float *__restrict__ depth, uint8_t *__restrict__ bgr,
+                                               const Colour &colour) {
+    const uint32_t t = (uint32_t)key;
+    id[i] = (int)t;
+    depth[i] = __uint_as_float((uint32_t)(key >> 32));
+    const size_t i0 = p.faces[6 * (size_t)t], i1 = p.faces[6 * (size_t)t + 1], i2 = p.faces[6 * (size_t)t + 2];
+    float shade = 1.f;
+    if (p.lit) {
+        const float *__restrict__ q = p.verts;
+        const float ax = q[3 * i2] - q[3 * i0], ay = q[3 * i2 + 1] - q[3 * i0 + 1], az = q[3 * i2 + 2] - q[3 * i0 + 2];
+        const float bx = q[3 * i1] - q[3 * i0], by = q[3 * i1 + 1] - q[3 * i0 + 1], bz = q[3 * i1 + 2] - q[3 * i0 + 2];
+        const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+        const float l = mesh_length(cx, cy, cz), m = mesh_length(p.light[0], p.light[1], p.light[2]);
+        const float d = (cx * p.light[0] + cy * p.light[1]) + cz * p.light[2];
+        const float f = (l == 0.f || m == 0.f) ? 1.f : fminf(fabsf(d) / (l * m), 1.f);
+        shade = 0.25f + 0.75f * f;
+    }
+    float v[3];
+    colour(p, t, i0, i1, i2, w0, w1, w2, S, v);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        if (p.lit) v[ch] = shade * v[ch];
+    bgr[3 * i] = render_channel(v[2]);
+    bgr[3 * i + 1] = render_channel(v[1]);
+    bgr[3 * i + 2] = render_channel(v[0]);
+}
+
+// One lane per pixel: only the covered pixels are written.
 template <class Colour>
 __global__ __launch_bounds__(256) void render_mesh_resolve_kernel(const RenderMeshParams p, size_t npix,
                                                                   int *__restrict__ id, float *__restrict__ depth,
@@ -308,32 +358,11 @@ __global__ __launch_bounds__(256) void render_mesh_resolve_kernel(const RenderMe
         depth[i] = INFINITY;
         return;
     }
-    id[i] = (int)t;
-    depth[i] = __uint_as_float((uint32_t)(key >> 32));
     long long e0, e1, e2;
     (void)mesh_edges(tri, (int)(i % (size_t)p.W), (int)(i / (size_t)p.W), e0, e1, e2);
     double t0, t1, t2;
     const double S = mesh_weights(tri, e0, e1, e2, t0, t1, t2);
-    const size_t i0 = p.faces[6 * (size_t)t], i1 = p.faces[6 * (size_t)t + 1], i2 = p.faces[6 * (size_t)t + 2];
-    float shade = 1.f;
-    if (p.lit) {
-        const float *__restrict__ q = p.verts;
-        const float ax = q[3 * i2] - q[3 * i0], ay = q[3 * i2 + 1] - q[3 * i0 + 1], az = q[3 * i2 + 2] - q[3 * i0 + 2];
-        const float bx = q[3 * i1] - q[3 * i0], by = q[3 * i1 + 1] - q[3 * i0 + 1], bz = q[3 * i1 + 2] - q[3 * i0 + 2];
-        const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-        const float l = mesh_length(cx, cy, cz), m = mesh_length(p.light[0], p.light[1], p.light[2]);
-        const float d = (cx * p.light[0] + cy * p.light[1]) + cz * p.light[2];
-        const float f = (l == 0.f || m == 0.f) ? 1.f : fminf(fabsf(d) / (l * m), 1.f);
-        shade = 0.25f + 0.75f * f;
-    }
-    float v[3];
-    colour(p, t, i0, i1, i2, t0, t1, t2, S, v);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-        if (p.lit) v[ch] = shade * v[ch];
-    bgr[3 * i] = render_channel(v[2]);
-    bgr[3 * i + 1] = render_channel(v[1]);
-    bgr[3 * i + 2] = render_channel(v[0]);
+    mesh_pixel_out(p, i, key, t0, t1, t2, S, id, depth, bgr, colour);
 }
 
 }  // namespace arvx

@@ -977,7 +977,7 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]);
  *     fx = (int)std::round(qu * 16.0f), fy = (int)std::round(qv * 16.0f): the products are exact and
  *     |fx|, |fy| <= 2^19.  Pixel (c, r) is the point (16 c, 16 r): pixel centres are the integers, as
  *     everywhere in this library.
- *  2. Triangle.  REFUSED if a corner is not VALID (no near-plane clipping).  With corners (x0, y0),
+ *  2. Triangle.  REFUSED if a corner is not VALID (near-plane clipping: below).  With corners (x0, y0),
  *     (x1, y1), (x2, y2): A = (x1 - x0)(y2 - y0) - (x2 - x0)(y1 - y0) in int64; FLAT if A == 0.  Both
  *     windings are drawn.
  *  3. Coverage.  For P = (px, py) = (16 c, 16 r): E0 = (x1 - px)(y2 - py) - (x2 - px)(y1 - py),
@@ -1017,6 +1017,41 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]);
  * render as the current one and counts as arvx_render_agreement does, with ONE host synchronisation.
  * arvx_render_mesh_stats returns the class counts of the current render, {DRAWN, EMPTY, FLAT,
  * REFUSED}; they sum to T; it synchronises.  An empty mesh renders the background.
+ * Near plane (arvx_ctx_set_render_near; 0, the default: none, and everything above holds as it
+ * stands).  With near = n > 0, steps 1-6 stay as they are except for the following.
+ *  Front and behind.  Corner i is IN FRONT iff a2_i >= n (a NaN is behind).  All three corners in
+ *     front: the triangle is treated exactly as above.  None in front: REFUSED, and counted as WHOLLY
+ *     BEHIND.  Otherwise the face STRADDLES the plane.
+ *  Clipped vertex C(i, j) of an edge with exactly one end in front: with lo < hi its two VERTEX
+ *     indices in index order (not face order: two faces that share the edge compute the same vertex,
+ *     bit for bit), t = ((double)n - (double)a2_lo) / ((double)a2_hi - (double)a2_lo);
+ *     c0 = (float)((double)a0_lo + t * ((double)a0_hi - (double)a0_lo)), c1 the same from a1; its a2
+ *     is n exactly; qu = c0 / n, qv = c1 / n; VALID and fx, fy are decided as in step 1.  Its weights
+ *     towards the face's corners are B_hi = (float)t, B_lo = (float)(1.0 - t) and 0 for the third; an
+ *     original corner has the unit weight vector.
+ *  Polygon and pieces, the face's corners P_0, P_1, P_2 in face order, indices mod 3.  One corner r
+ *     in front: (P_r, C(r, r+1), C(r+2, r)), one piece.  Two in front, r and r+1: (v0, v1, v2, v3) =
+ *     (P_r, P_{r+1}, C(r+1, r+2), C(r+2, r)); piece 0 is (v0, v1, v2), piece 1 (v0, v2, v3).  Each
+ *     piece goes through steps 2-4 as a triangle of its own corners: one with a corner that is not
+ *     VALID is REFUSED; iz of a clipped corner is 1.0 / (double)n.  The key is still
+ *     bits(depth) << 32 | t with t the FACE.
+ *  Winner and colour.  The winner of a pixel is the minimum of (bits(depth), t, k), k the piece:
+ *     the key is unchanged, and k is the least piece of face t that covers the pixel with exactly
+ *     that depth.  With the piece's t_0, t_1, t_2, S and the rows B_0, B_1, B_2 of its corners:
+ *     w_j = (t_0 * (double)B_0j + t_1 * (double)B_1j) + t_2 * (double)B_2j, j = 0, 1, 2; step 5 (and
+ *     the mesh textures' lookup) runs with (w_0, w_1, w_2, S) and the face's corners' colours.  For
+ *     an unclipped triangle B is the identity and w_j = t_j exactly.  The shade is the face's.
+ *  Classes.  id is the face.  A straddling face takes the best class among its pieces, in the order
+ *     DRAWN, EMPTY, FLAT, REFUSED; the four classes still sum to T.
+ * arvx_ctx_set_render_near sets n for the context, as arvx_ctx_set_view_window sets its switch: it
+ * drops no product and leaves the current render alone, and holds from the next arvx_render_mesh,
+ * _view, _agreement or arvx_render_triangles on, with ARVX_MESH_IMAGE_COLORS and ARVX_MESH_TEXTURED
+ * too.  near == 0: off; a finite near >= FLT_MIN: on; a negative, NaN, infinite or subnormal one:
+ * ARVX_ERR_INVALID, nothing changed.  arvx_ctx_render_near returns it.  arvx_render (the voxel
+ * render), arvx_mesh_color and arvx_mesh_texture ignore it.  arvx_render_mesh_clip_stats returns
+ * {faces wholly behind, faces that straddle, pieces made, pieces DRAWN} of the current render (zeros
+ * for one made with the plane off); it synchronises; ARVX_ERR_STATE when the current render is no
+ * triangle render.  With the plane on, the four counts lie behind the list (32 bytes).
  * Refusals.  ARVX_ERR_STATE: the source mesh does not exist (slab and striped contexts never have
  * one); the _view and _agreement forms without views, or the agreement form when the views were set
  * with masks == NULL; arvx_render_mesh_stats when the current render is no triangle render;
@@ -1028,8 +1063,8 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]);
  * Device memory beside the render's, sized at first use and kept: 16 bytes per vertex of projected
  * positions and the list of triangles whose pixel box exceeds 64 pixels (16 bytes each), swept by a
  * wave each; what does not fit the list is swept by the wave that found it.
- * Out of scope: near-plane and guard-band clipping, anti-aliasing, per-vertex normals, slabs and
- * multi-GPU.  (Textures: the mesh textures' block below, ARVX_MESH_TEXTURED.) */
+ * Out of scope: guard-band clipping (a piece with a corner that is not VALID is REFUSED), a far plane,
+ * anti-aliasing, per-vertex normals, slabs and multi-GPU.  (Textures: the mesh textures' block below, ARVX_MESH_TEXTURED.) */
 #define ARVX_MESH_WELDED 0
 #define ARVX_MESH_SMOOTHED 1
 #define ARVX_MESH_DECIMATED 2
@@ -1042,6 +1077,9 @@ int arvx_render_triangles(arvx_ctx *ctx, int64_t nv, const float *verts, const f
                           const uint32_t *faces, const float M[12], int W, int H, const uint8_t *background,
                           size_t bg_stride, const float *light);
 int arvx_render_mesh_stats(arvx_ctx *ctx, int64_t out[4]);
+int arvx_ctx_set_render_near(arvx_ctx *ctx, float near); /* 0: off (default) */
+int arvx_ctx_render_near(const arvx_ctx *ctx, float *near);
+int arvx_render_mesh_clip_stats(arvx_ctx *ctx, int64_t out[4]);
 /* Self-test hook: room of the triangle render's list of large pixel boxes from the next render on
  * (0: everything large is swept in place; -1: the default sizing), and of arvx_render's list of large
  * footprints.  The room changes the time, never the images. */
@@ -1110,7 +1148,8 @@ int arvx_selftest_compute_units(arvx_ctx *ctx, int n);
  * box exceeds 64 pixels (16 bytes each; what does not fit is swept by the wave that found it, and
  * arvx_selftest_render_mesh_list bounds this list too); W * H * 4 bytes for a depth download.
  * Out of scope (per-face textures are the next block's): view weighting by surface normal, blending
- * across seams, a caller's mesh (arvx_render_triangles), near-plane clipping, slabs and multi-GPU,
+ * across seams, a caller's mesh (arvx_render_triangles), near-plane clipping (the depth pass ignores
+ * arvx_ctx_set_render_near: the plane is the drawing's alone), slabs and multi-GPU,
  * writing the colours back into the meshes' own vertex_rgb or the voxel colour list. */
 #define ARVX_MESH_COLOR_FOREGROUND 1u /* flags of arvx_mesh_color */
 #define ARVX_MESH_IMAGE_COLORS 0x100  /* OR-ed into `source` of the arvx_render_mesh family */
@@ -1186,7 +1225,8 @@ int arvx_selftest_mesh_color_batch(arvx_ctx *ctx, int views_per_batch);
  * list of large boxes are arvx_mesh_color's, bounded by the same two self-test hooks.
  * Out of scope: blending across the seams between faces that chose different views, view weighting by
  * normals, mip levels, packing by projected area, charts larger than one face, a caller's mesh,
- * near-plane clipping, slabs and multi-GPU. */
+ * near-plane clipping (filling the atlas ignores arvx_ctx_set_render_near; drawing with
+ * ARVX_MESH_TEXTURED honours it), slabs and multi-GPU. */
 #define ARVX_MESH_TEXTURE_FOREGROUND 1u /* flags of arvx_mesh_texture */
 #define ARVX_MESH_TEXTURED 0x400       /* OR-ed into `source` of the arvx_render_mesh family */
 #define ARVX_MESH_TEXTURE_MAX_RESOLUTION 253

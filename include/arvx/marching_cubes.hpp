@@ -739,6 +739,35 @@ inline RenderedView renderMesh(Model *model, int source, const float M[12], int 
     return detail::rendered_view(ctx, W, H);
 }
 
+// The near plane of the model's triangle renders (arvx_ctx_set_render_near, defined in
+// include/arvx/arvx.h): from the next renderMesh of either form on, faces that cross a2 = near are
+// clipped against it in place of being refused, so a camera may stand inside the mesh.  0: none (the
+// default).  The setting lives in the model's context: colorMesh, textureMesh and renderWelded ignore
+// it.  An invalid value throws with the library's message.
+inline void setRenderNear(Model *model, float near) {
+    detail::check(arvx_ctx_set_render_near(model->device_for_reading(), near), "arvx_ctx_set_render_near");
+}
+
+inline float renderNear(Model *model) {
+    float near = 0.f;
+    detail::check(arvx_ctx_render_near(model->device_for_reading(), &near), "arvx_ctx_render_near");
+    return near;
+}
+
+// What the near plane did to the faces of the model's current triangle render
+// (arvx_render_mesh_clip_stats); zeros for a render made without a plane.
+struct RenderClipStats {
+    int64_t behind = 0, straddling = 0, pieces = 0, piecesDrawn = 0;
+};
+
+inline RenderClipStats renderMeshClipStats(Model *model) {
+    int64_t out[4] = {0, 0, 0, 0};
+    detail::check(arvx_render_mesh_clip_stats(model->device_for_reading(), out), "arvx_render_mesh_clip_stats");
+    RenderClipStats st;
+    st.behind = out[0], st.straddling = out[1], st.pieces = out[2], st.piecesDrawn = out[3];
+    return st;
+}
+
 // ---- mesh colours from the images (an extension beyond the reference) -----------------------------
 //
 // The vertices of the mesh `source` that the model's context holds, coloured from the views' images

@@ -196,6 +196,11 @@ bool render_views(const std::string &dir, const Inputs &in, arvx::Model &model, 
         const arvx::RenderedView out =
             mesh_source < 0 ? arvx::renderWelded(&model, M, W, H, over ? bg.data() : nullptr)
                             : arvx::renderMesh(&model, mesh_source, M, W, H, over ? bg.data() : nullptr, light);
+        if (mesh_source >= 0 && arvx::renderNear(&model) > 0.f) {  // -near=D: what the plane did to the faces
+            const arvx::RenderClipStats st = arvx::renderMeshClipStats(&model);
+            std::cout << "LOG - RENDER CLIP: view " << i << " behind " << st.behind << " straddling " << st.straddling
+                      << " pieces " << st.pieces << " drawn " << st.piecesDrawn << std::endl;
+        }
         rgb.resize(out.bgr.size());
         for (size_t p = 0; p < out.bgr.size(); p += 3) {
             rgb[p] = out.bgr[p + 2];
@@ -258,7 +263,7 @@ int main(int argc, char *argv[]) {
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
         {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"},
-        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"renderMesh", "false"},
+        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"renderMesh", "false"}, {"near", "0"},
         {"meshColor", ""}, {"meshForeground", "false"}, {"texture", "0"}, {"atlasWidth", "4096"},
         {"segment", ""}, {"segLo", "120,120,120"}, {"segHi", "255,255,255"}, {"plates", ""}, {"segThreshold", "30"},
         {"segOpen", "0"}, {"segClose", "0"}, {"segMinArea", "0"}, {"segLargest", "false"}, {"segMaxHole", "0"},
@@ -297,6 +302,9 @@ int main(int argc, char *argv[]) {
                      "  -renderMesh=true (with -render: the triangles of the mesh the run wrote -- refined,\n"
                      "    decimated, smoothed, else welded -- with a depth buffer and a light at the camera,\n"
                      "    in place of the welded model's voxels),\n"
+                     "  -near=D (with -render and -renderMesh=true: faces that cross the plane at depth D in front of\n"
+                     "    a camera are clipped against it, not refused, so a camera may stand inside the mesh;\n"
+                     "    0, the default: off),\n"
                      "  -meshColor=closest|average (with -render and -renderMesh=true: the mesh's vertices\n"
                      "    coloured from the input images -- per view the depth buffer of the mesh itself, per\n"
                      "    vertex a vote over the views that see it within -visibleTol voxel edges, sampled\n"
@@ -701,6 +709,9 @@ int main(int argc, char *argv[]) {
             }
             if (mesh_source >= 0) drawn = mesh_source | ARVX_MESH_TEXTURED;
         }
+        // -near=D: the triangle renders' near plane (the library refuses an invalid one)
+        if (mesh_source >= 0 && !parser.str("render").empty() && parser.str("near") != "0")
+            arvx::setRenderNear(&model, parser.f("near"));
         if (!parser.str("render").empty() && !render_views(parser.str("render"), in, model, drawn)) return 1;
     } catch (const arvx::Error &e) {
         return 3;  // (already logged)
