@@ -61,6 +61,7 @@ def build_host_tests() -> str:
     build_mesh_color_host_test()
     build_mesh_texture_host_test()
     build_segment_host_test()
+    build_mesh_relax_host_test()
     return os.path.join(ROOT, "tests", "cpp", "test_host")
 
 
@@ -127,6 +128,13 @@ def build_segment_host_test() -> str:
     """g++ -> tests/cpp/test_segment_host: arvx::segmentViews (include/arvx/segmentation.hpp) on a
     scene from a file, built as build_weld_host_test builds its test."""
     return _build_host_test("test_segment_host")
+
+
+def build_mesh_relax_host_test() -> str:
+    """g++ -> tests/cpp/test_mesh_relax_host: arvx::relaxMesh, both overloads
+    (include/arvx/marching_cubes.hpp), on a scene from a file, built as build_weld_host_test builds its
+    test."""
+    return _build_host_test("test_mesh_relax_host")
 
 
 def _build_host_test(name: str) -> str:

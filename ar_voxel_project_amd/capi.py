@@ -55,6 +55,7 @@ MESH_WELDED = 0
 MESH_SMOOTHED = 1
 MESH_DECIMATED = 2
 MESH_REFINED = 3
+MESH_RELAXED = 5  # mesh_relax()'s product: its base's faces and colours, the relaxed positions
 MESH_IMAGE_COLORS = 0x100  # OR-ed into `source` of the render_mesh family: draw mesh_color()'s colours
 MESH_COLOR_FOREGROUND = 1  # flags of mesh_color
 MESH_TEXTURED = 0x400  # OR-ed into `source` of the render_mesh family: draw mesh_texture()'s atlas
@@ -105,6 +106,7 @@ SYMBOLS = [
     "arvx_mesh_color", "arvx_mesh_color_count", "arvx_mesh_color_download", "arvx_mesh_color_depth_download",
     "arvx_selftest_mesh_color_batch",
     "arvx_mesh_texture", "arvx_mesh_texture_info", "arvx_mesh_texture_download",
+    "arvx_mesh_relax", "arvx_mesh_relax_info", "arvx_mesh_relax_download", "arvx_mesh_relax_triangles",
     "arvx_occupancy_packet_words", "arvx_occupancy_compress", "arvx_occupancy_expand",
     "arvx_occupancy_expand_striped", "arvx_occupancy_pack_compress", "arvx_occupancy_expand_striped_others",
     "arvx_export_model", "arvx_get_stats", "arvx_last_carve_path", "arvx_last_fast_carve_path",
@@ -330,6 +332,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         lib.arvx_mesh_texture.argtypes = [p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint, C.POINTER(C.c_int64)]
         lib.arvx_mesh_texture_info.argtypes = [p, C.POINTER(C.c_int64)]
         lib.arvx_mesh_texture_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "arvx_mesh_relax") or not ab_build:
+        lib.arvx_mesh_relax.argtypes = [p, C.c_int, C.c_int, C.c_float, C.c_float]
+        lib.arvx_mesh_relax_info.argtypes = [p, C.POINTER(C.c_int64)]
+        lib.arvx_mesh_relax_download.argtypes = [p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.arvx_mesh_relax_triangles.argtypes = [p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int,
+                                                  C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(lib, "arvx_segment_views") or not ab_build:
         sp = C.POINTER(SegmentParams)
         lib.arvx_segment_views.argtypes = [p, C.c_int, f32p, f32p, C.c_void_p, C.c_int, C.c_int, C.c_size_t,
@@ -1219,6 +1227,47 @@ class Context:
                                                  lt.ctypes.data if lt is not None else None))
         self._render_wh = (int(W), int(H))
         return self.render_download() if download else None
+
+    def mesh_relax(self, source: int, iterations: int = 1, lam: float = 0.5, mu: float = -0.53,
+                   download: bool = True):
+        """arvx_mesh_relax: Taubin smoothing and vertex normals of the context's mesh `source` (MESH_WELDED,
+        MESH_SMOOTHED, MESH_DECIMATED, MESH_REFINED) -- mc_mesh_smooth's definition on any of them.
+        Returns mesh_relax_download()'s tuple; download=False: the call only, the product stays on the
+        device.  MESH_RELAXED then names it as a source of render_mesh, mesh_color and mesh_texture."""
+        self._ck(self._lib.arvx_mesh_relax(self._h, int(source), int(iterations), float(lam), float(mu)))
+        return self.mesh_relax_download() if download else None
+
+    def mesh_relax_info(self) -> Tuple[int, int, int]:
+        """arvx_mesh_relax_info: (base source, V, T) of the relaxed mesh."""
+        out = (C.c_int64 * 3)()
+        self._ck(self._lib.arvx_mesh_relax_info(self._h, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def mesh_relax_download(self, verts: bool = True, normals: bool = True, degree: bool = True):
+        """arvx_mesh_relax_download: (verts (V, 3) float32, normals (V, 3) float32, degree (V,) int32), each
+        or None."""
+        nv = self.mesh_relax_info()[1]
+        v = np.empty((nv, 3), np.float32) if verts else None
+        n = np.empty((nv, 3), np.float32) if normals else None
+        d = np.empty(nv, np.int32) if degree else None
+        self._ck(self._lib.arvx_mesh_relax_download(
+            self._h, *(a.ctypes.data if a is not None else None for a in (v, n, d))))
+        return v, n, d
+
+    def mesh_relax_triangles(self, verts, faces, iterations: int = 1, lam: float = 0.5, mu: float = -0.53):
+        """arvx_mesh_relax_triangles: mesh_relax() of a caller's mesh -- verts (V, 3) float32, faces (T, 3)
+        vertex indices or (T, 6) face records.  Returns (verts, normals, degree); the context's own
+        relaxed mesh stays as it was."""
+        v = _f32(verts).reshape(-1, 3)
+        f = np.asarray(faces)
+        rec = np.zeros((len(f), 6), np.uint32)
+        if len(f):
+            rec[:, :f.shape[1]] = f
+        q, n, d = np.empty_like(v), np.empty_like(v), np.empty(len(v), np.int32)
+        self._ck(self._lib.arvx_mesh_relax_triangles(self._h, len(v), v.ctypes.data, len(rec), rec.ctypes.data,
+                                                     int(iterations), float(lam), float(mu), q.ctypes.data,
+                                                     n.ctypes.data, d.ctypes.data))
+        return q, n, d
 
     def render_mesh_stats(self) -> Tuple[int, int, int, int]:
         """arvx_render_mesh_stats: (drawn, empty, flat, refused) triangles of the current triangle render."""

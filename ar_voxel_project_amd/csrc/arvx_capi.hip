@@ -38,6 +38,7 @@
 #include "mc_mesh_kernels.h"
 #include "mc_weld_kernels.h"
 #include "mc_smooth_kernels.h"
+#include "mesh_relax_kernels.h"
 #include "mc_decimate_kernels.h"
 #include "mc_refine_kernels.h"
 #include "visibility_kernels.h"
@@ -3909,6 +3910,8 @@ int arvx_mc_mesh_welded(arvx_ctx *ctx, int apply_unseen, int64_t *vertices, int6
     ctx->render_ready = false;                           // (... and the old one's render goes)
     for (int src : {ARVX_MESH_WELDED, ARVX_MESH_SMOOTHED, ARVX_MESH_DECIMATED})
         ctx->mesh_color_ended(src);                      // (... and the image colours of the three)
+    for (int src : {ARVX_MESH_WELDED, ARVX_MESH_SMOOTHED, ARVX_MESH_DECIMATED})
+        ctx->relax_ended(src);                           // (... and a relaxed mesh made of one of them)
     ctx->weld_verts = ctx->weld_tris = 0;
     *vertices = *triangles = 0;
     const arvx::BitGrid g = bit_grid(ctx);
@@ -3990,6 +3993,7 @@ int arvx_mc_mesh_smooth(arvx_ctx *ctx, int iterations, float lambda, float mu) {
     if (!ctx->weld_ready) return fail(ARVX_ERR_STATE, "no welded mesh (call arvx_mc_mesh_welded)");
     ctx->smooth_ready = false;
     ctx->mesh_color_ended(ARVX_MESH_SMOOTHED);
+    ctx->relax_ended(ARVX_MESH_SMOOTHED);
     const long long V = ctx->weld_verts, T = ctx->weld_tris;
     if (V == 0) {
         ctx->smooth_q = 0;
@@ -4032,6 +4036,7 @@ int arvx_mc_mesh_smooth_download(arvx_ctx *ctx, float *verts, float *normals) {
     if (int rc = check_fault(ctx)) {  // (a scan gave up: the CSRs are built again)
         ctx->smooth_ready = ctx->smooth_csr_ready = false;
         ctx->mesh_color_ended(ARVX_MESH_SMOOTHED);
+        ctx->relax_ended(ARVX_MESH_SMOOTHED);
         return rc;
     }
     return ARVX_OK;
@@ -4051,6 +4056,7 @@ int arvx_mc_mesh_decimate(arvx_ctx *ctx, int cell, int source, int64_t *vertices
         return fail(ARVX_ERR_STATE, "no smoothed mesh on this welded mesh (call arvx_mc_mesh_smooth)");
     ctx->dec_ready = false;
     ctx->mesh_color_ended(ARVX_MESH_DECIMATED);
+    ctx->relax_ended(ARVX_MESH_DECIMATED);
     ctx->dec_verts = ctx->dec_tris = 0;
     const long long V = ctx->weld_verts, T = ctx->weld_tris;
     if (V == 0) {
@@ -4155,6 +4161,7 @@ int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_
     ctx->free_mc();
     ctx->ref_ready = false;
     ctx->mesh_color_ended(ARVX_MESH_REFINED);
+    ctx->relax_ended(ARVX_MESH_REFINED);
     ctx->ref_verts = ctx->ref_tris = 0;
     *vertices = *triangles = 0;
     const arvx::BitGrid g = bit_grid(ctx);
@@ -4403,6 +4410,11 @@ static int mesh_source(const Ctx *ctx, int source, MeshSource &m, bool image_col
         m = MeshSource{ctx->pool_ref_verts.data(), ctx->pool_ref_rgb.data(), ctx->pool_ref_faces.data(),
                        ctx->ref_verts, ctx->ref_tris};
         break;
+    case ARVX_MESH_RELAXED:  // the faces and colours of the product's base with the product's positions
+        if (!ctx->relax_ready) return fail(ARVX_ERR_STATE, "no relaxed mesh (call arvx_mesh_relax)");
+        if (int rc = mesh_source(ctx, ctx->relax_base, m, false)) return rc;  // (it ends with its base)
+        if (ctx->relax_q != 0) m.verts = ctx->relax.xyz(ctx->relax_q);
+        break;
     default:
         return fail(ARVX_ERR_INVALID, "unknown mesh source %d", source);
     }
@@ -4416,6 +4428,174 @@ static int mesh_source(const Ctx *ctx, int source, MeshSource &m, bool image_col
             return fail(ARVX_ERR_STATE, "no texture of mesh source %d (call arvx_mesh_texture)", base);
         m.textured = true;  // (a cell half per face of the source: the product ends with them)
     }
+    return ARVX_OK;
+}
+
+// ---- relaxed mesh (mesh_relax_kernels.h) -----------------------------------------------------
+
+// The neighbour CSR and the incidence CSR of the mesh `faces` (V > 0 vertices, T faces) into r.  Every
+// buffer is sized from V and T (6 T neighbour slots, 3 T incidences, a listed row per 49 of either),
+// so no count comes back: launches only.
+static int relax_csr(Ctx *ctx, Ctx::Relax &r, const unsigned *faces, long long V, long long T) {
+    r.V = V, r.T = T;
+    const long long ncap = r.ncap(), icap = r.icap();
+    const int nrows_cap = r.nrows_cap(), irows_cap = r.irows_cap();
+    ARVX_HIP(r.csr.reserve(r.csr_bytes()));
+    ARVX_HIP(r.nbr.reserve((size_t)std::max(ncap, 1ll) * sizeof(unsigned)));
+    ARVX_HIP(r.inc.reserve((size_t)std::max(icap, 1ll) * sizeof(unsigned)));
+    ARVX_HIP(r.rows.reserve((size_t)(nrows_cap + irows_cap) * sizeof(int)));
+    int *degree = r.degree(), *icount = r.icount(), *noff = r.noff(), *ioff = r.ioff();
+    int *nrows = r.rows.data(), *irows = nrows + nrows_cap;
+    const unsigned blocks_v = blocks_for(V), blocks_t = blocks_for(T);
+    // (the row counters and both count arrays: all that lies before the offsets)
+    ARVX_HIP(hipMemsetAsync(r.csr.data(), 0, (size_t)(noff - r.csr.data()) * sizeof(int), ctx->stream));
+    if (T > 0) ARVX_TRY(launch(ctx, arvx::mesh_relax_count_kernel, blocks_t, 256, faces, T, V, degree, icount));
+    // (a total no call reads)
+    if (int rc = scan_counts(ctx, degree, nullptr, V + 1, nullptr, noff, Ctx::kRelaxScan, nullptr)) return rc;
+    if (int rc = scan_counts(ctx, icount, nullptr, V + 1, nullptr, ioff, Ctx::kRelaxScan, nullptr)) return rc;
+    if (T > 0)
+        ARVX_TRY(launch(ctx, arvx::mesh_relax_fill_kernel, blocks_t, 256, faces, T, V, degree, icount, noff, ioff,
+                        ncap, icap, r.nbr.data(), r.inc.data()));
+    // the rows: a lane each, then the listed ones a workgroup each (the grid strides over the list)
+    const int ncu = compute_units(ctx);
+    ARVX_TRY(launch(ctx, arvx::mesh_relax_rows_kernel<true>, blocks_v, 256, noff, V, ncap, r.nbr.data(), degree,
+                    nrows, r.n_rows(), nrows_cap));
+    if (ncap > arvx::kRelaxLaneRow)
+        ARVX_TRY(launch(ctx, arvx::mesh_relax_long_rows_kernel<true>, (unsigned)std::min(nrows_cap, 2 * ncu), 256,
+                        noff, V, ncap, r.nbr.data(), degree, nrows, r.n_rows(), nrows_cap));
+    ARVX_TRY(launch(ctx, arvx::mesh_relax_rows_kernel<false>, blocks_v, 256, ioff, V, icap, r.inc.data(), nullptr,
+                    irows, r.n_rows() + 1, irows_cap));
+    if (icap > arvx::kRelaxLaneRow)
+        ARVX_TRY(launch(ctx, arvx::mesh_relax_long_rows_kernel<false>, (unsigned)std::min(irows_cap, 2 * ncu), 256,
+                        ioff, V, icap, r.inc.data(), nullptr, irows, r.n_rows() + 1, irows_cap));
+    return ARVX_OK;
+}
+
+// The steps from positions p0 and the normals of the final positions, on r's CSRs; *q: where the
+// final positions are (0: p0 itself, else r.xyz(*q)).  Launches only.
+static int relax_run(Ctx *ctx, Ctx::Relax &r, const float *p0, const unsigned *faces, int iterations, float lambda,
+                     float mu, int *q_out) {
+    const long long V = r.V, T = r.T;
+    const unsigned blocks_v = blocks_for(V), blocks_t = blocks_for(T);
+    if (iterations > 0) ARVX_HIP(r.verts.reserve((size_t)2 * V * Ctx::kVertexBytes));
+    const float *in = p0;
+    int q = 0;
+    for (int s = 0; s < 2 * iterations; ++s) {
+        const int next = q == 1 ? 2 : 1;
+        ARVX_TRY(launch(ctx, arvx::mesh_relax_step_kernel, blocks_v, 256, in, V, r.noff(), r.degree(), r.ncap(),
+                        r.nbr.data(), (s & 1) ? mu : lambda, r.xyz(next)));
+        q = next;
+        in = r.xyz(q);
+    }
+    ARVX_HIP(r.cross.reserve((size_t)std::max(3 * T, 1ll) * sizeof(float)));
+    ARVX_HIP(r.normals.reserve((size_t)V * Ctx::kVertexBytes));
+    if (T > 0) ARVX_TRY(launch(ctx, arvx::mc_smooth_cross_kernel, blocks_t, 256, faces, T, in, V, r.cross.data()));
+    ARVX_TRY(launch(ctx, arvx::mc_smooth_normal_kernel, blocks_v, 256, r.ioff(), V, r.icap(), r.inc.data(),
+                    r.cross.data(), T, r.normals.data()));
+    *q_out = q;
+    return ARVX_OK;
+}
+
+static int relax_arguments(int iterations, float lambda, float mu) {
+    if (iterations < 0 || !std::isfinite(lambda) || !std::isfinite(mu))
+        return fail(ARVX_ERR_INVALID, "iterations must be >= 0 and the factors finite");
+    return ARVX_OK;
+}
+
+int arvx_mesh_relax(arvx_ctx *ctx, int source, int iterations, float lambda, float mu) {
+    ARVX_CHECK_CTX(ctx);
+    if (int rc = relax_arguments(iterations, lambda, mu)) return rc;
+    if (source == ARVX_MESH_RELAXED) return fail(ARVX_ERR_INVALID, "the relaxed mesh cannot be its own source");
+    MeshSource m;
+    if (int rc = mesh_source(ctx, source, m, false)) return rc;
+    if (6 * m.T > (long long)INT32_MAX || 3 * m.V > (long long)INT32_MAX)
+        return fail(ARVX_ERR_STATE, "the mesh is too long: 6 T or 3 V > INT32_MAX (the CSR offsets are 32-bit)");
+    ctx->relax_ready = false;
+    ctx->mesh_color_ended(ARVX_MESH_RELAXED);
+    // (the smoothed mesh has the welded mesh's faces: one adjacency for both)
+    const int faces_of = source == ARVX_MESH_SMOOTHED ? ARVX_MESH_WELDED : source;
+    int q = 0;
+    if (m.V == 0) {
+        ctx->relax_csr_ready = false;
+        ctx->relax.V = ctx->relax.T = 0;
+    } else {
+        if (!ctx->relax_csr_ready || ctx->relax_csr_base != faces_of) {
+            ctx->relax_csr_ready = false;
+            if (int rc = relax_csr(ctx, ctx->relax, m.faces, m.V, m.T)) return rc;
+            ctx->relax_csr_base = faces_of;
+            ctx->relax_csr_ready = true;
+        }
+        if (int rc = relax_run(ctx, ctx->relax, m.verts, m.faces, iterations, lambda, mu, &q)) return rc;
+    }
+    ctx->relax_base = source;
+    ctx->relax_q = q;
+    ctx->relax_ready = true;
+    return ARVX_OK;
+}
+
+int arvx_mesh_relax_info(arvx_ctx *ctx, int64_t out[3]) {
+    ARVX_CHECK_CTX(ctx);
+    if (!out) return fail(ARVX_ERR_INVALID, "null out");
+    MeshSource m;
+    if (int rc = mesh_source(ctx, ARVX_MESH_RELAXED, m, false)) return rc;
+    out[0] = ctx->relax_base;
+    out[1] = m.V;
+    out[2] = m.T;
+    return ARVX_OK;
+}
+
+int arvx_mesh_relax_download(arvx_ctx *ctx, float *verts, float *normals, int32_t *degree) {
+    ARVX_CHECK_CTX(ctx);
+    MeshSource m;
+    if (int rc = mesh_source(ctx, ARVX_MESH_RELAXED, m, false)) return rc;
+    const size_t V = (size_t)m.V;
+    ARVX_TRY(download(ctx, verts, m.verts, V, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, normals, ctx->relax.normals.data(), V, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, degree, ctx->relax.degree(), V, sizeof(int)));
+    ARVX_HIP(hipStreamSynchronize(ctx->stream));
+    if (int rc = check_fault(ctx)) {  // (a scan gave up: the CSRs are built again)
+        ctx->relax_ready = ctx->relax_csr_ready = false;
+        ctx->mesh_color_ended(ARVX_MESH_RELAXED);
+        return rc;
+    }
+    return ARVX_OK;
+}
+
+int arvx_mesh_relax_triangles(arvx_ctx *ctx, int64_t nv, const float *verts, int64_t nt, const uint32_t *faces,
+                              int iterations, float lambda, float mu, float *out_verts, float *out_normals,
+                              int32_t *out_degree) {
+    ARVX_CHECK_CTX(ctx);
+    if (!whole_grid(ctx)) return fail(ARVX_ERR_STATE, "arvx_mesh_relax_triangles needs a whole-grid context");
+    if (int rc = relax_arguments(iterations, lambda, mu)) return rc;
+    if (nv < 0 || nt < 0) return fail(ARVX_ERR_INVALID, "a negative count");
+    if ((nv > 0 && !verts) || (nt > 0 && !faces)) return fail(ARVX_ERR_INVALID, "null mesh array");
+    if (nt > (int64_t)INT32_MAX / 6 || nv > (int64_t)INT32_MAX / 3)
+        return fail(ARVX_ERR_INVALID, "the mesh is too long: 6 nt or 3 nv > INT32_MAX (the CSR offsets are 32-bit)");
+    for (int64_t t = 0; t < nt; ++t)
+        for (int k = 0; k < 3; ++k)
+            if ((int64_t)faces[6 * t + k] >= nv)
+                return fail(ARVX_ERR_INVALID, "face %lld: index %u >= nv", (long long)t, faces[6 * t + k]);
+    for (int64_t k = 0; k < 3 * nv; ++k)
+        if (!(std::fabs(verts[k]) <= 1048576.f))  // (a NaN fails the comparison too)
+            return fail(ARVX_ERR_INVALID, "vertex %lld: a coordinate that is not finite or above 2^20 in magnitude",
+                        (long long)(k / 3));
+    if (nv == 0) return ARVX_OK;  // (no face either: there is nothing to return)
+    Ctx::Relax &r = ctx->relax_tri;
+    ARVX_HIP(ctx->pool_rtri_verts.reserve((size_t)nv * Ctx::kVertexBytes));
+    ARVX_HIP(ctx->pool_rtri_faces.reserve((size_t)std::max<int64_t>(nt, 1) * Ctx::kFaceBytes));
+    ARVX_HIP(hipMemcpyAsync(ctx->pool_rtri_verts.p, verts, (size_t)nv * Ctx::kVertexBytes, hipMemcpyHostToDevice,
+                            ctx->stream));
+    if (nt > 0)
+        ARVX_HIP(hipMemcpyAsync(ctx->pool_rtri_faces.p, faces, (size_t)nt * Ctx::kFaceBytes, hipMemcpyHostToDevice,
+                                ctx->stream));
+    int q = 0;
+    if (int rc = relax_csr(ctx, r, ctx->pool_rtri_faces.data(), nv, nt)) return rc;
+    if (int rc = relax_run(ctx, r, ctx->pool_rtri_verts.data(), ctx->pool_rtri_faces.data(), iterations, lambda, mu, &q))
+        return rc;
+    ARVX_TRY(download(ctx, out_verts, q == 0 ? ctx->pool_rtri_verts.data() : r.xyz(q), (size_t)nv, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, out_normals, r.normals.data(), (size_t)nv, Ctx::kVertexBytes));
+    ARVX_TRY(download(ctx, out_degree, r.degree(), (size_t)nv, sizeof(int)));
+    ARVX_SYNC(ctx);
     return ARVX_OK;
 }
 

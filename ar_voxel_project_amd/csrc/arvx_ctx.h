@@ -83,6 +83,7 @@ struct Ctx {
         kComponents,                    // the component table's length (arvx_components[_keep])
         kDecVerts, kDecTris,            // arvx_mc_mesh_decimate: decimated vertices, surviving faces
         kRefVerts,                      // arvx_mc_mesh_refined: cut edges (kCells and kTris carry its other lists)
+        kRelaxScan,                     // arvx_mesh_relax's offset scans: a total nobody reads
         kDeviceTotals,
         kPhotoRemoved = kDeviceTotals,  // voxels an iteration of arvx_photo_carve removed
         kVisNeed,                       // large footprints the visible pass wanted to list
@@ -339,7 +340,7 @@ struct Ctx {
     // those calls against it.  Every entry point calls drop() once, after its refusals and before its
     // work, so that a refused call leaves the context as it was.  (The closure calls it where its fills
     // go into the state: the colour pass's planes it starts from are those of the state before.)  The
-    // mesh products (mc_ready, weld_ready, smooth_*, dec_ready, ref_ready) are not here: each lives until the next
+    // mesh products (mc_ready, weld_ready, smooth_*, dec_ready, ref_ready, relax_ready) are not here: each lives until the next
     // call of its own stage (CtxModel holds them as well, and the sequences download them after other calls).  The render of the welded mesh (arvx_render) is: it shows the state the
     // mesh was built from, so whatever replaces that state drops it (and so does the next
     // arvx_mc_mesh_welded).
@@ -460,6 +461,48 @@ struct Ctx {
     int *smooth_ioff() const { return smooth_noff() + weld_verts + 1; }
     float *smooth_xyz(int q) const {  // 0: the welded mesh's own positions, 1 / 2: a buffer
         return q == 0 ? pool_weld_verts.data() : pool_smooth_verts.data() + (q - 1) * 3 * weld_verts;
+    }
+    // arvx_mesh_relax / arvx_mesh_relax_triangles (mesh_relax_kernels.h): the CSRs of one mesh of V vertices
+    // and T faces -- two counters of listed rows (and two ints of padding), then V + 1 ints each of neighbour
+    // counts (the degrees once the rows are finished), incidence counts, neighbour offsets, incidence offsets;
+    // the neighbour list (6 T slots) and the incidence list (3 T); the listed rows (neighbour rows, then
+    // incidence rows) --, two position buffers, cross products, normals.  V, T: what the layout was made for.
+    struct Relax {
+        DevArray<int> csr, rows;
+        DevArray<unsigned> nbr, inc;
+        DevArray<float> verts, cross, normals;
+        int64_t V = 0, T = 0;
+        size_t csr_bytes() const { return (size_t)(4 * (V + 1) + 4) * sizeof(int); }
+        int *n_rows() const { return csr.data(); }  // [0] neighbour rows listed, [1] incidence rows
+        int *degree() const { return csr.data() + 4; }
+        int *icount() const { return degree() + V + 1; }
+        int *noff() const { return icount() + V + 1; }
+        int *ioff() const { return noff() + V + 1; }
+        long long ncap() const { return 6 * T; }
+        long long icap() const { return 3 * T; }
+        // (a listed row has more than kRelaxLaneRow = 48 slots)
+        int nrows_cap() const { return (int)(ncap() / 49 + 1); }
+        int irows_cap() const { return (int)(icap() / 49 + 1); }
+        float *xyz(int q) const { return verts.data() + (q - 1) * 3 * V; }  // q = 1, 2: a buffer
+    };
+    // relax: the context's product, "the relaxed mesh" -- positions (those of its base where relax_q == 0,
+    // else relax.xyz(relax_q)), normals, degrees; read only while relax_ready is set -- and the CSRs of the
+    // mesh whose faces relax_csr_base names (ARVX_MESH_WELDED for the welded faces, _DECIMATED, _REFINED),
+    // current while relax_csr_ready is set.  relax_tri: a caller's mesh, nothing kept between calls.
+    // relax_ended(source) is called where a mesh stage replaces or drops the arrays of `source`.
+    Relax relax, relax_tri;
+    DevArray<float> pool_rtri_verts;
+    DevArray<unsigned> pool_rtri_faces;
+    bool relax_ready = false, relax_csr_ready = false;
+    int relax_base = 0, relax_csr_base = 0, relax_q = 0;
+    void relax_ended(int source) {
+        constexpr int kSmoothed = 1, kRelaxed = 5;  // (ARVX_MESH_SMOOTHED, ARVX_MESH_RELAXED: arvx.h)
+        if (relax_ready && relax_base == source) {
+            relax_ready = false;
+            mesh_color_ended(kRelaxed);
+        }
+        // (the smoothed mesh has the welded faces: its end alone leaves their CSRs)
+        if (source != kSmoothed && relax_csr_base == source) relax_csr_ready = false;
     }
     // arvx_mc_mesh_decimate: the cluster plane behind its dec_words ranks, the cluster list, the decimated
     // mesh, the welded vertices' map, the welded faces' flags and offsets (T each), the slot table

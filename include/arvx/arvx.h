@@ -692,7 +692,10 @@ int arvx_colors_upload(arvx_ctx *ctx, int64_t n, const int64_t *index, const flo
  *     arvx_components_keep or arvx_morph; the field of arvx_distance lives exactly as long;
  *   - arvx_morph with ERODE or OPEN drops exactly what arvx_components_keep drops; with DILATE or
  *     CLOSE it also drops what earlier carves settled for whole coarse tiles, as a state upload
- *     does, because it occupies voxels.
+ *     does, because it occupies voxels;
+ *   - the relaxed mesh (arvx_mesh_relax) lives until the next arvx_mesh_relax or the call that
+ *     replaces or ends its base mesh (arvx_mc_mesh_welded, and arvx_mc_mesh_smooth, _decimate or
+ *     _refined for the base each of them builds); none of the calls above touches it.
  * A closure that filled voxels leaves them occupied in the state.  Once its list is gone the
  * context no longer has their colours, which the reference's Model keeps: until a carve, fast
  * carve, upload or reset replaces the state, the calls that return colours (arvx_export_model,
@@ -901,13 +904,79 @@ int arvx_mc_mesh_decimate_download(arvx_ctx *ctx, float *verts, uint32_t *faces,
  * The refined mesh lives until the next arvx_mc_mesh_refined.  It is a snapshot of the state and the
  * views at the call and touches no other product -- the unwelded, welded, smoothed and decimated
  * meshes and a render stay as they were; like arvx_mc_mesh_welded it runs arvx_mc_cells itself.
- * Out of scope: smoothing or decimating this mesh (arvx_render_mesh draws it); normals; slabs and
- * multi-GPU; colour interpolation along the edge (arvx_mesh_color samples the photographs at the
- * vertex itself instead). */
+ * Out of scope: decimating this mesh (arvx_render_mesh draws it; arvx_mesh_relax smooths it and gives
+ * its normals); slabs and multi-GPU; colour interpolation along the edge (arvx_mesh_color samples the
+ * photographs at the vertex itself instead). */
 int arvx_mc_mesh_refined(arvx_ctx *ctx, int apply_unseen, int bisections, int64_t *vertices,
                          int64_t *triangles);
 int arvx_mc_mesh_refined_download(arvx_ctx *ctx, float *verts, uint32_t *faces, float *vertex_rgb,
                                   int32_t *edges, int32_t *cut);
+
+/* ---- relaxed mesh: Taubin smoothing and vertex normals of any mesh (extension beyond the reference) --
+ * arvx_mc_mesh_smooth's stage for every mesh with shared vertices the context holds, and for a caller's.
+ * Input: the V positions p (fp32) and the T faces (i0, i1, i2) of `source`, one of ARVX_MESH_WELDED,
+ * ARVX_MESH_SMOOTHED (the welded faces with the positions of the last arvx_mc_mesh_smooth),
+ * ARVX_MESH_DECIMATED, ARVX_MESH_REFINED: the positions and face records the arvx_render_mesh family
+ * draws for that source.  A source with an ARVX_MESH_IMAGE_COLORS or ARVX_MESH_TEXTURED bit, and
+ * ARVX_MESH_RELAXED itself, are ARVX_ERR_INVALID.
+ * Result: exactly the definition of arvx_mc_mesh_smooth (its block above: neighbours N(i), ascending,
+ * each once; the Jacobi step with factor f; Taubin as 2 * iterations steps with factors lambda, mu,
+ * lambda, mu, ...; the normals from the final positions q -- c_t per face, summed per vertex in
+ * ascending t from +0, then normalised, (0, 0, 0) when the length is 0), applied to that mesh, bit for
+ * bit, with every fp32 operation rounded on its own.  The mesh may have any valence, may hold a face
+ * more than once (each copy is a face of its own: it adds its c_t again and no neighbour) and faces
+ * with a repeated corner.  Such a face has a = 0 or b = 0 or a = b, so c_t = (+-0, +-0, +-0) for finite
+ * positions: it changes no sum that starts at +0, and the implementation leaves it out of the normals'
+ * sums as the welded one does; its distinct corners are neighbours of each other all the same.
+ * degree[i] = |N(i)|.  A vertex no face uses keeps its position, has normal (0, 0, 0) and degree 0.
+ * The sums of a vertex are serial, in the definition's order, whatever its valence: no result depends
+ * on the order the device's threads run in.
+ * Product: "the relaxed mesh" -- q (3 V floats), normals (3 V floats), degree (V int32) --, tagged with
+ * its base `source`; one per context.  arvx_mesh_relax does not synchronise.  arvx_mesh_relax_download
+ * synchronises; any of its pointers may be null.  arvx_mesh_relax_info returns the base source, V and
+ * T (ARVX_ERR_STATE without a product).
+ * ARVX_MESH_RELAXED as a source of arvx_render_mesh, _view, _agreement, arvx_mesh_color and
+ * arvx_mesh_texture (and, OR-ed with ARVX_MESH_IMAGE_COLORS or ARVX_MESH_TEXTURED, of the renders): the
+ * faces and vertex colours of the product's base mesh with the product's positions; ARVX_ERR_STATE
+ * without a product.
+ * Lifetime: the product is replaced by the next arvx_mesh_relax and ended by whatever replaces or ends
+ * its base -- base WELDED: arvx_mc_mesh_welded; SMOOTHED: arvx_mc_mesh_welded, arvx_mc_mesh_smooth;
+ * DECIMATED: arvx_mc_mesh_welded, arvx_mc_mesh_decimate; REFINED: arvx_mc_mesh_refined.  Nothing else
+ * touches it (a carve, an upload, new views, a render leave it), and it touches nothing else: the four
+ * meshes, the current render and arvx_mc_mesh_smooth's product stay as they are.  The image colours
+ * and the texture of source ARVX_MESH_RELAXED end where the product is replaced or ended.  A refused
+ * call leaves the previous product as it was.
+ * The adjacency (a neighbour CSR and an incidence CSR) is built on the device at the first call on a
+ * base mesh and reused by later calls that name the same faces (WELDED and SMOOTHED share theirs) while
+ * that mesh has not been built again.
+ * Refusals.  ARVX_ERR_STATE: the source mesh does not exist (slab and striped contexts never have
+ * one); 6 T or 3 V above INT32_MAX (the CSR offsets are 32-bit); info or download before a product.
+ * ARVX_ERR_INVALID: iterations < 0, a factor that is not finite, an unknown source (see above).
+ * arvx_mesh_relax_triangles does the same for a caller's mesh: nv positions (3 floats each) and nt face
+ * records of 6 uints, as the mesh downloads return them and arvx_render_triangles takes them (r, g, b
+ * are not read).  It copies the mesh in, relaxes it in buffers of its own, copies the three outputs
+ * out (any may be null) and synchronises; the context's relaxed mesh and everything else stay as they
+ * were.  Refused, on the host, before anything is enqueued -- ARVX_ERR_STATE: a slab or a striped
+ * context (as arvx_render_triangles); ARVX_ERR_INVALID: iterations < 0 or a factor that is not finite,
+ * a negative count, a null array with a non-zero count, 6 nt or 3 nv above INT32_MAX, a face index
+ * >= nv, a coordinate that is not finite or has |c| > 2^20 (so that no product of the normals
+ * overflows).  nv == 0 or nt == 0 is legal: positions unchanged, normals 0, degrees 0.
+ * Device memory, beside the base mesh: the CSRs -- 16 V + 36 T bytes (four arrays of V + 1 ints; 6 T
+ * neighbour slots and 3 T incidences of 4 bytes; rows are sorted in place and not compacted) and the
+ * list of rows longer than 48 slots (at most 4 bytes per 49 slots) --, kept with the product; the
+ * ping-pong positions 24 V (none for iterations == 0), the cross products 12 T, the normals 12 V; the
+ * degrees are the CSR's first array.  A caller's mesh takes the same again plus its copy, 12 nv + 24 nt.
+ * Out of scope: boundary pinning, constraining refined vertices to their edges, consuming the normals
+ * in the renders and the colour votes, slabs and multi-GPU. */
+/* (5, not 4: source 4 has been refused as unknown, ARVX_ERR_INVALID, by every call that takes a source, and
+ * callers rely on that; it stays unknown.) */
+#define ARVX_MESH_RELAXED 5 /* a source of the arvx_render_mesh / arvx_mesh_color / arvx_mesh_texture families */
+int arvx_mesh_relax(arvx_ctx *ctx, int source, int iterations, float lambda, float mu);
+int arvx_mesh_relax_info(arvx_ctx *ctx, int64_t out[3]); /* base source, V, T */
+int arvx_mesh_relax_download(arvx_ctx *ctx, float *verts, float *normals, int32_t *degree);
+int arvx_mesh_relax_triangles(arvx_ctx *ctx, int64_t nv, const float *verts, int64_t nt, const uint32_t *faces,
+                              int iterations, float lambda, float mu, float *out_verts, float *out_normals,
+                              int32_t *out_degree);
 
 /* ---- render (extension beyond the reference) -------------------------------------------------
  * Draws the welded mesh's vertex voxels into a camera view: the model over a photograph, the voxel
@@ -1004,7 +1073,8 @@ int arvx_render_agreement(arvx_ctx *ctx, int view, int64_t counts[3]);
  *     none).
  * Sources: ARVX_MESH_WELDED -- the mesh of arvx_mc_mesh_welded, lattice positions --,
  * ARVX_MESH_SMOOTHED -- the same faces and colours with the positions of the last arvx_mc_mesh_smooth
- * --, ARVX_MESH_DECIMATED -- arvx_mc_mesh_decimate's --, ARVX_MESH_REFINED -- arvx_mc_mesh_refined's.
+ * --, ARVX_MESH_DECIMATED -- arvx_mc_mesh_decimate's --, ARVX_MESH_REFINED -- arvx_mc_mesh_refined's
+ * --, ARVX_MESH_RELAXED -- the faces and colours of arvx_mesh_relax's base with its positions.
  * arvx_render_triangles draws a caller's mesh instead: nv positions and colours (3 floats each), nt
  * face records {i0, i1, i2, r, g, b} as the mesh downloads return them (r, g, b are not read); the
  * arrays are copied before the call returns, into buffers of their own.

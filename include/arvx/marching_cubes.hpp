@@ -910,6 +910,60 @@ inline RenderedView renderMesh(Model *model, const SimpleMesh &mesh, const float
     return detail::rendered_view(ctx, W, H);
 }
 
+// ---- relaxed mesh (an extension beyond the reference) ---------------------------------------------
+//
+// Taubin smoothing and vertex normals of the mesh `source` (ARVX_MESH_WELDED, _SMOOTHED, _DECIMATED,
+// _REFINED) that the model's context holds (arvx_mesh_relax, defined in include/arvx/arvx.h): the mesh
+// with the base's triangles and face colours and the relaxed vertices; normals, if not null, gets 3
+// floats per vertex.  A source the context does not hold throws.  renderMesh, colorMesh and textureMesh
+// then take ARVX_MESH_RELAXED as their source, until the base mesh is built again.
+inline SimpleMesh relaxMesh(Model *model, int source, int iterations = 1, float lambda = 0.5f, float mu = -0.53f,
+                            std::vector<float> *normals = nullptr) {
+    arvx_ctx *ctx = model->device_for_reading();
+    detail::check(arvx_mesh_relax(ctx, source, iterations, lambda, mu), "arvx_mesh_relax");
+    int64_t n[3] = {0, 0, 0};
+    detail::check(arvx_mesh_relax_info(ctx, n), "arvx_mesh_relax_info");
+    SimpleMesh mesh;
+    HostVector<Vec3f> &mv = mesh.GetVertices();
+    HostVector<Triangle> &mt = mesh.GetTriangles();
+    mv.resize((size_t)n[1]);  // (recycled memory, not zeroed: host_pool.hpp)
+    mt.resize((size_t)n[2]);
+    float *v = n[1] ? mv[0].data() : nullptr;
+    uint32_t *f = n[2] ? &mt[0].idx0 : nullptr;
+    static_assert(sizeof(Triangle) == 24, "a face record: three indices, then r, g, b");
+    // (the base's download for its faces; its positions land where the relaxed ones follow)
+    if (source == ARVX_MESH_DECIMATED)
+        detail::check(arvx_mc_mesh_decimate_download(ctx, v, f, nullptr, nullptr, nullptr), "arvx_mc_mesh_decimate_download");
+    else if (source == ARVX_MESH_REFINED)
+        detail::check(arvx_mc_mesh_refined_download(ctx, v, f, nullptr, nullptr, nullptr), "arvx_mc_mesh_refined_download");
+    else
+        detail::check(arvx_mc_mesh_welded_download(ctx, v, f, nullptr), "arvx_mc_mesh_welded_download");
+    if (normals) normals->resize(3 * (size_t)n[1]);
+    detail::check(arvx_mesh_relax_download(ctx, v, normals && n[1] ? normals->data() : nullptr, nullptr),
+                  "arvx_mesh_relax_download");
+    return mesh;
+}
+
+// The same for a mesh of the caller's, relaxed on the model's context (arvx_mesh_relax_triangles): its
+// vertices in any units within 2^20, as the marchingCubesMesh* calls return them.  The context's own
+// relaxed mesh stays as it was.
+inline SimpleMesh relaxMesh(Model *model, const SimpleMesh &mesh, int iterations = 1, float lambda = 0.5f,
+                            float mu = -0.53f, std::vector<float> *normals = nullptr) {
+    arvx_ctx *ctx = model->device_for_reading();
+    SimpleMesh out = mesh;
+    const HostVector<Vec3f> &mv = mesh.GetVertices();
+    const HostVector<Triangle> &mt = mesh.GetTriangles();
+    HostVector<Vec3f> &ov = out.GetVertices();
+    if (normals) normals->resize(3 * mv.size());
+    static_assert(sizeof(Triangle) == 24, "a face record: three indices, then r, g, b");
+    detail::check(arvx_mesh_relax_triangles(ctx, (int64_t)mv.size(), mv.empty() ? nullptr : mv[0].data(),
+                                            (int64_t)mt.size(), mt.empty() ? nullptr : &mt[0].idx0, iterations, lambda,
+                                            mu, ov.empty() ? nullptr : ov[0].data(),
+                                            normals && !mv.empty() ? normals->data() : nullptr, nullptr),
+                  "arvx_mesh_relax_triangles");
+    return out;
+}
+
 namespace detail {
 // carve(..., intermediateMeshes = true) without a caller-supplied hook writes what the
 // reference writes after every view (src/VoxelCarving.cpp:65-68): the model so far, moved

@@ -263,7 +263,7 @@ int main(int argc, char *argv[]) {
         {"intermediateMesh", "false"}, {"outFile", "./out/mesh.off"}, {"undistort", "false"}, {"weld", "false"},
         {"smooth", "0"}, {"decimate", "0"}, {"visible", "false"}, {"visibleTol", "3"}, {"photo", "0"}, {"photoViews", "2"},
         {"photoIters", "32"}, {"render", ""}, {"misses", "0"}, {"floaters", "0"}, {"largest", "false"},
-        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"renderMesh", "false"}, {"near", "0"},
+        {"erode", ""}, {"dilate", ""}, {"open", ""}, {"close", ""}, {"refine", ""}, {"relax", ""}, {"renderMesh", "false"}, {"near", "0"},
         {"meshColor", ""}, {"meshForeground", "false"}, {"texture", "0"}, {"atlasWidth", "4096"},
         {"segment", ""}, {"segLo", "120,120,120"}, {"segHi", "255,255,255"}, {"plates", ""}, {"segThreshold", "30"},
         {"segOpen", "0"}, {"segClose", "0"}, {"segMinArea", "0"}, {"segLargest", "false"}, {"segMaxHole", "0"},
@@ -281,6 +281,9 @@ int main(int argc, char *argv[]) {
                      "  -refine=B (in place of the plain mesh: one vertex per cut edge, placed where the edge\n"
                      "    leaves the masks' visual hull by B bisection steps, 0 <= B <= 10; 0: edge midpoints;\n"
                      "    not together with -smooth or -decimate),\n"
+                     "  -relax=N (the mesh the run would write -- refined, decimated, smoothed, else welded --\n"
+                     "    after N Taubin iterations, lambda 0.5, mu -0.53, on whatever mesh that is; -renderMesh,\n"
+                     "    -meshColor and -texture then use the relaxed mesh),\n"
                      "  -visible=true (-color=1|2 over the views in which each voxel is visible),\n"
                      "  -visibleTol=T (its depth tolerance in voxel edges, default 3),\n"
                      "  -misses=K (-carve=1: empty a voxel only when more than K views see it as\n"
@@ -365,6 +368,10 @@ int main(int argc, char *argv[]) {
         }
         if (morphs > 1) {
             std::cerr << "At most one of -erode, -dilate, -open and -close may be given.";
+            return 1;
+        }
+        if (!parser.str("relax").empty() && parser.i("relax") < 0) {
+            std::cerr << "Invalid relax argument.";
             return 1;
         }
         if (!parser.str("refine").empty()) {
@@ -636,7 +643,26 @@ int main(int argc, char *argv[]) {
         // -smooth=N (N > 0): that mesh after N Taubin iterations; -decimate=C (C > 0): the welded
         // (and smoothed) mesh reduced by vertex clustering; -refine=B: marching cubes with one vertex
         // per cut edge, moved to where the edge leaves the masks' visual hull
-        if (!parser.str("refine").empty())
+        // -relax=N: the mesh one of those would write (welded where none is named), relaxed on the device
+        const bool relax = !parser.str("relax").empty();
+        const int base_source = !parser.str("refine").empty() ? ARVX_MESH_REFINED
+                                : parser.i("decimate") > 0    ? ARVX_MESH_DECIMATED
+                                : parser.i("smooth") > 0      ? ARVX_MESH_SMOOTHED
+                                                              : ARVX_MESH_WELDED;
+        if (relax)
+            arvx::detail::marching_cubes_write(
+                &model, parser.f("scale"), modelTranslation, 0.5f, parser.str("outFile"), [&](arvx::Model *m, float t) {
+                    if (base_source == ARVX_MESH_REFINED)
+                        (void)arvx::marchingCubesMeshRefined(in.intr, m, in.views, parser.i("refine"), t);
+                    else if (base_source == ARVX_MESH_DECIMATED)
+                        (void)arvx::marchingCubesMeshDecimated(m, t, parser.i("decimate"), std::max(parser.i("smooth"), 0));
+                    else if (base_source == ARVX_MESH_SMOOTHED)
+                        (void)arvx::marchingCubesMeshSmoothed(m, t, parser.i("smooth"));
+                    else
+                        (void)arvx::marchingCubesMeshWelded(m, t);
+                    return arvx::relaxMesh(m, base_source, parser.i("relax"));
+                });
+        else if (!parser.str("refine").empty())
             arvx::marchingCubesRefined(in.intr, &model, in.views, parser.i("refine"), parser.f("scale"),
                                        modelTranslation, 0.5f, parser.str("outFile"));
         else if (parser.i("decimate") > 0)
@@ -654,6 +680,7 @@ int main(int argc, char *argv[]) {
         // into every view over its input image, then each render's agreement with the view's mask
         // -renderMesh=true: the triangles of the mesh written above instead, with a headlight
         const int mesh_source = !parser.b("renderMesh")          ? -1
+                                : relax                          ? ARVX_MESH_RELAXED
                                 : !parser.str("refine").empty() ? ARVX_MESH_REFINED
                                 : parser.i("decimate") > 0      ? ARVX_MESH_DECIMATED
                                 : parser.i("smooth") > 0        ? ARVX_MESH_SMOOTHED
@@ -680,13 +707,14 @@ int main(int argc, char *argv[]) {
         // -texture=R -atlasWidth=AW: the mesh written above textured from the images, written beside the
         // OFF file with the OFF file's own vertices, and drawn by the renders
         if (parser.i("texture") != 0) {
-            const int source = !parser.str("refine").empty() ? ARVX_MESH_REFINED
+            const int source = relax                         ? ARVX_MESH_RELAXED
+                               : !parser.str("refine").empty() ? ARVX_MESH_REFINED
                                : parser.i("decimate") > 0    ? ARVX_MESH_DECIMATED
                                : parser.i("smooth") > 0      ? ARVX_MESH_SMOOTHED
                                : parser.b("weld")            ? ARVX_MESH_WELDED
                                                              : -1;
             if (source < 0) {
-                std::cerr << "-texture needs a mesh with shared vertices: -weld, -smooth, -decimate or -refine" << std::endl;
+                std::cerr << "-texture needs a mesh with shared vertices: -weld, -smooth, -decimate, -refine or -relax" << std::endl;
                 return 1;
             }
             if (!meshColor.empty()) {
